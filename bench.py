@@ -2,15 +2,21 @@
 """Benchmark: DP cells/s of globalign's hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c4|c4tb|c5|c2|c1]
-                    [--no-cpu-baseline] [--no-extra]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-extra]]
+
+A plain run sets up, warms up, times the K steps and prints the result line: the headline (metric, value,
+ms_per_step), the timed steps' own figures (fill / walk / tie-break milliseconds, the kernels that ran) and the
+cost against the oracle's pin, which is what the metric names.  --dump-outputs DIR also writes what the last timed
+step returned as DIR/<name>.npy.  Everything that takes further runs or checks further references is behind --full:
+the repeated-pair pipeline, the C4 point, the CPU baselines, the roofline block and the alignment pin.
 
 Workloads (BASELINE.json configs, SURVEY 8d SplitMix64 inputs, resident in HBM):
   c3 (default at N=1): 100k x 100k DNA, match 2 / mismatch -3 / open -5 / ext -1, full traceback --
                 the config BASELINE's roofline target is quoted on.  A step is ONE whole
                 find_global_alignment DP call (fill + tie-break table + walk + strings,
-                globaligner.py:258-302), steps run one after another with nothing overlapped; the
-                repeated-pair pipeline is reported beside it as an extra key.  The N=1 line also carries "c4": one GPU's point of
-                the C4 scaling curve.
+                globaligner.py:258-302), steps run one after another with nothing overlapped; with --full the
+                repeated-pair pipeline is reported beside it as an extra key, and the N=1 line also carries "c4":
+                one GPU's point of the C4 scaling curve.
   c4 (default at N>1): 1M x 1M DNA, same scoring, score only.  BASELINE's 1/2/4/8-GPU scaling
                 config: the SAME pair for every N (strong scaling), cut into N column slabs, each fill
                 storing its right edge into the next GPU's memory over xGMI (RCCL row bands as the
@@ -329,6 +335,7 @@ def measure_single(wl, steps, warmup, pipelined=True):
             _, (a, mid, b), status, mt_after = result
             assert status == 0 and a.replace("-", "") == s1 and b.replace("-", "") == s2
             out["aln"] = (a, mid, b)
+            out["status"] = int(status)
             out["mt_after"] = mt_after
             out["latency_ms"] = elapsed * 1e3 / steps
         out["mode"] = "one call per step"
@@ -357,10 +364,34 @@ def traceback_pin(workload, r):
             "matches_oracle": dig == g["aln_sha16"] and len(mid) == g["aln_len"] and st == g["state_sha32"]}
 
 
+DUMP_LIMIT_BYTES = 64_000_000  # all files of one --dump-outputs together
+
+
+def dump_outputs(directory, r):
+    """--dump-outputs: what the LAST timed step returned to its caller, one DIR/<name>.npy each: the cost, and for a
+    traceback workload the three alignment strings (one byte value per element), the call's status and the MT19937
+    words the call left.  float64 holds every one of these integers exactly.  Outputs past the size limit are cut to
+    a fixed, seeded sample of their elements (the same elements in every run)."""
+    arrays = {"cost": np.array([r["cost"]], dtype=np.float64)}
+    if "aln" in r:
+        for name, s in zip(("seq_1_aligned", "middle_part", "seq_2_aligned"), r["aln"]):
+            arrays[name] = np.frombuffer(s.encode("ascii"), dtype=np.uint8).astype(np.float64)
+        arrays["status"] = np.array([r["status"]], dtype=np.float64)
+        arrays["random_state_after"] = np.asarray(r["mt_after"]).astype(np.float64)
+    budget = (DUMP_LIMIT_BYTES // len(arrays) - 128) // 8  # float64 elements per file, beside its 128-byte header
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in arrays.items():
+        if arr.size > budget:
+            arr = arr[np.sort(np.random.default_rng(0).choice(arr.size, size=budget, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), arr)
+
+
 def single_line(args, workload, wl):
     # the headline: consecutive single find_global_alignment-equivalent calls (ga_problem_align), nothing
     # overlapped across steps (for C3-sized problems the recompute walk, DESIGN.md 5.8)
     r = measure_single(wl, args.steps, args.warmup, pipelined=False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r)
     gold = golden_cost(wl.get("golden", workload))
     line = {
         "metric": METRIC,
@@ -378,10 +409,11 @@ def single_line(args, workload, wl):
         "config": {"workload": wl["desc"], "m": wl["m"], "n": wl["n"], "traceback": wl["traceback"],
                    "parallelism": "single GPU", "cost": r["cost"], "oracle_cost": gold,
                    "cost_matches_oracle": (r["cost"] == gold) if gold is not None else None},
-        "roofline": roofline(workload, wl, r["fill_ms"], fill_kind=r.get("fill_kind")),
         "fill_ms": r["fill_ms"],
         "fill_cells_per_s": r["cells"] / (r["fill_ms"] * 1e-3),
     }
+    if args.full:
+        line["roofline"] = roofline(workload, wl, r["fill_ms"], fill_kind=r.get("fill_kind"))
     if wl["traceback"]:
         line["walk_ms"] = r["walk_ms"]
         line["walk_ns_per_step"] = r["walk_ms"] * 1e6 / max(len(r["aln"][1]), 1)
@@ -390,8 +422,9 @@ def single_line(args, workload, wl):
         line["step_mode"] = r["mode"]
         line["fill_kind"] = r.get("fill_kind")
         line["walk_kind"] = r.get("walk_kind")  # 'jump': the tie-to-tie walk
-        line["config"]["traceback_pin"] = traceback_pin(workload, r)
-        if not args.no_extra:
+        if args.full:
+            line["config"]["traceback_pin"] = traceback_pin(workload, r)
+        if args.full and not args.no_extra:
             # the repeated-pair throughput mode (ga_problem_align_many: walk k beside fill k+1, stored words)
             q = measure_single(wl, max(4, args.steps), 2, pipelined=True)
             line["pipelined_repeated_pair"] = {
@@ -400,7 +433,7 @@ def single_line(args, workload, wl):
                 "traceback_pin": traceback_pin(workload, q),
                 "note": "consecutive alignments of the SAME pair with fills in flight beside the walks; not the "
                         "headline (a single call cannot overlap)"}
-    if workload == SINGLE_GPU_DEFAULT and not args.no_extra:
+    if args.full and workload == SINGLE_GPU_DEFAULT and not args.no_extra:
         # one GPU's point of BASELINE's C4 scaling curve (the same pair bench.py --gpus N slabs)
         w4 = WORKLOADS["c4"]
         h = measure_single(w4, max(2, min(args.steps, 5)), 1)
@@ -408,7 +441,7 @@ def single_line(args, workload, wl):
         line["c4"] = {"workload": w4["desc"], "value": h["value"], "unit": "cells/s", "n_gpus": 1,
                       "ms_per_step": h["ms_per_step"], "cost": h["cost"], "cost_matches_oracle": h["cost"] == g4,
                       "fill_ms": h["fill_ms"], "roofline": roofline("c4", w4, h["fill_ms"], fill_kind=h.get("fill_kind"))}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline()
     print(json.dumps(line), flush=True)
 
@@ -443,8 +476,14 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C4 point of the N=1 line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (--gpus 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the repeated-pair pipeline, the C4 "
+                         "point, the CPU baselines, the roofline block, the alignment pin")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the repeated-pair pipeline and the C4 point of the N=1 line")
     ap.add_argument("--opt", action="append", default=[], metavar="GA_NAME=VALUE",
                     help="a context option (ga_ctx_create_opts: kernel variants for experiments); repeatable")
     args = ap.parse_args()
@@ -455,6 +494,10 @@ def main():
             _native.OPTIONS[k] = v
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs writes the single-GPU path's outputs: use it with --gpus 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))

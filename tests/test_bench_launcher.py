@@ -56,6 +56,37 @@ def test_bench_refuses_world_mismatch():
     assert r.returncode == 2 and "launcher started 1 ranks" in r.stderr
 
 
+def test_dump_outputs_writes_what_the_step_returned(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 .npy per output of the last timed step, every value exact; an output past the size
+    limit is cut to the same seeded sample of its elements in every run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    mt = np.arange(625, dtype=np.uint32) * np.uint32(6700417)  # words up to 2^32: exact in float64, not in float32
+    r = {"cost": 2471, "aln": ("AC-GT", "|| .|", "ACTCT"), "status": 0, "mt_after": mt}
+    bench.dump_outputs(str(tmp_path / "a"), r)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["cost", "middle_part", "random_state_after", "seq_1_aligned", "seq_2_aligned", "status"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["cost"].tolist() == [2471.0] and got["status"].tolist() == [0.0]
+    assert bytes(got["seq_1_aligned"].astype(np.uint8)).decode() == "AC-GT"
+    assert bytes(got["middle_part"].astype(np.uint8)).decode() == "|| .|"
+    assert bytes(got["seq_2_aligned"].astype(np.uint8)).decode() == "ACTCT"
+    assert np.array_equal(got["random_state_after"].astype(np.uint32), mt)
+    # a score-only step returns its cost alone
+    bench.dump_outputs(str(tmp_path / "s"), {"cost": 7})
+    assert os.listdir(tmp_path / "s") == ["cost.npy"] and np.load(tmp_path / "s" / "cost.npy").tolist() == [7.0]
+    # past the limit: a sample of budget elements per array, in order, the same in every run
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 6 * 8 * 100)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), dict(r, aln=("A" * 500 + "C" * 500,) * 3))
+    b, c = (np.load(tmp_path / d / "seq_1_aligned.npy") for d in ("b", "c"))
+    assert b.shape == (84,) and np.array_equal(b, c) and np.all(np.diff(b) >= 0) and set(b.tolist()) == {65.0, 67.0}
+    assert np.array_equal(np.load(tmp_path / "b" / "random_state_after.npy"), np.load(tmp_path / "c" / "random_state_after.npy"))
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= 6 * 8 * 100  # the files, headers included, within the limit
+
+
 def test_roofline_profiles_must_match_the_variant_that_ran():
     """bench.roofline divides the committed profile's SQ_INSTS_VALU per launch by the fill's measured time: only when
     the profile (and its VALU mix) are of the kernel variant that ran (columns per lane), else achieved stays null."""

@@ -1,4 +1,4 @@
-# round-end evidence: full GPU suite, the default bench line (C3 pipelined + C4 point + CPU legs), rocprofv3
+# round-end evidence: full GPU suite, the full bench line (bench.py --full: C3 + pipeline + C4 point + CPU legs), rocprofv3
 # kernel stats of it, the C3 lane-kernel traceback fill's and the C4 fill's FETCH/WRITE/SQ passes (each its
 # own run), the walk micro-benchmarks
 set -o pipefail
@@ -6,9 +6,11 @@ export TMPDIR=/tmp
 mkdir -p gpurun_out
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 240 --timeout-method thread > gpurun_out/gpu_check.log 2>&1 || { tail -40 gpurun_out/gpu_check.log; exit 1; }
 tail -1 gpurun_out/gpu_check.log
-timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 > gpurun_out/check_bench.json 2> gpurun_out/check_bench.err || { tail -20 gpurun_out/check_bench.err; exit 1; }
+C=${GA_CHECK_OUT:-check_out}
+mkdir -p $C
+timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 > $C/check_bench.json 2> $C/check_bench.err || { tail -20 $C/check_bench.err; exit 1; }
 for W in c5 c2; do
-  timeout -k 10 200 python -u bench.py --workload $W --no-cpu-baseline --no-extra > gpurun_out/check_bench_$W.json 2> gpurun_out/check_bench_$W.err || { tail -20 gpurun_out/check_bench_$W.err; exit 1; }
+  timeout -k 10 200 python -u bench.py --workload $W --full --no-cpu-baseline --no-extra > $C/check_bench_$W.json 2> $C/check_bench_$W.err || { tail -20 $C/check_bench_$W.err; exit 1; }
 done
 bash tools/profile_c3_lane.sh
 O=gpurun_out/prof3

@@ -7,7 +7,7 @@ O=gpurun_out/prof3
 mkdir -p $O
 timeout -k 10 60 ./tools/micro/walk_chain > $O/walk_chain.txt 2>&1 || { cat $O/walk_chain.txt; exit 1; }
 cat $O/walk_chain.txt
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -o run -- python3 bench.py --no-cpu-baseline --steps 20 --warmup 5 > $O/stats_default.log 2>&1 || { tail -20 $O/stats_default.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -o run -- python3 bench.py --full --no-cpu-baseline --steps 20 --warmup 5 >$O/stats_default.log 2>&1 || { tail -20 $O/stats_default.log; exit 1; }
 export GA_FILL_MODE=lane GA_LANE_COLS_PER_LANE=4 GA_FILL_NWC=4 GA_LANE_QROWS=2048
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch_c3 -o run -- python3 tools/fill_only.py 100000 100000 1 > $O/fetch_c3.log 2>&1 || { tail -20 $O/fetch_c3.log; exit 1; }
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write_c3 -o run -- python3 tools/fill_only.py 100000 100000 1 > $O/write_c3.log 2>&1 || { tail -20 $O/write_c3.log; exit 1; }
