@@ -516,6 +516,9 @@ __global__ void __launch_bounds__(lane_block_threads(NWC)) fill_lane_kernel(Fill
     // the lean sub-chunk's LDS addresses: the producer's counter, the profile table, a scratch slot per lane (the
     // all-lane row stores of lanes that carry no row)
     const unsigned ca_lds = lds_addr(prod_in);
+    // (held in a VGPR: as a uniform value the compiler moved it there again before every second statement)
+    unsigned ca_v;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(ca_v) : "s"(ca_lds));
     const unsigned pq_lds = lds_addr(pq);
     const unsigned scr_lds = lds_addr(smem + LK_SCR_OFF);
     // ... and their loop-invariant per-lane parts, so that a sub-chunk's addresses cost one op each (round 5: the
@@ -569,7 +572,7 @@ __global__ void __launch_bounds__(lane_block_threads(NWC)) fill_lane_kernel(Fill
             avail = sgpr_u(max(avail, pnext));
             if ((int)avail < r0 + 2 * SUB) wait_ge(prod_in, 0, avail, r0 + 2 * SUB, 0);
         }
-        if ((int)qavail < r0 + 2 * SUB) wait_ge(&cnt[LK_PRODQ], 0, qavail, r0 + 2 * SUB, 1);
+        if (__builtin_expect((int)qavail < r0 + 2 * SUB, 0)) wait_ge(&cnt[LK_PRODQ], 0, qavail, r0 + 2 * SUB, 1);
         int eh[SUB], ex[SUB];
 #pragma unroll
         for (int k = 0; k < NE; k++) {
@@ -673,7 +676,7 @@ __global__ void __launch_bounds__(lane_block_threads(NWC)) fill_lane_kernel(Fill
                     const int rlo = r0 - 62;
                     // (a wave-uniform test: compared in a VGPR, the compiler masked exec around the wait, twice a sub-chunk)
                     outfree = sgpr_u(outfree);
-                    if ((int)outfree < rlo + SUB - 1) wait_ge(cons_out, RING, outfree, rlo + SUB - 1, 2);
+                    if (__builtin_expect((int)outfree < rlo + SUB - 1, 0)) wait_ge(cons_out, RING, outfree, rlo + SUB - 1, 2);
                     lk_v4i Ev[NE];
 #pragma unroll
                     for (int k = 0; k < NE; k++) Ev[k] = lk_v4i{C[k].x, C[k].y, C[k].z, C[k].w};
@@ -695,11 +698,11 @@ __global__ void __launch_bounds__(lane_block_threads(NWC)) fill_lane_kernel(Fill
                     lk_v4i En[NE];
                     lk_v2u qn[TD][2];
                     int R[4];
-                    LaneSub<TD, LE ? 12 : 0>::run(H, Y, Xl, HLp, Ev, qc, o, ca_lds, ea, qbv, wa, wb, wc, cp, cv, En, qn, R);
+                    LaneSub<TD, LE ? 12 : 0>::run(H, Y, Xl, HLp, Ev, qc, o, ca_v, ea, qbv, wa, wb, wc, cp, cv, En, qn, R);
                     Hl = H[TD - 1];
                     if (DBG && rlo <= m / 2 && m / 2 < rlo + SUB) t_pub = __builtin_amdgcn_s_memrealtime();
                     const int need = min(r0 + 2 * SUB, m);
-                    if ((int)sgpr_u(cv) < need) {
+                    if (__builtin_expect((int)cv < need, 0)) {  // (cv: an SGPR out of the statement)
                         wait_ge(prod_in, 0, avail, need, 0);
                         asm volatile("" ::: "memory");
                         const int4* src = lane == 0 ? reinterpret_cast<const int4*>(rin + ((r0 + SUB) & RMASK)) : ezero;

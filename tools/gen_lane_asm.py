@@ -91,6 +91,7 @@ def sub_chunk(td, rs):
         no DPP waits on the previous write of its own destination;
       * two ds_write2_b32 of those rows (wa / wb: the ring slots of lanes 48..63 of the register's banks, a scratch
         slot for every other lane) and the counters {cons, prod} (wc, lane 0), all lanes active (no exec change);
+      * the producer's counter moved to an SGPR (v_readfirstlane) after step 15, before the last transposes;
       * one wait for the reads (the three writes may still be in flight).
     Every DPP reads registers written >= 2 VALU earlier (gfx950's wait states; the compiler does not look inside)."""
     def step(s):
@@ -146,6 +147,11 @@ def sub_chunk(td, rs):
                           f"ds_read2_b32 %[qc{k}], %[qb{k}] offset0:8 offset1:12"]
         if s == rs:
             lines += ["ds_read_b32 %[cv], %[ca]"] + [f"ds_read_b128 %[E{k}], %[ea] offset:{16 * k}" for k in range(8)]
+    # the producer's counter into an SGPR while the last transposes run, so that the test after the statement is one
+    # s_cmp and a branch, with no VALU -> SGPR round trip between two statements: LDS returns a wave's reads in order,
+    # so the counter has landed once at most the 8 edge reads after it are outstanding (RS = 0: the profile reads were
+    # issued after them, and everything landed long ago); an SALU reads a readfirstlane's SGPR without a gap
+    lines += [f"s_waitcnt lgkmcnt({8 if rs >= 2 else 0})", "v_readfirstlane_b32 %[cvs], %[cv]"]
     # rows 8..15 (banks 2 and 3) at the end, the two register pairs interleaved
     b2, b3 = chain(2), chain(3)
     for i in range(8):
@@ -156,7 +162,8 @@ def sub_chunk(td, rs):
     outs = [f'[X{s}] "=&v"(X[{s}])' for s in range(16)] + [f'[hn{s}] "=&v"(hn[{s}])' for s in range(16)] + \
            ['[HLn0] "=&v"(HLn[0])', '[HLn1] "=&v"(HLn[1])'] + [f'[H{k}] "+v"(H[{k}])' for k in range(td - 1)] + \
            [f'[Y{k}] "+v"(Y[{k}])' for k in range(td)] + ['[T] "=&v"(T)'] + [f'[M{k}] "=&v"(M[{k}])' for k in range(td)] + \
-           ['[Rha] "=&v"(R[0])', '[Rxa] "=&v"(R[1])', '[Rhb] "=&v"(R[2])', '[Rxb] "=&v"(R[3])', '[cv] "=&v"(cv)'] + \
+           ['[Rha] "=&v"(R[0])', '[Rxa] "=&v"(R[1])', '[Rhb] "=&v"(R[2])', '[Rxb] "=&v"(R[3])'] + \
+           ['[cv] "=&v"(cvt)', '[cvs] "=&s"(cv)'] + \
            [f'[E{k}] "=&v"(En[{k}])' for k in range(8)] + \
            [f'[qa{k}] "=&v"(qn[{k}][0])' for k in range(td)] + [f'[qc{k}] "=&v"(qn[{k}][1])' for k in range(td)]
     ins = ['[Xl] "v"(Xl)', '[HLp] "v"(HLp)', f'[Hlast] "v"(H[{td - 1}])', '[o] "s"(o)'] + \
@@ -168,13 +175,14 @@ def sub_chunk(td, rs):
     return f"""template <>
 struct LaneSub<{td}, {rs}> {{
     // E / q: this sub-chunk's edge rows (lane 0; 0 elsewhere) and profile dwords; En / qn / cv: the next sub-chunk's
-    // (read after step {rs}) and the producer's counter read before them; R: lane 63's rows in lanes 48..63 (banks 1
-    // and 3: R[0] / R[1] = H' / h1', banks 0 and 2: R[2] / R[3])
+    // (read after step {rs}) and the producer's counter read before them (wave-uniform, in an SGPR); R: lane 63's rows
+    // in lanes 48..63 (banks 1 and 3: R[0] / R[1] = H' / h1', banks 0 and 2: R[2] / R[3])
     __device__ __forceinline__ static void run(int (&H)[{td}], int (&Y)[{td}], int& Xl, int& HLp, const lk_v4i (&E)[8],
                                                const uint32_t (&q)[{td}][4], int o, unsigned ca, unsigned ea,
                                                const unsigned (&qb)[{td}], unsigned wa, unsigned wb, unsigned wc, lk_v2u cp,
                                                unsigned& cv, lk_v4i (&En)[8], lk_v2u (&qn)[{td}][2], int (&R)[4]) {{
         int X[16], hn[16], HLn[2], T, M[{td}];
+        unsigned cvt;
         asm volatile(
 {body}
         : {", ".join(outs)}
