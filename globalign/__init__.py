@@ -9,8 +9,8 @@ Every name resolves to the MI355X engine in globalign_amd; the DP fill and trace
 (no CPU fallback).  Install only one of globalign / globalign_amd on a path: this package shadows
 the pure-Python reference of the same name.
 """
-from globalign_amd import (AlignmentResults, GlobalAligner, __version__, dp_array_backward, dp_array_forward,
+from globalign_amd import (AlignmentResults, BatchScores, GlobalAligner, __version__, dp_array_backward, dp_array_forward,
                            find_global_alignment, make_dp_array)
 
-__all__ = ["AlignmentResults", "GlobalAligner", "find_global_alignment", "make_dp_array", "dp_array_forward",
+__all__ = ["AlignmentResults", "BatchScores", "GlobalAligner", "find_global_alignment", "make_dp_array", "dp_array_forward",
            "dp_array_backward", "__version__"]

@@ -40,7 +40,7 @@ class EngineError(RuntimeError):
 
 # every symbol include/globalign_amd.h declares (tests check the exports)
 EXPORTS = [
-    "ga_last_error", "ga_device_count", "ga_ctx_create", "ga_ctx_create_opts", "ga_ctx_destroy", "ga_build_flags", "ga_problem_set", "ga_problem_fill", "ga_problem_set_cells",
+    "ga_last_error", "ga_device_count", "ga_ctx_create", "ga_ctx_create_opts", "ga_ctx_destroy", "ga_build_flags", "ga_problem_set", "ga_problem_fill", "ga_batch_costs", "ga_batch_costs_ex", "ga_problem_set_cells",
     "ga_problem_traceback", "ga_problem_align", "ga_problem_align_many", "ga_problem_set_slab", "ga_slab_buffers", "ga_slab_bind_halos",
     "ga_slab_link", "ga_slab_link_export", "ga_slab_link_import", "ga_enable_peer_access",
     "ga_slab_fill_launch", "ga_slab_fill_finish", "ga_slab_walk_prepare", "ga_slab_walk", "ga_slab_mt_state",
@@ -104,6 +104,8 @@ def load_library():
         L.ga_ctx_destroy.restype = None
         L.ga_problem_set.argtypes = [vp, C.c_char_p, i64, C.c_char_p, i64, C.POINTER(GaCosts), p32, p32]
         L.ga_problem_fill.argtypes = [vp, i32, pi64, p32]
+        L.ga_batch_costs.argtypes = [vp, vp, pi64, i64, p32, p32, i64, C.POINTER(GaCosts), pi64]
+        L.ga_batch_costs_ex.argtypes = [vp, vp, pi64, i64, p32, p32, p32, i64, C.POINTER(GaCosts), pi64]
         L.ga_problem_set_cells.argtypes = [vp, p32, pi64]
         L.ga_problem_traceback.argtypes = [vp, pu32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, i64,
                                            pi64, p32]
@@ -249,6 +251,33 @@ class Engine:
             ptr = out.ctypes.data_as(C.POINTER(C.c_int32))
         _check(self._L.ga_problem_fill(self._h, flags, C.byref(cost), ptr))
         return cost.value, out
+
+    def batch_costs(self, codes, seq_off, pair_a, pair_b, tables, pair_max_cost=None):
+        """Costs of many pairs in one call (ga_batch_costs_ex): codes = every sequence's codes concatenated (uint8),
+        sequence s at codes[seq_off[s]:seq_off[s + 1]]; pair k aligns sequence pair_a[k] with sequence pair_b[k];
+        pair_max_cost: the max_cost of each pair's own costing matrix (None: tables.max_cost for all).
+        -> int64 array of costs, in pair order.  Afterwards no problem counts as loaded."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        seq_off = np.ascontiguousarray(seq_off, dtype=np.int64)
+        pair_a = np.ascontiguousarray(pair_a, dtype=np.int32)
+        pair_b = np.ascontiguousarray(pair_b, dtype=np.int32)
+        if pair_a.shape != pair_b.shape or pair_a.ndim != 1 or seq_off.ndim != 1 or len(seq_off) < 1:
+            raise ValueError("pair_a and pair_b must be 1-d and of equal length, seq_off 1-d and non-empty")
+        if int(seq_off[-1]) != codes.size:
+            raise ValueError("seq_off must end at len(codes)")
+        out = np.zeros(len(pair_a), dtype=np.int64)
+        p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        pmc = None
+        if pair_max_cost is not None:
+            pair_max_cost = np.ascontiguousarray(pair_max_cost, dtype=np.int32)
+            if pair_max_cost.shape != pair_a.shape:
+                raise ValueError("pair_max_cost must have one entry per pair")
+            pmc = pair_max_cost.ctypes.data_as(p32)
+        _check(self._L.ga_batch_costs_ex(self._h, codes.ctypes.data, seq_off.ctypes.data_as(p64), len(seq_off) - 1,
+                                         pair_a.ctypes.data_as(p32), pair_b.ctypes.data_as(p32), pmc, len(pair_a),
+                                         C.byref(tables.struct), out.ctypes.data_as(p64)))
+        self.m = self.n = 0
+        return out
 
     def fill_kind(self):
         """The kernel and geometry of the last fill: (kind, T, nstripes, nwc, nslabs), kind 'row' / 'diag' / 'lane', or

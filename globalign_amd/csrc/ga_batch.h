@@ -1,0 +1,157 @@
+// ga_batch.h -- host-side planning of a batch of score-only alignments (ga_batch_costs; no HIP: built into the engine,
+// into the kernel's translation unit for the work-item layout, and into the planner self-test,
+// ga_batch_selftest.cpp, under AddressSanitizer / UBSan).
+//
+// A batch is a list of sequences (codes concatenated, seq_off[s] .. seq_off[s + 1]) and a list of pairs of sequence
+// indices.  The planner checks every pair as check_problem (ga_check.h) checks a single problem -- with that pair's
+// own sentinel big = (max_cost + 1) * max(m, n) -- and turns the pairs into a work list for batch_fill_kernel
+// (ga_batch.hip, one wave per pair), longest first, plus the pairs that go to the single-pair score fill instead.
+#pragma once
+#include <stdint.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "ga_check.h"
+
+// One pair as the kernel takes it (a wave reads it with one uniform 32-byte load).
+struct ga_batch_item {
+    int32_t a_off, m;    // seq_1: codes[a_off .. a_off + m)
+    int32_t b_off, n;    // seq_2: codes[b_off .. b_off + n)
+    int32_t big;         // this pair's sentinel (globaligner.py:777)
+    int32_t out;         // index into the caller's pair list (the cost goes to cost_out[out])
+    int32_t T, nstripes; // columns per lane; stripes of 64 * T columns, left to right in the same wave
+};
+
+namespace gabatch {
+
+constexpr int kMaxT = 8;                    // widest stripe: 512 columns
+constexpr int kLdsEdgeRows = 1024;          // rows of a wave's edge column kept in LDS
+constexpr int kLdsTableBytes = 16 * 1024;   // LDS budget of the sub' table (K * K entries of qbytes)
+constexpr int kWavesPerGroup = 4;
+// Pairs above this many cells take the single-pair fill (GA_BATCH_MAX_CELLS overrides).  Not the measured crossover
+// of a lone pair (about 2.7e5 cells) but a value reasoned from that measurement: single-pair fills run one after the
+// other while the kernel's pairs run side by side.
+constexpr int64_t kDefaultMaxCells = 1 << 20;
+constexpr int64_t kScratchBytesCap = 256ll << 20;  // HBM edge scratch of one launch, all waves
+
+// Stripe geometry of a pair with n columns: the fewest stripes of at most 64 * kMaxT columns, then the narrowest T
+// that covers n with them (a 300-column pair is one stripe at T = 5).
+inline void stripe_geometry(int64_t n, int& T, int& nstripes) {
+    nstripes = (int)((n + 64 * kMaxT - 1) / (64 * kMaxT));
+    T = (int)((n + 64ll * nstripes - 1) / (64ll * nstripes));
+}
+
+// A pair's edge column lives in HBM scratch when it has a second stripe to hand an edge to and more rows than the
+// wave's LDS share holds.
+inline bool needs_scratch(int64_t m, int64_t n) { return n > 64 * kMaxT && m > kLdsEdgeRows; }
+
+inline bool table_fits_lds(int K, int qbytes) { return (int64_t)K * K * qbytes <= kLdsTableBytes; }
+
+struct Limits {
+    int64_t max_cells = kDefaultMaxCells;  // 0: every pair to the single-pair fill
+    int64_t scratch_rows_cap = 0;          // most rows of HBM edge column a wave may be given
+};
+
+struct Plan {
+    std::vector<ga_batch_item> kernel;  // batch_fill_kernel's work list: cells descending, ties in input order
+    std::vector<int64_t> single;        // pair indices for the single-pair fill, in the same order
+    int64_t scratch_rows = 0;           // rows per wave and ping-pong slice of the HBM edge scratch (0: none)
+    int qbytes = 1;                     // bytes per entry of the kernel's sub' table: 1, 2 or 4
+};
+
+// The most rows a wave's scratch slice may have with `waves` resident waves (two ping-pong slices of int2 rows each).
+inline int64_t scratch_rows_cap(int64_t waves) { return kScratchBytesCap / (std::max<int64_t>(waves, 1) * 2 * 8); }
+
+// One pair's range check: check_problem's guard with the pair's own big, from the pair's own max_cost (the largest
+// entry of the costing matrix the single call would build for this pair).  GA_OK or GA_E_RANGE.
+inline int check_pair_range(int64_t m, int64_t n, const ga_costs* cs, int64_t max_cost, int64_t maxabs,
+                            int64_t& big_out) {
+    const int64_t big = (max_cost + 1) * std::max(m, n);
+    big_out = big;
+    return range_fits(range_bound(std::llabs(big), m, n, maxabs, cs->gap_open)) ? GA_OK : GA_E_RANGE;
+}
+
+// GA_OK and the plan, or the code the single-pair path gives for the first failing pair (input order) with
+// "pair <index>: <reason>" in err.  pair_max_cost: per pair, the max_cost of that pair's own costing matrix (a
+// match / mismatch matrix over one letter has no mismatch entry, so its maximum -- and with it big -- is smaller);
+// nullptr: cs->max_cost for every pair.
+inline int plan_batch(const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                      const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                      const Limits& lim, Plan& out, std::string& err) {
+    auto fail = [&](int code, const std::string& msg) {
+        err = msg;
+        return code;
+    };
+    out = Plan();
+    if (npairs < 0 || nseq < 0) return fail(GA_E_ARG, "negative count");
+    if (npairs == 0) return GA_OK;
+    if (npairs > (int64_t)INT32_MAX) return fail(GA_E_RANGE, "a batch holds at most 2^31 - 1 pairs");
+    if (!codes || !seq_off || !pair_a || !pair_b || !cs || !cs->sub || !cs->gap_h || !cs->gap_v)
+        return fail(GA_E_ARG, "null argument");
+    const int K = cs->K;
+    if (K < 1 || K > 255) return fail(GA_E_ARG, "alphabet size K must be in [1,255]");
+    if (cs->gap_open < 0) return fail(GA_E_ARG, "gap_open cost must be >= 0");
+    if (seq_off[0] != 0) return fail(GA_E_ARG, "seq_off must start at 0");
+    for (int64_t s = 0; s < nseq; s++)
+        if (seq_off[s + 1] < seq_off[s]) return fail(GA_E_ARG, "seq_off must not decrease");
+    if (seq_off[nseq] > (int64_t)INT32_MAX) return fail(GA_E_RANGE, "a batch holds at most 2^31 - 1 codes");
+    // a sequence's codes are checked once, however many pairs use it
+    std::vector<uint8_t> bad(nseq, 0);
+    for (int64_t s = 0; s < nseq; s++)
+        for (int64_t q = seq_off[s]; q < seq_off[s + 1]; q++)
+            if (codes[q] >= K) {
+                bad[s] = 1;
+                break;
+            }
+    const int64_t maxabs = costs_maxabs(cs);
+    // sub' beyond the single-pair fill's int16 query profile: the batch kernel then reads 4-byte table entries (a
+    // pair routed to the single-pair fill fails there, as a single call does)
+    const int qbytes = profile_bytes(cs) ? profile_bytes(cs) : 4;
+    const int o = cs->gap_open;
+    const bool o_fits = (o + 1) < 32768;  // the single path's traceback-word limit holds for a score too
+    struct Cand {
+        int64_t cells, idx, big;
+    };
+    std::vector<Cand> cand((size_t)npairs);
+    for (int64_t k = 0; k < npairs; k++) {
+        auto at = [k](const char* why) { return "pair " + std::to_string(k) + ": " + why; };
+        const int64_t sa = pair_a[k], sb = pair_b[k];
+        if (sa < 0 || sa >= nseq || sb < 0 || sb >= nseq) return fail(GA_E_ARG, at("sequence index out of range"));
+        const int64_t m = seq_off[sa + 1] - seq_off[sa], n = seq_off[sb + 1] - seq_off[sb];
+        if (m < 1 || n < 1) return fail(GA_E_ARG, at("sequences must be non-empty"));
+        if (bad[sa]) return fail(GA_E_ARG, at("seq_1 code out of range"));
+        if (bad[sb]) return fail(GA_E_ARG, at("seq_2 code out of range"));
+        int64_t big = 0;
+        if (check_pair_range(m, n, cs, pair_max_cost ? pair_max_cost[k] : cs->max_cost, maxabs, big))
+            return fail(GA_E_RANGE, at("problem exceeds the int32 score range of the device path"));
+        if (!o_fits) return fail(GA_E_RANGE, at("gap_open cost too large for the traceback word"));
+        cand[(size_t)k] = Cand{m * n, k, big};
+    }
+    out.qbytes = qbytes;
+    std::stable_sort(cand.begin(), cand.end(), [](const Cand& x, const Cand& y) { return x.cells > y.cells; });
+    const bool tab_ok = table_fits_lds(K, qbytes);
+    for (const Cand& cd : cand) {
+        const int64_t sa = pair_a[cd.idx], sb = pair_b[cd.idx];
+        const int64_t m = seq_off[sa + 1] - seq_off[sa], n = seq_off[sb + 1] - seq_off[sb];
+        const bool scr = needs_scratch(m, n);
+        if (cd.cells > lim.max_cells || !tab_ok || (scr && m > lim.scratch_rows_cap)) {
+            out.single.push_back(cd.idx);
+            continue;
+        }
+        ga_batch_item it;
+        it.a_off = (int32_t)seq_off[sa];
+        it.m = (int32_t)m;
+        it.b_off = (int32_t)seq_off[sb];
+        it.n = (int32_t)n;
+        it.big = (int32_t)cd.big;  // range_fits: |big| < 2^29
+        it.out = (int32_t)cd.idx;
+        stripe_geometry(n, it.T, it.nstripes);
+        out.kernel.push_back(it);
+        if (scr) out.scratch_rows = std::max(out.scratch_rows, m);
+    }
+    return GA_OK;
+}
+
+}  // namespace gabatch

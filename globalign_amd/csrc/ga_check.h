@@ -20,6 +20,34 @@ struct ProblemShape {
     int CB = 1;       // traceback word bytes per cell: 1 / 2 / 4 for o + 1 < 8 / 128 / 32768
 };
 
+// The int32 range guard, shared by check_problem and the batch planner (ga_batch.h): the largest
+// magnitude in the cost tables, the bound on every stored value and intermediate of a problem whose boundary values
+// stay within bmax, and whether that bound keeps clear of overflow.
+inline int64_t costs_maxabs(const ga_costs* cs) {
+    const int K = cs->K;
+    int64_t maxabs = 0;
+    for (int q = 0; q < K * K; q++) maxabs = std::max<int64_t>(maxabs, std::llabs((long long)cs->sub[q]));
+    for (int q = 0; q < K; q++) {
+        maxabs = std::max<int64_t>(maxabs, std::llabs((long long)cs->gap_h[q]));
+        maxabs = std::max<int64_t>(maxabs, std::llabs((long long)cs->gap_v[q]));
+    }
+    return maxabs;
+}
+inline int64_t range_bound(int64_t bmax, int64_t m, int64_t n, int64_t maxabs, int64_t gap_open) {
+    return bmax + (m + n + 2) * (3 * maxabs + gap_open);
+}
+inline bool range_fits(int64_t bound) { return 4 * bound < (int64_t)INT32_MAX; }
+// bytes of a query-profile entry: 1 or 2 by the largest |sub'| = |sub - gV - gH|, 0 when it exceeds int16
+inline int profile_bytes(const ga_costs* cs) {
+    const int K = cs->K;
+    int64_t subp_max = 0;
+    for (int x = 0; x < K; x++)
+        for (int y = 0; y < K; y++)
+            subp_max = std::max<int64_t>(subp_max,
+                                         std::llabs((long long)cs->sub[x * K + y] - cs->gap_v[x] - cs->gap_h[y]));
+    return subp_max <= 127 ? 1 : subp_max <= 32767 ? 2 : 0;
+}
+
 // GA_OK, or GA_E_ARG / GA_E_RANGE with the reason in err.  cb, ce: the column slab [cb, ce) of seq_2 this context
 // fills (the whole problem: 0, n_all); row0 / col0: caller-supplied boundary triples (both or neither).
 inline int check_problem(const uint8_t* a, int64_t m, const uint8_t* b_all, int64_t n_all, const ga_costs* cs,
@@ -42,26 +70,16 @@ inline int check_problem(const uint8_t* a, int64_t m, const uint8_t* b_all, int6
         if (b_all[j] >= K) return fail(GA_E_ARG, "seq_2 code out of range");
     // int32 range guard: every stored value, shifted or not, and every intermediate (value + o) must
     // stay far from overflow
-    int64_t maxabs = 0;
-    for (int q = 0; q < K * K; q++) maxabs = std::max<int64_t>(maxabs, std::llabs((long long)cs->sub[q]));
-    for (int q = 0; q < K; q++) {
-        maxabs = std::max<int64_t>(maxabs, std::llabs((long long)cs->gap_h[q]));
-        maxabs = std::max<int64_t>(maxabs, std::llabs((long long)cs->gap_v[q]));
-    }
+    const int64_t maxabs = costs_maxabs(cs);
     const int64_t big = ((int64_t)cs->max_cost + 1) * std::max(m, n_all);
     int64_t bmax = std::llabs(big);
     if (row0)
         for (int64_t q = 0; q < 3 * (n_all + 1); q++) bmax = std::max<int64_t>(bmax, std::llabs((long long)row0[q]));
     if (col0)
         for (int64_t q = 0; q < 3 * (m + 1); q++) bmax = std::max<int64_t>(bmax, std::llabs((long long)col0[q]));
-    const int64_t bound = bmax + (m + n_all + 2) * (3 * maxabs + (int64_t)cs->gap_open);
-    if (4 * bound >= (int64_t)INT32_MAX) return fail(GA_E_RANGE, "problem exceeds the int32 score range of the device path");
-    int64_t subp_max = 0;
-    for (int x = 0; x < K; x++)
-        for (int y = 0; y < K; y++)
-            subp_max = std::max<int64_t>(subp_max,
-                                         std::llabs((long long)cs->sub[x * K + y] - cs->gap_v[x] - cs->gap_h[y]));
-    out.qbytes = subp_max <= 127 ? 1 : subp_max <= 32767 ? 2 : 0;
+    if (!range_fits(range_bound(bmax, m, n_all, maxabs, cs->gap_open)))
+        return fail(GA_E_RANGE, "problem exceeds the int32 score range of the device path");
+    out.qbytes = profile_bytes(cs);
     if (!out.qbytes) return fail(GA_E_RANGE, "substitution costs exceed the int16 query profile");
     const int o = cs->gap_open;
     out.CB = (o + 1) < 8 ? 1 : (o + 1) < 128 ? 2 : (o + 1) < 32768 ? 4 : 0;

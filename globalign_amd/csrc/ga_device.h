@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct ga_batch_item;  // ga_batch.h
+
 namespace ga {
 
 // Row-scan fill: a workgroup = NWC compute waves (4 or 8) + 1 IO wave.
@@ -205,5 +207,11 @@ void launch_fill_lane(hipStream_t s, const FillArgs& p, int CB);
 size_t fill_lane_lds_bytes(int nwc, int K, int qrows);
 // the lane fill's query profile (FillArgs::qprof) of rows a[0 .. m-1]: K x (m + 4) dwords at out
 void launch_lane_qprof(hipStream_t s, const uint8_t* a, int m, const int* subp, int K, uint32_t* out);
+// many score-only pairs in one launch, one wave per pair (ga_batch.hip): `items` is the planner's
+// work list (ga_batch.h), `waves` the resident waves the grid and the edge scratch ([waves][2][scratch_rows] int2,
+// nullptr when no pair needs it) are sized for, `ticket` a word the caller zeroes ahead of every launch
+void launch_batch_fill(hipStream_t s, const uint8_t* codes, const ga_batch_item* items, int nitems, const int* subp,
+                       const int* gh, const int* gv, int K, int o, int qbytes, unsigned* ticket, long long* cost_out,
+                       int2* scratch, long long scratch_rows, int waves);
 
 }  // namespace ga

@@ -29,6 +29,7 @@
 #include "ga_device.h"
 #include "ga_lane.h"
 #include "ga_check.h"
+#include "ga_batch.h"
 #include "ga_rng.h"
 
 namespace {
@@ -203,6 +204,9 @@ struct ga_ctx {
     // the recompute walk: the score fill's checkpoints, the tile cache, the blocks' flags
     DevBuf colck, stck, rc_tb, rc_flags, rc_pos, rc_own;
     DevBuf qprof;  // the lane fill's query profile (ga::launch_lane_qprof), rebuilt by every lane fill
+    // ga_batch_costs: buffers of its own, so a loaded problem's stay as they are -- every sequence's
+    // codes, the work list, sub' / gap tables, the ticket word, the costs, the waves' HBM edge columns
+    DevBuf bt_codes, bt_items, bt_sub, bt_gh, bt_gv, bt_ticket, bt_out, bt_scratch;
     int walk_jump_diag[3] = {0, 0, 0};  // the tie-to-tie walk's trips, region re-checks, ties (result[12..14])
     DevBuf jlut;           // the jump workers' LUT for gap open jlut_o (ga::jump_lut_build)
     int jlut_o = -1;
@@ -2259,7 +2263,8 @@ void ga_ctx_destroy(ga_ctx* c) {
     for (DevBuf* b : {&c->a, &c->b, &c->sub, &c->gh, &c->gv, &c->qp, &c->GVp, &c->GHp, &c->top, &c->left, &c->bnd_row,
                       &c->bnd_col, &c->meta, &c->hand, &c->flags, &c->tb, &c->out_last, &c->full, &c->rng, &c->ops,
                       &c->result, &c->halo_in, &c->dbg, &c->wdbg, &c->bscr, &c->ckpt, &c->colck, &c->stck,
-                      &c->rc_tb, &c->rc_flags, &c->rc_pos, &c->rc_own, &c->link, &c->qprof})
+                      &c->rc_tb, &c->rc_flags, &c->rc_pos, &c->rc_own, &c->link, &c->qprof, &c->bt_codes, &c->bt_items,
+                      &c->bt_sub, &c->bt_gh, &c->bt_gv, &c->bt_ticket, &c->bt_out, &c->bt_scratch})
         b->release();
     if (c->prog_host) (void)hipHostFree(c->prog_host);
     if (c->peer_link) (void)hipIpcCloseMemHandle(c->peer_link);
@@ -2313,6 +2318,91 @@ int ga_problem_fill(ga_ctx* c, int32_t flags, int64_t* cost_out, int32_t* full_o
     if ((flags & GA_FILL_FULL) && !full_out) return fail(GA_E_ARG, "GA_FILL_FULL needs full_out");
     if (int r = enqueue_fill(c, flags)) return r;
     return finish_fill(c, cost_out, (flags & GA_FILL_FULL) ? full_out : nullptr);
+}
+
+int ga_batch_costs(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                   const int32_t* pair_b, int64_t npairs, const ga_costs* cs, int64_t* cost_out) {
+    return ga_batch_costs_ex(c, codes, seq_off, nseq, pair_a, pair_b, nullptr, npairs, cs, cost_out);
+}
+
+int ga_batch_costs_ex(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                      const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                      int64_t* cost_out) {
+    if (int r = check_ctx(c)) return r;
+    if (npairs == 0) return GA_OK;  // an empty batch: no launch
+    if (!cost_out) return fail(GA_E_ARG, "null argument");
+    // resident waves: two per SIMD on every CU, and the planner's routing limits
+    const int64_t max_waves = (int64_t)c->num_cu * 4 * 2;
+    gabatch::Limits lim;
+    if (const char* e = c->knob("GA_BATCH_MAX_CELLS")) lim.max_cells = std::max<int64_t>(0, atoll(e));
+    lim.scratch_rows_cap = gabatch::scratch_rows_cap(max_waves);
+    gabatch::Plan plan;
+    std::string why;
+    if (int r = gabatch::plan_batch(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim, plan, why))
+        return fail(r, why);
+    const int K = cs->K;
+    if (!plan.kernel.empty()) {
+        const int nitems = (int)plan.kernel.size();
+        // never more waves than pairs; whole workgroups
+        const int W = gabatch::kWavesPerGroup;
+        const int waves = (int)((std::min<int64_t>(max_waves, nitems) + W - 1) / W * W);
+        std::vector<int> subp((size_t)K * K);
+        for (int x = 0; x < K; x++)
+            for (int y = 0; y < K; y++) subp[x * K + y] = cs->sub[x * K + y] - cs->gap_v[x] - cs->gap_h[y];
+        const size_t ncodes = (size_t)seq_off[nseq];
+        HIPCHK(c->bt_codes.ensure(ncodes));
+        HIPCHK(c->bt_items.ensure(sizeof(ga_batch_item) * nitems));
+        HIPCHK(c->bt_sub.ensure(sizeof(int) * K * K));
+        HIPCHK(c->bt_gh.ensure(sizeof(int) * K));
+        HIPCHK(c->bt_gv.ensure(sizeof(int) * K));
+        HIPCHK(c->bt_ticket.ensure(sizeof(unsigned)));
+        HIPCHK(c->bt_out.ensure(sizeof(long long) * npairs));
+        if (plan.scratch_rows > 0) HIPCHK(c->bt_scratch.ensure(sizeof(int2) * 2 * plan.scratch_rows * waves));
+        HIPCHK(hipMemcpyAsync(c->bt_codes.p, codes, ncodes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->bt_items.p, plan.kernel.data(), sizeof(ga_batch_item) * nitems, hipMemcpyHostToDevice,
+                              c->stream));
+        HIPCHK(hipMemcpyAsync(c->bt_sub.p, subp.data(), sizeof(int) * K * K, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->bt_gh.p, cs->gap_h, sizeof(int) * K, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->bt_gv.p, cs->gap_v, sizeof(int) * K, hipMemcpyHostToDevice, c->stream));
+        // the ticket starts at zero for every launch (no last-arriver reset to rely on)
+        HIPCHK(hipMemsetAsync(c->bt_ticket.p, 0, sizeof(unsigned), c->stream));
+        HIPCHK(hipEventRecord(c->ev[0], c->stream));
+        ga::launch_batch_fill(c->stream, c->bt_codes.as<uint8_t>(), c->bt_items.as<ga_batch_item>(), nitems,
+                              c->bt_sub.as<int>(), c->bt_gh.as<int>(), c->bt_gv.as<int>(), K, cs->gap_open, plan.qbytes,
+                              c->bt_ticket.as<unsigned>(), c->bt_out.as<long long>(),
+                              plan.scratch_rows > 0 ? c->bt_scratch.as<int2>() : nullptr, plan.scratch_rows, waves);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->ev[1], c->stream));
+        std::vector<long long> got((size_t)npairs);
+        HIPCHK(hipMemcpyAsync(got.data(), c->bt_out.p, sizeof(long long) * npairs, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipEventElapsedTime(&c->fill_ms, c->ev[0], c->ev[1]));
+        for (const ga_batch_item& it : plan.kernel) {
+            if (got[(size_t)it.out] == INT64_MIN)
+                return fail(GA_E_STATE, "pair " + std::to_string(it.out) + ": work item does not fit the batch launch");
+            cost_out[it.out] = got[(size_t)it.out];
+        }
+    }
+    if (!plan.single.empty()) {
+        // the existing score fill, one pair at a time (as ga_problem_set + ga_problem_fill): it goes through the
+        // context's problem slot, so no problem is loaded afterwards.  A slab context keeps its slab: refused.
+        if (c->slab)
+            return fail(GA_E_STATE, "pair " + std::to_string(plan.single[0]) +
+                                        ": needs the single-pair fill, which a slab context cannot run");
+        c->rc_used = false;
+        for (const int64_t k : plan.single) {
+            const int64_t sa = pair_a[k], sb = pair_b[k];
+            const int64_t m = seq_off[sa + 1] - seq_off[sa], n = seq_off[sb + 1] - seq_off[sb];
+            ga_costs own = *cs;  // this pair's sentinel comes from its own max_cost
+            if (pair_max_cost) own.max_cost = pair_max_cost[k];
+            int r = load_problem(c, codes + seq_off[sa], m, codes + seq_off[sb], n, &own, nullptr, nullptr, 0, n);
+            if (!r) r = enqueue_fill(c, 0);
+            if (!r) r = finish_fill(c, &cost_out[k], nullptr);
+            c->loaded = false;
+            if (r) return fail(r, "pair " + std::to_string(k) + ": " + g_err);
+        }
+    }
+    return GA_OK;
 }
 
 int ga_problem_set_cells(ga_ctx* c, const int32_t* cells, int64_t* cost_out) {

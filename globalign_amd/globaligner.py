@@ -16,6 +16,7 @@ process-global ``random`` state exactly like the reference (18
 ``random.seed`` the alignment strings are identical.
 """
 import argparse
+import math
 import random
 import sys
 from pathlib import Path
@@ -23,7 +24,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _native
-from .results import AlignmentResults, final_cost_to_score
+from .results import AlignmentResults, BatchScores, final_cost_to_score
 from .scoring import MAX_SEQ_LEN_PROD, get_max_val, validate_and_transform_args
 
 __version__ = "0.1.0"
@@ -107,6 +108,163 @@ class GlobalAligner:
             score = final_cost_to_score(cost=cost, m=len(s1), n=len(s2), max_score=get_max_val(scoring_mat))
             out.append(AlignmentResults(a, mid, b, cost, score, scoring_mat, costing_mat, gos, goc, output))
         return out
+
+    def score_pairs(self, seqs_1, seqs_2):
+        """Costs and scores of seqs_1[k] aligned with seqs_2[k] for every k, in one call: no alignment strings, no
+        use of the global random state.  costs[k] / scores[k] equal .cost / .score of
+        GlobalAligner(traceback=False, ...).align(seqs_1[k], seqs_2[k]) under this aligner's settings.
+        -> BatchScores with arrays of shape (len(seqs_1),)."""
+        seqs_1, seqs_2 = list(seqs_1), list(seqs_2)
+        if len(seqs_1) != len(seqs_2):
+            raise ValueError(f"score_pairs needs as many first as second sequences, got {len(seqs_1)} and "
+                             f"{len(seqs_2)}")
+        P = len(seqs_1)
+        return self._score_batch(seqs_1 + seqs_2, np.arange(P, dtype=np.int64), np.arange(P, 2 * P, dtype=np.int64),
+                                 (P,))
+
+    def score_matrix(self, seqs, seqs_2=None):
+        """Costs and scores of every seqs[i] aligned with every seqs_2[j] (seqs_2=None: seqs against itself).  All
+        N1 x N2 entries are computed: costs are not symmetric in general (the vertical and horizontal gap costs of
+        a transformed scoring matrix differ when its maximum is odd).  -> BatchScores with (N1, N2) arrays."""
+        seqs = list(seqs)
+        rows = np.arange(len(seqs), dtype=np.int64)
+        if seqs_2 is None:
+            cols = rows
+        else:
+            seqs_2 = list(seqs_2)
+            cols = np.arange(len(seqs), len(seqs) + len(seqs_2), dtype=np.int64)
+            seqs = seqs + seqs_2
+        return self._score_batch(seqs, np.repeat(rows, len(cols)), np.tile(cols, len(rows)), (len(rows), len(cols)))
+
+    def _empty_batch(self, shape):
+        """No pairs: empty arrays, no launch.  The option checks still run, through the single call's validation of
+        a placeholder pair; the matrices are reported only where they do not depend on the sequences (a named or
+        file matrix)."""
+        empty = np.zeros(shape, dtype=np.int64)
+        from_matrix = self.settings["scoring_mat_name"] is not None or self.settings["scoring_mat_path"] is not None
+        try:
+            _, _, smat, cmat, gos, goc, _ = validate_and_transform_args(None, None, "A", "A", max_seq_len_prod=None,
+                                                                        **self.settings)
+        except RuntimeError as e:
+            if not (from_matrix and str(e).startswith("common_alphabet contains values")):
+                raise
+            # (a file matrix without the placeholder's letter: every option check had passed by then)
+            return BatchScores(empty, empty.copy(), None, None, None, None)
+        if not from_matrix:
+            smat = cmat = None
+        return BatchScores(empty, empty.copy(), smat, cmat, gos, goc)
+
+    def _score_batch(self, seqs, pair_a, pair_b, shape):
+        """seqs[pair_a[k]] against seqs[pair_b[k]] for every k.  Validation is the single call's, per pair and in
+        pair order, before any engine exists; the options and the score -> cost transform run once."""
+        if len(self.devices) > 1:
+            raise ValueError("score_pairs / score_matrix run on one GPU; this aligner was made with devices="
+                             f"{self.devices}")
+        if len(pair_a) == 0:
+            return self._empty_batch(shape)
+        try:
+            joined = "".join(seqs)
+        except TypeError:
+            raise TypeError("sequences must be str") from None
+
+        def single_call(k):
+            return validate_and_transform_args(None, None, seqs[pair_a[k]], seqs[pair_b[k]],
+                                               max_seq_len_prod=self.max_seq_len_prod, **self.settings)
+
+        # pair 0 as the single call validates it: its own faults first, then whatever does not depend on the sequences
+        # (option combinations, the matrix file)
+        _, _, scoring_mat, costing_mat, gap_open_score, gap_open_cost, _ = single_call(0)
+        from_matrix = self.settings["scoring_mat_name"] is not None or self.settings["scoring_mat_path"] is not None
+        # The other pairs: find the first one the single call would refuse, and let the single call refuse it.  The
+        # whole batch is looked at as one string (one upper(), one byte histogram), the sequences one by one only
+        # when something in it is wrong.
+        raw_len = np.fromiter(map(len, seqs), dtype=np.int64, count=len(seqs))
+        upper = joined.upper()
+        lens = raw_len
+        if len(upper) != len(joined):  # (a letter whose upper case is longer: per sequence)
+            lens = np.fromiter((len(s.upper()) for s in seqs), dtype=np.int64, count=len(seqs))
+        # what the batch holds beyond pair 0's tables (its alphabet, or the matrix's letters): other letters, and '-'
+        keys = set(scoring_mat.keys()) - {"-"}
+        try:
+            text = upper.encode("latin-1")
+            extra = set(text.translate(None, bytes(ord(k) for k in keys if len(k) == 1 and ord(k) < 256)).decode("latin-1"))
+        except UnicodeEncodeError:
+            text = None
+            extra = set(upper) - keys
+        dash = "-" in extra
+        extra.discard("-")
+        unknown = extra if from_matrix else set()
+        prod = raw_len[pair_a] * raw_len[pair_b]
+        bad = prod == 0
+        if self.max_seq_len_prod is not None:
+            bad |= ~(prod < self.max_seq_len_prod)
+        if dash or unknown:
+            flagged = np.fromiter(("-" in s or not unknown.isdisjoint(s.upper()) for s in seqs), dtype=bool,
+                                  count=len(seqs))
+            bad |= flagged[pair_a] | flagged[pair_b]
+        if bad.any():
+            k = int(np.argmax(bad))
+            single_call(k)
+            raise RuntimeError(f"pair {k} failed validation")  # (the single call raises before this)
+        if not from_matrix and extra:
+            # match / mismatch tables over the whole batch's alphabet: they are constant off the diagonal, so every
+            # entry a pair reads is what its own alphabet's tables hold (the maximum is another matter, below)
+            alphabet = "".join(sorted(keys | extra))
+            _, _, scoring_mat, costing_mat, gap_open_score, gap_open_cost, _ = validate_and_transform_args(
+                None, None, alphabet, alphabet, max_seq_len_prod=None, **self.settings)
+        tables = _native.CostTables(costing_mat, gap_open_cost)
+        seq_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        # A pair made of ONE letter: the single call builds its match / mismatch matrices over that letter alone, and
+        # they hold no mismatch entry, so their maxima -- the sentinel big = (max_cost + 1) * max(m, n) and the
+        # score's deltas come from them -- differ from the batch tables'.  Such pairs get their own.
+        max_score = get_max_val(scoring_mat)
+        delta_d, delta_i, pair_max_cost = math.floor(max_score / 2), math.ceil(max_score / 2), None
+        if not from_matrix and len(keys | extra) > 1:
+            letter = _one_letter_sequences(upper, text, seq_off)
+            one = (letter[pair_a] >= 0) & (letter[pair_a] == letter[pair_b])
+            if one.any():
+                x = upper[0]
+                _, _, smat_1, cmat_1, _, _, _ = validate_and_transform_args(None, None, x, x, max_seq_len_prod=None,
+                                                                            **self.settings)
+                pair_max_cost = np.where(one, int(get_max_val(cmat_1)), tables.max_cost).astype(np.int32)
+                b1 = get_max_val(smat_1)
+                delta_d = np.where(one, math.floor(b1 / 2), delta_d).astype(np.int64)
+                delta_i = np.where(one, math.ceil(b1 / 2), delta_i).astype(np.int64)
+        if text is not None:
+            lut = bytearray(256)
+            for ch, code in tables.code.items():
+                if len(ch) == 1 and ord(ch) < 256:
+                    lut[ord(ch)] = code
+            codes = np.frombuffer(text.translate(bytes(lut)), dtype=np.uint8)
+        else:
+            codes = np.fromiter((tables.code[ch] for ch in upper), dtype=np.uint8, count=len(upper))
+        eng = _native.default_engine(self.device)
+        costs = eng.batch_costs(codes, seq_off, pair_a, pair_b, tables, pair_max_cost)
+        scores = final_cost_to_score(cost=costs, m=lens[pair_a], n=lens[pair_b], max_score=max_score, delta_d=delta_d,
+                                     delta_i=delta_i)
+        return BatchScores(costs.reshape(shape), np.asarray(scores, dtype=np.int64).reshape(shape), scoring_mat,
+                           costing_mat, gap_open_score, gap_open_cost)
+
+
+def _one_letter_sequences(upper, text, seq_off):
+    """Per sequence of the batch (upper: all of them joined, text: the same as latin-1 bytes or None, seq_off: where
+    each starts), the code point of its letter if it consists of one letter only, else -1."""
+    starts, ends = seq_off[:-1], seq_off[1:]
+    out = np.full(len(starts), -1, dtype=np.int64)
+    if text is None:
+        for s in range(len(starts)):
+            u = upper[starts[s]:ends[s]]
+            if u.count(u[0]) == len(u):
+                out[s] = ord(u[0])
+        return out
+    arr = np.frombuffer(text, dtype=np.uint8)
+    # only a sequence whose second letter equals its first can be one: the others are settled without a look
+    maybe = arr[np.minimum(starts + 1, ends - 1)] == arr[starts]
+    for s in np.flatnonzero(maybe):
+        seg = text[starts[s]:ends[s]]
+        if seg.count(seg[:1]) == len(seg):
+            out[s] = seg[0]
+    return out
 
 
 def _align_validated(good, device=0, traceback=True, devices=None):

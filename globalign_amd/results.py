@@ -47,6 +47,17 @@ def prettify_mat(mat):
     return "".join(parts)
 
 
+class BatchScores(NamedTuple):
+    """Costs and scores of many pairs (GlobalAligner.score_pairs / score_matrix): numpy int64 arrays, shape (P,) for
+    a pair list and (N1, N2) for a matrix, with the settings every pair was scored under."""
+    costs: "numpy.ndarray"
+    scores: "numpy.ndarray"
+    scoring_mat: dict
+    costing_mat: dict
+    gap_open_score: int
+    gap_open_cost: int
+
+
 class AlignmentResults(NamedTuple):
     seq_1_aligned: str
     middle_part: str

@@ -80,6 +80,42 @@ int ga_problem_set(ga_ctx* ctx, const uint8_t* a, int64_t m, const uint8_t* b, i
  * 3*(m+1)*(n+1) int32 (row-major, boundary included). */
 int ga_problem_fill(ga_ctx* ctx, int32_t flags, int64_t* cost_out, int32_t* full_out);
 
+/* Costs of many pairs in one call, scores only (no traceback, no random
+ * state).  For every pair this replaces make_dp_array (globaligner.py:756-821)
+ * + dp_array_forward (:366-392) and the min of the last cell (:425), each pair
+ * with its own sentinel big=(max_cost+1)*max(m,n): cost_out[k] is what
+ * ga_problem_set + ga_problem_fill give for pair k.
+ * codes holds every sequence's codes concatenated, sequence s being
+ * codes[seq_off[s] .. seq_off[s+1]) (seq_off has nseq+1 entries, seq_off[0]
+ * = 0); it is uploaded once, however many pairs use a sequence.  Pair k aligns
+ * sequence pair_a[k] (seq_1, the rows) with sequence pair_b[k] (seq_2).
+ * Every pair is checked as ga_problem_set checks a problem; the first failing
+ * pair fails the call with that code and "pair <k>: ..." as the message, and
+ * nothing is launched.  Short pairs share one kernel launch, one wave per
+ * pair; a pair above GA_BATCH_MAX_CELLS cells (a context option, see
+ * INTEGRATION.md), or one that does not fit that kernel's LDS or edge scratch,
+ * takes the single-pair score fill.  The call works in a fresh context and
+ * keeps buffers of its own, so a loaded problem stays loaded -- unless a pair
+ * took the single-pair fill, which uses the context's problem slot: then no
+ * problem is loaded afterwards (GA_E_STATE until the next ga_problem_set); on
+ * a slab context (ga_problem_set_slab) such a call fails with GA_E_STATE and
+ * leaves the slab as it is.
+ * npairs = 0 returns GA_OK without a launch. */
+int ga_batch_costs(ga_ctx* ctx, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                   const int32_t* pair_b, int64_t npairs, const ga_costs* costs, int64_t* cost_out);
+/* The same with a max_cost per pair (NULL: costs->max_cost for all, which is
+ * ga_batch_costs).  The reference builds a match / mismatch costing matrix
+ * over the letters of the two sequences it is given (start.py:431-468), so a
+ * pair made of one letter has no mismatch entry, a smaller get_max_val
+ * (start.py:488-497) and a smaller sentinel big than a pair scored under the
+ * same settings with two letters or more; where big leaks into the optimum
+ *  the cost differs.  pair_max_cost[k] is the maximum of pair
+ * k's own matrix; the tables in `costs` may then span the whole batch's
+ * alphabet. */
+int ga_batch_costs_ex(ga_ctx* ctx, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                      const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* costs,
+                      int64_t* cost_out);
+
 /* Traceback walk (dp_array_backward :395-593, cost_ranks_dispatcher
  * :595-685, take_* :688-753) on the last GA_FILL_TRACEBACK fill.
  * mt_state: 625 words = random.getstate()[1] in, the state after the

@@ -1,0 +1,109 @@
+"""Throughput of the batched score-only calls (GlobalAligner.score_pairs / score_matrix): one JSON
+line per workload with pairs, cells, ms (median of 5 calls after 2 warm-ups), pairs_per_s and cells_per_s.
+
+    python tools/batch_bench.py                 B1, B2, B3
+    python tools/batch_bench.py --loop K        K of B1's pairs through GlobalAligner(traceback=False).align, one at a
+                                                time (only API that predates the batch calls: runs on older trees too)
+    python tools/batch_bench.py --crossover     one pair per call through the batch kernel and through the single-pair
+                                                fill, at growing sizes (the GA_BATCH_MAX_CELLS default)
+
+Workloads (SplitMix64 sequences of tests.conftest, lengths from a seeded random.Random):
+  B1  4096 DNA pairs, lengths 200-400         B2  1024 BLOSUM62 pairs, lengths 100-600
+  B3  score_matrix of 256 DNA sequences of about 300"""
+import argparse
+import json
+import os
+import random
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from globalign_amd import GlobalAligner, _native  # noqa: E402
+from tests.conftest import splitmix_seq  # noqa: E402
+
+DNA = dict(match_score=2, mismatch_score=-3, gap_open_score=-5, gap_extension_score=-1)
+BLOSUM = dict(scoring_mat_name="BLOSUM62", gap_open_score=-10)
+WARMUP, REPEATS = 2, 5
+
+
+def pairs_of(count, lo, hi, alphabet, seed):
+    rng = random.Random(seed)
+    return [(splitmix_seq(rng.randint(lo, hi), 2 * k + 1, alphabet), splitmix_seq(rng.randint(lo, hi), 2 * k + 2, alphabet))
+            for k in range(count)]
+
+
+def timed(call):
+    for _ in range(WARMUP):
+        call()
+    ms = []
+    for _ in range(REPEATS):
+        t0 = time.perf_counter()
+        call()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ms)
+
+
+def report(name, pairs, cells, ms, **extra):
+    print(json.dumps(dict(workload=name, pairs=pairs, cells=cells, ms=round(ms, 4), pairs_per_s=round(pairs / ms * 1e3, 1),
+                          cells_per_s=round(cells / ms * 1e3, 1), **extra)), flush=True)
+
+
+def workloads():
+    b1 = pairs_of(4096, 200, 400, "dna", 1)
+    al = GlobalAligner(max_seq_len_prod=None, **DNA)
+    a, b = [p[0] for p in b1], [p[1] for p in b1]
+    report("B1", len(b1), sum(len(x) * len(y) for x, y in b1), timed(lambda: al.score_pairs(a, b)),
+           kernel_ms=round(_native.default_engine(0).kernel_ms()[0], 4))
+    b2 = pairs_of(1024, 100, 600, "protein", 2)
+    al2 = GlobalAligner(max_seq_len_prod=None, **BLOSUM)
+    a2, b2s = [p[0] for p in b2], [p[1] for p in b2]
+    report("B2", len(b2), sum(len(x) * len(y) for x, y in b2), timed(lambda: al2.score_pairs(a2, b2s)),
+           kernel_ms=round(_native.default_engine(0).kernel_ms()[0], 4))
+    rng = random.Random(3)
+    seqs = [splitmix_seq(rng.randint(280, 320), 1000 + k, "dna") for k in range(256)]
+    total = sum(len(s) for s in seqs)
+    report("B3", len(seqs) ** 2, total * total, timed(lambda: al.score_matrix(seqs)),
+           kernel_ms=round(_native.default_engine(0).kernel_ms()[0], 4))
+
+
+def loop(count):
+    """The per-pair loop a user writes without the batch calls: one align per pair."""
+    b1 = pairs_of(count, 200, 400, "dna", 1)  # a prefix of B1 (the same seeds and lengths)
+    al = GlobalAligner(max_seq_len_prod=None, traceback=False, **DNA)
+
+    def call():
+        for x, y in b1:
+            al.align(x, y)
+
+    report("B1-loop", len(b1), sum(len(x) * len(y) for x, y in b1), timed(call))
+
+
+def crossover():
+    for side in (256, 512, 768, 1024, 1536, 2048, 3072, 4096):
+        x, y = splitmix_seq(side, 1, "dna"), splitmix_seq(side, 2, "dna")
+        for route, limit in (("kernel", 1 << 40), ("single", 0)):
+            _native.OPTIONS["GA_BATCH_MAX_CELLS"] = str(limit)
+            al = GlobalAligner(max_seq_len_prod=None, **DNA)
+            ms = timed(lambda: al.score_pairs([x], [y]))
+            report(f"1x {side}x{side} {route}", 1, side * side, ms,
+                   kernel_ms=round(_native.default_engine(0).kernel_ms()[0], 4))
+        del _native.OPTIONS["GA_BATCH_MAX_CELLS"]
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--loop", type=int, default=0, metavar="K")
+    ap.add_argument("--crossover", action="store_true")
+    args = ap.parse_args()
+    if args.loop:
+        loop(args.loop)
+    elif args.crossover:
+        crossover()
+    else:
+        workloads()
+
+
+if __name__ == "__main__":
+    main()
