@@ -40,7 +40,8 @@ class EngineError(RuntimeError):
 
 # every symbol include/globalign_amd.h declares (tests check the exports)
 EXPORTS = [
-    "ga_last_error", "ga_device_count", "ga_ctx_create", "ga_ctx_create_opts", "ga_ctx_destroy", "ga_build_flags", "ga_problem_set", "ga_problem_fill", "ga_batch_costs", "ga_batch_costs_ex", "ga_problem_set_cells",
+    "ga_last_error", "ga_device_count", "ga_ctx_create", "ga_ctx_create_opts", "ga_ctx_destroy", "ga_build_flags", "ga_problem_set", "ga_problem_fill", "ga_batch_costs", "ga_batch_costs_ex", "ga_batch_align", "ga_batch_align_timings", "ga_debug_seed_state",
+    "ga_problem_set_cells",
     "ga_problem_traceback", "ga_problem_align", "ga_problem_align_many", "ga_problem_set_slab", "ga_slab_buffers", "ga_slab_bind_halos",
     "ga_slab_link", "ga_slab_link_export", "ga_slab_link_import", "ga_enable_peer_access",
     "ga_slab_fill_launch", "ga_slab_fill_finish", "ga_slab_walk_prepare", "ga_slab_walk", "ga_slab_mt_state",
@@ -106,6 +107,10 @@ def load_library():
         L.ga_problem_fill.argtypes = [vp, i32, pi64, p32]
         L.ga_batch_costs.argtypes = [vp, vp, pi64, i64, p32, p32, i64, C.POINTER(GaCosts), pi64]
         L.ga_batch_costs_ex.argtypes = [vp, vp, pi64, i64, p32, p32, p32, i64, C.POINTER(GaCosts), pi64]
+        L.ga_batch_align.argtypes = [vp, vp, pi64, i64, p32, p32, p32, i64, C.POINTER(GaCosts), vp, vp, vp, vp, vp, pi64,
+                                     pi64, p32, pi64]
+        L.ga_batch_align_timings.argtypes = [vp, C.POINTER(C.c_float)]
+        L.ga_debug_seed_state.argtypes = [C.c_uint64, pu32]
         L.ga_problem_set_cells.argtypes = [vp, p32, pi64]
         L.ga_problem_traceback.argtypes = [vp, pu32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, i64,
                                            pi64, p32]
@@ -278,6 +283,57 @@ class Engine:
                                          C.byref(tables.struct), out.ctypes.data_as(p64)))
         self.m = self.n = 0
         return out
+
+    def batch_align(self, codes, seq_off, pair_a, pair_b, tables, seeds, chars, pair_max_cost=None):
+        """Alignments of many pairs in one call, every pair from its own random seed (ga_batch_align): batch_costs's
+        arguments, seeds (uint64, one per pair) and chars, the upper-cased sequences' bytes concatenated as codes is.
+        -> (costs int64, status int32, lengths int64, offsets int64, (seq_1_aligned, middle, seq_2_aligned) uint8
+        buffers): pair k's strings are the lengths[k] bytes at offsets[k] of each buffer.  Afterwards no problem
+        counts as loaded."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        chars = np.ascontiguousarray(chars, dtype=np.uint8)
+        seq_off = np.ascontiguousarray(seq_off, dtype=np.int64)
+        pair_a = np.ascontiguousarray(pair_a, dtype=np.int32)
+        pair_b = np.ascontiguousarray(pair_b, dtype=np.int32)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        if pair_a.shape != pair_b.shape or pair_a.ndim != 1 or seq_off.ndim != 1 or len(seq_off) < 1:
+            raise ValueError("pair_a and pair_b must be 1-d and of equal length, seq_off 1-d and non-empty")
+        if int(seq_off[-1]) != codes.size or chars.size != codes.size:
+            raise ValueError("seq_off must end at len(codes), and chars must hold one byte per code")
+        if seeds.shape != pair_a.shape:
+            raise ValueError("seeds must have one entry per pair")
+        P = len(pair_a)
+        if P and (min(pair_a.min(), pair_b.min()) < 0 or max(pair_a.max(), pair_b.max()) >= len(seq_off) - 1):
+            raise ValueError("sequence index out of range")
+        p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        pmc = None
+        if pair_max_cost is not None:
+            pair_max_cost = np.ascontiguousarray(pair_max_cost, dtype=np.int32)
+            if pair_max_cost.shape != pair_a.shape:
+                raise ValueError("pair_max_cost must have one entry per pair")
+            pmc = pair_max_cost.ctypes.data_as(p32)
+        lens = np.diff(seq_off)
+        offsets = np.concatenate([[0], np.cumsum(lens[pair_a] + lens[pair_b] + 1)]).astype(np.int64)
+        bufs = tuple(np.empty(max(int(offsets[-1]), 1), dtype=np.uint8) for _ in range(3))
+        costs = np.zeros(P, dtype=np.int64)
+        lengths = np.zeros(P, dtype=np.int64)
+        status = np.zeros(P, dtype=np.int32)
+        _check(self._L.ga_batch_align(self._h, codes.ctypes.data, seq_off.ctypes.data_as(p64), len(seq_off) - 1,
+                                      pair_a.ctypes.data_as(p32), pair_b.ctypes.data_as(p32), pmc, P,
+                                      C.byref(tables.struct), seeds.ctypes.data, chars.ctypes.data, bufs[0].ctypes.data,
+                                      bufs[1].ctypes.data, bufs[2].ctypes.data, offsets.ctypes.data_as(p64),
+                                      lengths.ctypes.data_as(p64), status.ctypes.data_as(p32),
+                                      costs.ctypes.data_as(p64)))
+        self.m = self.n = 0
+        return costs, status, lengths, offsets, bufs
+
+    def batch_align_timings(self):
+        """{kernel_ms, table_ms, decode_ms, call_ms, walk_ns_per_step, fill_ns_per_cell} of the last batch_align (the
+        last two: averages of what each wave timed for its own pairs)."""
+        out = (C.c_float * 6)()
+        _check(self._L.ga_batch_align_timings(self._h, out))
+        return dict(kernel_ms=out[0], table_ms=out[1], decode_ms=out[2], call_ms=out[3], walk_ns_per_step=out[4],
+                    fill_ns_per_cell=out[5])
 
     def fill_kind(self):
         """The kernel and geometry of the last fill: (kind, T, nstripes, nwc, nslabs), kind 'row' / 'diag' / 'lane', or

@@ -1,6 +1,7 @@
-// ga_batch.h -- host-side planning of a batch of score-only alignments (ga_batch_costs; no HIP: built into the engine,
-// into the kernel's translation unit for the work-item layout, and into the planner self-test,
-// ga_batch_selftest.cpp, under AddressSanitizer / UBSan).
+// ga_batch.h -- host-side planning of a batch of score-only alignments (ga_batch_costs) and of a batch of alignments
+// with strings (ga_batch_align, at the end); no HIP: built into the engine, into the kernels' translation unit for the
+// work-item layout, and into the planner self-tests, ga_batch_selftest.cpp and ga_batch_align_selftest.cpp, under
+// AddressSanitizer / UBSan.
 //
 // A batch is a list of sequences (codes concatenated, seq_off[s] .. seq_off[s + 1]) and a list of pairs of sequence
 // indices.  The planner checks every pair as check_problem (ga_check.h) checks a single problem -- with that pair's
@@ -22,6 +23,12 @@ struct ga_batch_item {
     int32_t big;         // this pair's sentinel (globaligner.py:777)
     int32_t out;         // index into the caller's pair list (the cost goes to cost_out[out])
     int32_t T, nstripes; // columns per lane; stripes of 64 * T columns, left to right in the same wave
+};
+
+// What batch_align_kernel needs per pair beyond its ga_batch_item (same index in the work list).
+struct ga_batch_walk_item {
+    int64_t tab_off;  // the pair's m + n tie-break entries in the launch's table
+    int64_t ops_off;  // its ceil((m + n) / 16) u32 words of packed levels
 };
 
 namespace gabatch {
@@ -77,9 +84,12 @@ inline int check_pair_range(int64_t m, int64_t n, const ga_costs* cs, int64_t ma
 // "pair <index>: <reason>" in err.  pair_max_cost: per pair, the max_cost of that pair's own costing matrix (a
 // match / mismatch matrix over one letter has no mismatch entry, so its maximum -- and with it big -- is smaller);
 // nullptr: cs->max_cost for every pair.
-inline int plan_batch(const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
-                      const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
-                      const Limits& lim, Plan& out, std::string& err) {
+// also_single(m, n, T, nstripes): a further reason to give a pair to the single-pair path (plan_batch has none;
+// plan_batch_align, below, adds its own).
+template <typename AlsoSingle>
+inline int plan_batch_routed(const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                             const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                             const Limits& lim, AlsoSingle also_single, Plan& out, std::string& err) {
     auto fail = [&](int code, const std::string& msg) {
         err = msg;
         return code;
@@ -136,20 +146,90 @@ inline int plan_batch(const uint8_t* codes, const int64_t* seq_off, int64_t nseq
         const int64_t sa = pair_a[cd.idx], sb = pair_b[cd.idx];
         const int64_t m = seq_off[sa + 1] - seq_off[sa], n = seq_off[sb + 1] - seq_off[sb];
         const bool scr = needs_scratch(m, n);
-        if (cd.cells > lim.max_cells || !tab_ok || (scr && m > lim.scratch_rows_cap)) {
+        ga_batch_item it;
+        stripe_geometry(n, it.T, it.nstripes);
+        if (cd.cells > lim.max_cells || !tab_ok || (scr && m > lim.scratch_rows_cap) ||
+            also_single(m, n, it.T, it.nstripes)) {
             out.single.push_back(cd.idx);
             continue;
         }
-        ga_batch_item it;
         it.a_off = (int32_t)seq_off[sa];
         it.m = (int32_t)m;
         it.b_off = (int32_t)seq_off[sb];
         it.n = (int32_t)n;
         it.big = (int32_t)cd.big;  // range_fits: |big| < 2^29
         it.out = (int32_t)cd.idx;
-        stripe_geometry(n, it.T, it.nstripes);
         out.kernel.push_back(it);
         if (scr) out.scratch_rows = std::max(out.scratch_rows, m);
+    }
+    return GA_OK;
+}
+
+inline int plan_batch(const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                      const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                      const Limits& lim, Plan& out, std::string& err) {
+    return plan_batch_routed(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim,
+                             [](int64_t, int64_t, int, int) { return false; }, out, err);
+}
+
+// ------------------------------------------------------------------ batches with alignment strings (ga_batch_align)
+// batch_align_kernel (ga_batch.hip) fills a pair as batch_fill_kernel does, writes every cell's traceback word to a
+// slice of HBM scratch that only the pair's wave touches, and walks the pair from (m, n) with the pair's own
+// tie-break table.  The words are packed into u32s down the rows, 4 / CB rows of a column to a u32, rows of u32s with
+// a pitch of the pair's padded columns: cell (i, j) is bits ((i - 1) % (4 / CB)) * 8 * CB .. of u32
+// ((i - 1) / (4 / CB)) * 64 * T * nstripes + (j - 1).
+constexpr int64_t kDefaultAlignMaxCells = 1 << 20;
+// The traceback scratch of one launch, all waves.  8 GiB of the device's 288: with two waves per SIMD on 256 CUs a
+// wave's share is 4 MiB, which holds a pair of kDefaultAlignMaxCells cells even at four bytes a word (its column
+// padding aside), so the cells limit and not this cap decides the routing at the default settings.  The engine
+// allocates only what the launch's largest pair needs.
+constexpr int64_t kTbScratchBytesCap = 8ll << 30;
+
+// u32 words of a pair's traceback slice
+inline int64_t tb_slice_words(int64_t m, int T, int nstripes, int CB) {
+    const int64_t rpw = 4 / CB;
+    return (m + rpw - 1) / rpw * 64 * T * nstripes;
+}
+inline int64_t tb_slice_words_cap(int64_t waves) { return kTbScratchBytesCap / (std::max<int64_t>(waves, 1) * 4); }
+
+struct AlignLimits : Limits {
+    AlignLimits() { max_cells = kDefaultAlignMaxCells; }
+    int64_t tb_words_cap = 0;  // most u32 words of traceback scratch a wave may be given
+};
+
+struct AlignPlan : Plan {
+    int CB = 1;                            // traceback word bytes (ga_check.h tb_word_bytes)
+    std::vector<ga_batch_walk_item> walk;  // parallel to `kernel`
+    int64_t tab_entries = 0;               // tie-break entries of all kernel pairs (m + n each)
+    int64_t ops_words = 0;                 // level words of all kernel pairs (ceil((m + n) / 16) each)
+    int64_t tb_words = 0;                  // u32 words per wave of the traceback scratch
+};
+
+// plan_batch's checks, order and stripe geometry; to the single-pair path also go pairs with a sequence of one letter
+// (only they can raise the reference's IndexError or take its first-step quirk) and pairs whose
+// traceback words exceed a wave's share of the scratch.
+inline int plan_batch_align(const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                            const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                            const AlignLimits& lim, AlignPlan& out, std::string& err) {
+    out = AlignPlan();
+    const int CB = cs ? tb_word_bytes(cs->gap_open) : 0;  // (0: plan_batch_routed refuses every pair)
+    Plan base;
+    const int r = plan_batch_routed(
+        codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim,
+        [&](int64_t m, int64_t n, int T, int nstripes) {
+            return std::min(m, n) < 2 || CB == 0 || tb_slice_words(m, T, nstripes, CB) > lim.tb_words_cap;
+        },
+        base, err);
+    if (r) return r;
+    static_cast<Plan&>(out) = std::move(base);
+    out.CB = std::max(CB, 1);
+    out.walk.reserve(out.kernel.size());
+    for (const ga_batch_item& it : out.kernel) {
+        const int64_t steps = (int64_t)it.m + it.n;
+        out.walk.push_back(ga_batch_walk_item{out.tab_entries, out.ops_words});
+        out.tab_entries += steps;
+        out.ops_words += (steps + 15) / 16;
+        out.tb_words = std::max(out.tb_words, tb_slice_words(it.m, it.T, it.nstripes, out.CB));
     }
     return GA_OK;
 }

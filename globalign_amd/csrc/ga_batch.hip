@@ -1,4 +1,5 @@
-// ga_batch.hip -- batch_fill_kernel: many score-only alignments in one launch, one wave per pair (gfx950).
+// ga_batch.hip -- batch_fill_kernel: many score-only alignments in one launch, one wave per pair (gfx950), and
+// batch_align_kernel (further down): the same with traceback words and the traceback walk, for alignment strings.
 //
 // For each pair this replaces make_dp_array (globaligner.py:756-821), dp_array_forward (:366-392) and the min of
 // the last cell (:425) -- what the single-pair path spreads over the boundary launches and a fill -- in the shifted
@@ -18,6 +19,7 @@
 #include "ga_batch.h"
 #include "ga_device.h"
 #include "ga_row.h"
+#include "ga_walk.h"
 
 namespace ga {
 
@@ -83,12 +85,47 @@ __device__ __forceinline__ void masked_row(int (&Hprev)[T], int (&Yc)[T], int eh
     }
 }
 
+// masked_row with the cells' traceback codes (blocked_row's, W-bit fields): the twin batch_align_kernel uses
+template <int T, int CB>
+__device__ __forceinline__ void masked_row_tb(int (&Hprev)[T], int (&Yc)[T], int eh, int ev, const int (&sub)[T], int o,
+                                              unsigned op1, const bool (&ok)[T], unsigned (&code)[T], int& oH, int& oV) {
+    constexpr int W = (8 * CB - 1) / 2;
+    int M[T], U[T], P[T];
+    M[0] = shr1(eh, Hprev[T - 1]) + sub[0];  // the DPP itself runs in every lane
+#pragma unroll
+    for (int k = 1; k < T; k++) M[k] = Hprev[k - 1] + sub[k];
+#pragma unroll
+    for (int k = 0; k < T; k++) U[k] = ok[k] ? min(M[k], Yc[k]) : BATCH_INF;
+    P[0] = U[0];
+#pragma unroll
+    for (int k = 1; k < T; k++) P[k] = min(P[k - 1], U[k]);
+    const int Wv = min(wave_scan_min(P[T - 1]), ev);
+    const int C = shr1(ev, Wv);
+    oH = Hprev[T - 1];
+    oV = Wv;
+    int Vl = C;
+#pragma unroll
+    for (int k = 0; k < T; k++) {
+        const int X = Vl + o;
+        const int H = min(U[k], X);
+        // (a column past n: garbage nobody reads)
+        code[k] = min((unsigned)(X - H), op1) | (min((unsigned)(Yc[k] - H), op1) << W) |
+                  (min((unsigned)(M[k] - H), 1u) << (2 * W));
+        if (k + 1 < T) Vl = min(C, P[k]);
+        Yc[k] = min(Yc[k], H + o);
+        Hprev[k] = H;
+    }
+}
+
 // HBM: the pair's edge column lies in the wave's HBM slices (m above the LDS share and more than one stripe), else
 // in LDS; a template parameter, so that every edge access has one address space (a run-time choice let the compiler
 // merge the two stores into one flat store through a selected pointer).
-template <typename QT, int T, bool HBM>
+// CB > 0 (batch_align_kernel): every cell's CB-byte traceback word also goes to tbw, the wave's slice of traceback
+// scratch, 4 / CB rows of a column to a u32 and rows of u32s npitch = 64 * T * nstripes apart (ga_batch.h).  Columns
+// past n are stored too (garbage nobody reads): the pitch covers them.
+template <typename QT, int T, bool HBM, int CB = 0>
 __device__ void batch_pair(const BatchArgs& p, const ga_batch_item& it, const QT* tab, const int* gh_s, const int* gv_s,
-                           int2* edge_l, int2* edge_g, int lane) {
+                           int2* edge_l, int2* edge_g, int lane, uint32_t* tbw = nullptr) {
     const int m = it.m, n = it.n, o = p.o, K = p.K, big = it.big;
     const uint8_t* a = p.codes + it.a_off;
     const uint8_t* b = p.codes + it.b_off;
@@ -131,6 +168,15 @@ __device__ void batch_pair(const BatchArgs& p, const ga_batch_item& it, const QT
         ghc += __builtin_amdgcn_readlane(incl, 63);  // columns past n add 0: GH(n) after the last stripe
         int gvc = 0;     // GV(i0)
         int lxp = 0;     // left[i0].x = H'(i0, 0) (row 0: the corner, 0)
+        // CB > 0: the u32s of this lane's columns being packed, and where the next ones go
+        constexpr int RPW = CB > 0 ? 4 / CB : 1;
+        [[maybe_unused]] uint32_t cur[T];
+        [[maybe_unused]] uint32_t* tbrow = nullptr;
+        if constexpr (CB > 0) {
+#pragma unroll
+            for (int k = 0; k < T; k++) cur[k] = 0;
+            tbrow = tbw + j0 + lane * T;
+        }
         for (int i0 = 0; i0 < m; i0 += 64) {
             const int rows = min(64, m - i0);
             const int i = i0 + lane + 1;
@@ -169,7 +215,32 @@ __device__ void batch_pair(const BatchArgs& p, const ga_batch_item& it, const QT
                 for (int k = 0; k < T; k++) subn[k] = (int)trow[bc[k]];
                 const int eh = __builtin_amdgcn_readlane(eH, r), ev = __builtin_amdgcn_readlane(eV, r);
                 int oH, oV;
-                if (partial) {
+                if constexpr (CB > 0) {
+                    const unsigned op1 = (unsigned)o + 1u;
+                    unsigned code[T];
+                    if (partial) {
+                        masked_row_tb<T, CB>(Hprev, Yc, eh, ev, sub, o, op1, ok, code, oH, oV);
+                    } else {
+                        uint32_t acc[T][4 * CB];
+#pragma unroll
+                        for (int k = 0; k < T; k++) acc[k][0] = 0;
+                        blocked_row<T, true, CB>(Hprev, Yc, eh, ev, sub, o, op1, 0, acc, oH, oV);
+#pragma unroll
+                        for (int k = 0; k < T; k++) code[k] = acc[k][0];
+                    }
+                    // (i0 is a multiple of 64, so r alone gives the row's place in its u32)
+                    const int q = r & (RPW - 1);
+#pragma unroll
+                    for (int k = 0; k < T; k++) cur[k] |= code[k] << (q * 8 * CB);
+                    if (q == RPW - 1 || r == rows - 1) {
+#pragma unroll
+                        for (int k = 0; k < T; k++) {
+                            tbrow[k] = cur[k];
+                            cur[k] = 0;
+                        }
+                        tbrow += 64 * T * it.nstripes;
+                    }
+                } else if (partial) {
                     masked_row<T>(Hprev, Yc, eh, ev, sub, o, ok, oH, oV);
                 } else {
                     uint32_t acc[T][4];
@@ -250,6 +321,162 @@ __global__ void __launch_bounds__(64 * gabatch::kWavesPerGroup) batch_fill_kerne
             default: p.cost_out[it.out] = BATCH_BAD_ITEM;  // (every lane, as batch_pair's cost)
         }
     }
+}
+
+// ------------------------------------------------------------------ batch_align_kernel
+// Alignments with strings: the same persistent ticket loop, and per pair the fill above with its
+// traceback words kept, then the traceback walk (dp_array_backward, globaligner.py:395-593) by the same wave, from
+// (m, n) to row 0 or column 0, under the pair's own tie-break table.  The work list holds only pairs with
+// min(m, n) >= 2: their walks stay inside the matrix (no first-step quirk, no IndexError).
+struct AlignArgs {
+    BatchArgs b;
+    const ga_batch_walk_item* witems;  // parallel to b.items
+    const uint32_t* rng;               // the pairs' tie-break entries (ga_rng.h), pair t at witems[t].tab_off
+    uint32_t* ops;                     // the chosen levels, 2 bits per dispatch, pair t at witems[t].ops_off
+    int4* walk_out;                    // [npairs][2] {dispatches, i, j, reason}, {fill ticks, walk ticks, 0, 0} (10 ns
+                                       // ticks of s_memrealtime), indexed by ga_batch_item::out
+    uint32_t* tb;                      // [waves][tb_words] traceback words
+    long long tb_words;
+};
+
+// The walk of one pair by one wave.  Groups of up to 7 steps: one vector load per lane fetches the 8 x 8 window
+// anchored at the current cell (lane r * 8 + c: cell (i - r, j - c), clamped at row / column 1 -- a clamped cell is
+// never walked, the walk ends where it would be needed) and every lane decodes its cell into the three 5-bit table
+// shifts of walk_body's cached cells; the steps then run on scalars, each reading its cell with a uniform-index
+// v_readlane.  Every step lowers i + j and the walk ends at i == 0 or j == 0, so it makes at most m + n - 1 steps
+// whatever the words and the table hold.  The words are read with vector loads only (the scalar cache could hold a
+// previous pair's lines of this slice), after the fence that follows the fill's stores.
+template <int CB>
+__device__ int4 batch_walk(const AlignArgs& q, const ga_batch_item& it, const ga_batch_walk_item& wi,
+                           const uint32_t* tbw, int lane) {
+    constexpr int RPW = 4 / CB;
+    constexpr unsigned MASK = CB == 4 ? 0xffffffffu : (1u << (8 * CB)) - 1u;
+    const int m = it.m, n = it.n, o = q.b.o;
+    const int npitch = 64 * it.T * it.nstripes, total = m + n;
+    const uint8_t* a = q.b.codes + it.a_off;
+    const uint8_t* b = q.b.codes + it.b_off;
+    const uint32_t* tab = q.rng + wi.tab_off;
+    uint32_t* ops = q.ops + wi.ops_off;
+    const int lr = lane >> 3, lc = lane & 7;
+    int i = m, j = n, D = 0;
+    unsigned L5 = 0, opsw = 0;  // 5 * the level the walk entered the cell with; the level word being packed
+    while (i > 0 && j > 0 && D < total) {
+        const int ci = max(i - lr, 1), cj = max(j - lc, 1);
+        const uint32_t wd = tbw[(unsigned)((ci - 1) / RPW) * (unsigned)npitch + (unsigned)(cj - 1)];
+        const unsigned code = (wd >> (((ci - 1) & (RPW - 1)) * 8 * CB)) & MASK;
+        const int shf = (int)cell_shifts(sets_from_code(code, CB, o), a[ci - 1] == b[cj - 1]);
+        const int tv = (int)tab[min(D + (lane & 7), total - 1)];  // lane s: the entry of the group's step s
+        int di = 0, dj = 0;
+#pragma unroll
+        for (int s = 0; s < 7; s++) {
+            const unsigned v = (unsigned)__builtin_amdgcn_readlane(shf, di * 8 + dj);
+            const unsigned t = (unsigned)__builtin_amdgcn_readlane(tv, s);
+            const unsigned lvl = (t >> (((v >> L5) & 31u) + 3u)) & 3u;
+            opsw |= lvl << (30 - 2 * (D & 15));
+            // every lane stores the same word (no lane-divergent branch in the persistent loop, see batch_pair)
+            if ((D & 15) == 15) {
+                ops[D >> 4] = opsw;
+                opsw = 0;
+            }
+            D++;
+            di += lvl != 1u;
+            dj += lvl != 2u;
+            L5 = 5u * lvl;
+            if (di == i || dj == j || D >= total) break;
+        }
+        i -= di;
+        j -= dj;
+    }
+    if (D & 15) ops[D >> 4] = opsw;
+    // reason as walk_body's: 1 the walk ended in row 0, 2 in column 0 (0: in the corner, no tail either way)
+    return make_int4(D, i, j, i == 0 ? (j == 0 ? 0 : 1) : 2);
+}
+
+template <typename QT, int T, int CB>
+__device__ __forceinline__ void align_pair_either(const BatchArgs& p, const ga_batch_item& it, bool hbm, const QT* tab,
+                                                  const int* gh_s, const int* gv_s, int2* edge_l, int2* edge_g, int lane,
+                                                  uint32_t* tbw) {
+    if (hbm) batch_pair<QT, T, true, CB>(p, it, tab, gh_s, gv_s, edge_l, edge_g, lane, tbw);
+    else batch_pair<QT, T, false, CB>(p, it, tab, gh_s, gv_s, edge_l, edge_g, lane, tbw);
+}
+
+template <typename QT, int CB>
+__global__ void __launch_bounds__(64 * gabatch::kWavesPerGroup) batch_align_kernel(AlignArgs q) {
+    __shared__ QT tab[gabatch::kLdsTableBytes / sizeof(QT)];
+    __shared__ int gh_s[256], gv_s[256];
+    __shared__ int2 edge_s[gabatch::kWavesPerGroup][gabatch::kLdsEdgeRows];
+    const BatchArgs& p = q.b;
+    const int K = p.K;
+    for (int x = threadIdx.x; x < K * K; x += blockDim.x) tab[x] = (QT)p.subp[x];
+    for (int x = threadIdx.x; x < K; x += blockDim.x) {
+        gh_s[x] = p.gh[x];
+        gv_s[x] = p.gv[x];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long gw = (long long)blockIdx.x * gabatch::kWavesPerGroup + w;
+    int2* edge_g = p.scratch ? p.scratch + gw * 2 * p.scratch_rows : nullptr;
+    uint32_t* tbw = q.tb + gw * q.tb_words;
+    for (;;) {
+        unsigned t = 0;
+        if (lane == 0) t = __hip_atomic_fetch_add(p.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        t = (unsigned)__builtin_amdgcn_readfirstlane((int)t);
+        if (t >= (unsigned)p.nitems) break;
+        const ga_batch_item it = p.items[t];
+        const ga_batch_walk_item wi = q.witems[t];
+        const bool hbm = it.nstripes > 1 && it.m > gabatch::kLdsEdgeRows;
+        // the edge column and the traceback words must fit this wave's slices, and the walk needs two letters a side
+        // (ga_batch.h plans it so)
+        const bool fits = !(hbm && (edge_g == nullptr || it.m > p.scratch_rows)) && it.m >= 2 && it.n >= 2 &&
+                          it.T >= 1 && it.T <= gabatch::kMaxT &&
+                          (long long)((it.m + 4 / CB - 1) / (4 / CB)) * 64 * it.T * it.nstripes <= q.tb_words &&
+                          (long long)64 * it.T * it.nstripes >= it.n;
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+        switch (fits ? it.T : 0) {
+            case 1: align_pair_either<QT, 1, CB>(p, it, hbm, tab, gh_s, gv_s, edge_s[w], edge_g, lane, tbw); break;
+            case 2: align_pair_either<QT, 2, CB>(p, it, hbm, tab, gh_s, gv_s, edge_s[w], edge_g, lane, tbw); break;
+            case 3: align_pair_either<QT, 3, CB>(p, it, hbm, tab, gh_s, gv_s, edge_s[w], edge_g, lane, tbw); break;
+            case 4: align_pair_either<QT, 4, CB>(p, it, hbm, tab, gh_s, gv_s, edge_s[w], edge_g, lane, tbw); break;
+            case 5: align_pair_either<QT, 5, CB>(p, it, hbm, tab, gh_s, gv_s, edge_s[w], edge_g, lane, tbw); break;
+            case 6: align_pair_either<QT, 6, CB>(p, it, hbm, tab, gh_s, gv_s, edge_s[w], edge_g, lane, tbw); break;
+            case 7: align_pair_either<QT, 7, CB>(p, it, hbm, tab, gh_s, gv_s, edge_s[w], edge_g, lane, tbw); break;
+            case 8: align_pair_either<QT, 8, CB>(p, it, hbm, tab, gh_s, gv_s, edge_s[w], edge_g, lane, tbw); break;
+            default: p.cost_out[it.out] = BATCH_BAD_ITEM;  // (every lane, as batch_pair's cost)
+        }
+        // the fill's words, stored by this wave's lanes, are read by other lanes of the wave: one wave's memory
+        // operations to an address stay in order (the edge column's fence, batch_pair)
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if (fits) {
+            const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
+            const int4 end = batch_walk<CB>(q, it, wi, tbw, lane);
+            const unsigned long long t2 = __builtin_amdgcn_s_memrealtime();
+            // every lane stores the same words (no lane-divergent branch in the loop, see batch_pair)
+            q.walk_out[2 * (long long)it.out] = end;
+            q.walk_out[2 * (long long)it.out + 1] = make_int4((int)(t1 - t0), (int)(t2 - t1), 0, 0);
+        }
+    }
+}
+
+template <typename QT>
+static void launch_batch_align_q(hipStream_t s, const AlignArgs& q, int CB, int groups) {
+    const int threads = 64 * gabatch::kWavesPerGroup;
+    if (CB == 1) batch_align_kernel<QT, 1><<<groups, threads, 0, s>>>(q);
+    else if (CB == 2) batch_align_kernel<QT, 2><<<groups, threads, 0, s>>>(q);
+    else batch_align_kernel<QT, 4><<<groups, threads, 0, s>>>(q);
+}
+
+// launch_batch_fill's arguments, then CB (the traceback word's bytes: 1, 2 or 4) and the walk's buffers
+void launch_batch_align(hipStream_t s, const uint8_t* codes, const ga_batch_item* items, int nitems, const int* subp,
+                        const int* gh, const int* gv, int K, int o, int qbytes, unsigned* ticket, long long* cost_out,
+                        int2* scratch, long long scratch_rows, int waves, int CB, const ga_batch_walk_item* witems,
+                        const uint32_t* rng, uint32_t* ops, int4* walk_out, uint32_t* tb, long long tb_words) {
+    const AlignArgs q{BatchArgs{codes, items, nitems, subp, gh, gv, K, o, ticket, cost_out, scratch, scratch_rows},
+                      witems, rng, ops, walk_out, tb, tb_words};
+    const int groups = waves / gabatch::kWavesPerGroup;
+    if (qbytes == 1) launch_batch_align_q<int8_t>(s, q, CB, groups);
+    else if (qbytes == 2) launch_batch_align_q<int16_t>(s, q, CB, groups);
+    else launch_batch_align_q<int32_t>(s, q, CB, groups);
 }
 
 // waves: resident waves the host sized the grid (and the scratch) for; a multiple of kWavesPerGroup

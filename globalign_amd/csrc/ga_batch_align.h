@@ -1,0 +1,95 @@
+// ga_batch_align.h -- the host's share of a batch of alignments with strings (ga_batch_align; no HIP: built into
+// the engine and into ga_batch_align_selftest.cpp under AddressSanitizer / UBSan / ThreadSanitizer).
+//
+// Every pair of the batch walks with a tie-break stream of its own, the one `random.seed(seed)` starts, so the walks
+// do not depend on each other: build_pair_tables makes the kernel pairs' tables (ga_rng.h) on a few threads, and
+// decode_levels turns a finished walk's packed levels into the three alignment strings.
+#pragma once
+#include <stdint.h>
+
+#include <algorithm>
+#include <thread>
+#include <vector>
+
+#include "ga_batch.h"
+#include "ga_rng.h"
+
+namespace gabatch {
+
+constexpr int kMaxRngThreads = 8;
+
+// Threads for the tables of nitems pairs.  requested > 0 (GA_BATCH_RNG_THREADS): that many, 1 meaning sequential;
+// else one per 64 pairs, never more than the machine reports.  At most kMaxRngThreads either way.
+inline int rng_threads(int requested, int64_t nitems) {
+    int64_t nt = requested > 0 ? requested : (nitems + 63) / 64;
+    if (requested <= 0) {
+        const unsigned hc = std::thread::hardware_concurrency();
+        if (hc > 0) nt = std::min<int64_t>(nt, hc);
+    }
+    return (int)std::max<int64_t>(1, std::min<int64_t>(nt, kMaxRngThreads));
+}
+
+// share(first, stride) on nthreads threads (the caller's among them): thread q gets (q, nthreads) and takes the
+// work items q, q + nthreads, ... -- the list is sorted longest first, so the shares are even.
+template <typename Share>
+inline void run_shares(int64_t nitems, int nthreads, Share share) {
+    nthreads = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(nthreads, kMaxRngThreads), nitems));
+    if (nthreads == 1) return share(0, 1);
+    std::vector<std::thread> pool;
+    for (int q = 1; q < nthreads; q++) pool.emplace_back(share, q, nthreads);
+    share(0, nthreads);
+    for (std::thread& th : pool) th.join();
+}
+
+// tab[walk[t].tab_off .. + m + n): the entries of work item t under seeds[items[t].out]; no two items share entries.
+inline void build_pair_tables(const ga_batch_item* items, const ga_batch_walk_item* walk, int64_t nitems,
+                              const uint64_t* seeds, int nthreads, uint32_t* tab) {
+    run_shares(nitems, nthreads, [=](int64_t first, int64_t stride) {
+        garng::RngTable R;
+        uint32_t state[garng::MTN + 1];
+        for (int64_t t = first; t < nitems; t += stride) {
+            const int64_t steps = (int64_t)items[t].m + items[t].n;
+            garng::seed_state(seeds[items[t].out], state);
+            R.start(state);
+            R.extend(steps);
+            std::copy(R.tab.begin(), R.tab.begin() + steps, tab + walk[t].tab_off);
+        }
+    });
+}
+
+// The strings of one walk (dp_array_backward's output, globaligner.py:514-586): the levels of dispatches [0, D),
+// 2 bits each, dispatch k at bits 30 - 2 * (k & 15) of ops[k >> 4], walked from (m, n) -- level 0 takes a column of
+// both sequences, 1 a gap above seq_2's letter, 2 seq_1's letter above a gap --, then the reference's tail for a walk
+// that ended in row 0 (reason 1: the rest of seq_2 under gaps) or column 0 (reason 2: the rest of seq_1 over gaps),
+// then the reversal.  Returns the length, -1 when it exceeds cap, -2 when the levels do not lead to (i_end, j_end)
+// inside the matrix.
+inline int64_t decode_levels(const uint32_t* ops, int64_t D, int64_t m, int64_t n, int64_t i_end, int64_t j_end,
+                             int reason, const char* a_chr, const char* b_chr, char* oa, char* om, char* ob,
+                             int64_t cap) {
+    int64_t i = m, j = n, len = 0;
+    auto put = [&](char x, char y, char z) {
+        if (len < cap) { oa[len] = x; om[len] = y; ob[len] = z; }
+        len++;
+    };
+    for (int64_t k = 0; k < D; k++) {
+        if (i < 1 || j < 1) return -2;
+        const char ca = a_chr[i - 1], cb = b_chr[j - 1];
+        const unsigned lv = (ops[k >> 4] >> (30 - 2 * (k & 15))) & 3u;
+        if (lv == 0) { put(ca, ca == cb ? '|' : '*', cb); i--; j--; }
+        else if (lv == 1) { put('-', ' ', cb); j--; }
+        else if (lv == 2) { put(ca, ' ', '-'); i--; }
+        else return -2;
+    }
+    if (i != i_end || j != j_end || (i > 0 && j > 0)) return -2;
+    if (reason == 1)
+        for (int64_t jj = j; jj > 0; jj--) put('-', ' ', b_chr[jj - 1]);
+    else if (reason == 2)
+        for (int64_t ii = i; ii > 0; ii--) put(a_chr[ii - 1], ' ', '-');
+    if (len > cap) return -1;
+    std::reverse(oa, oa + len);
+    std::reverse(om, om + len);
+    std::reverse(ob, ob + len);
+    return len;
+}
+
+}  // namespace gabatch

@@ -1,0 +1,302 @@
+// ga_batch_align_selftest.cpp -- CPU self-test of the host's share of ga_batch_align: the align planner (ga_batch.h
+// plan_batch_align), the per-pair tie-break tables and the levels-to-strings decode (ga_batch_align.h), plain, under
+// AddressSanitizer + UndefinedBehaviorSanitizer and -- for the threaded table build -- under ThreadSanitizer
+// (make -C globalign_amd/csrc batch_align_selftest batch_align_asan batch_align_tsan; run by
+// tests/test_batch_align_host.py).  No HIP: the kernel is tested on the GPU.
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "ga_batch_align.h"
+
+using namespace gabatch;
+
+namespace {
+
+int failures = 0;
+
+#define CHECK(cond, ...)                                   \
+    do {                                                   \
+        if (!(cond)) {                                     \
+            failures++;                                    \
+            std::fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); \
+            std::fprintf(stderr, __VA_ARGS__);             \
+            std::fprintf(stderr, "\n");                    \
+        }                                                  \
+    } while (0)
+
+// match 0 / mismatch `mis` / gap extension `ext` over K - 1 letters and the gap code K - 1
+struct Tables {
+    int K;
+    std::vector<int32_t> sub, gh, gv;
+    ga_costs cs;
+    Tables(int K_, int mis, int ext, int open) : K(K_), sub((size_t)K_ * K_), gh((size_t)K_, ext), gv((size_t)K_, ext) {
+        for (int x = 0; x < K; x++)
+            for (int y = 0; y < K; y++) sub[(size_t)x * K + y] = x == y ? 0 : (x == K - 1 || y == K - 1) ? ext : mis;
+        cs = ga_costs{K, sub.data(), gh.data(), gv.data(), open, std::max(mis, ext)};
+    }
+};
+
+// sequences of the given lengths (code 0 everywhere) and their offsets
+struct Seqs {
+    std::vector<uint8_t> codes;
+    std::vector<int64_t> off{0};
+    explicit Seqs(const std::vector<int64_t>& lens) {
+        for (int64_t L : lens) {
+            codes.insert(codes.end(), (size_t)L, 0);
+            off.push_back((int64_t)codes.size());
+        }
+    }
+    int64_t n() const { return (int64_t)off.size() - 1; }
+};
+
+AlignLimits wide_limits() {
+    AlignLimits lim;
+    lim.max_cells = 1 << 30;
+    lim.scratch_rows_cap = 1 << 20;
+    lim.tb_words_cap = (int64_t)1 << 40;
+    return lim;
+}
+
+int plan(const Seqs& sq, const std::vector<int32_t>& pa, const std::vector<int32_t>& pb, const Tables& t,
+         const AlignLimits& lim, AlignPlan& out, std::string& err) {
+    return plan_batch_align(sq.codes.data(), sq.off.data(), sq.n(), pa.data(), pb.data(), nullptr, (int64_t)pa.size(),
+                            &t.cs, lim, out, err);
+}
+
+void test_routing_and_order() {
+    Tables t(5, 5, 3, 4);
+    Seqs sq({1, 2, 40, 300, 513, 1, 90});
+    //                        1x2   2x1   2x2   40x300 513x513 1x1   90x40  300x2
+    std::vector<int32_t> pa{0, 1, 1, 2, 4, 5, 6, 3}, pb{1, 0, 1, 3, 4, 5, 2, 1};
+    AlignPlan p;
+    std::string err;
+    CHECK(plan(sq, pa, pb, t, wide_limits(), p, err) == GA_OK, "plan failed: %s", err.c_str());
+    // a sequence of one letter: the single-pair path, whatever the other side
+    const std::vector<int64_t> want_single{0, 1, 5};
+    CHECK(p.single == want_single, "one-letter pairs route to the single path (%zu do)", p.single.size());
+    // the rest in plan_batch's order: the score planner's list without the pairs routed away
+    Plan score;
+    Limits lim;
+    lim.max_cells = 1 << 30;
+    lim.scratch_rows_cap = 1 << 20;
+    CHECK(plan_batch(sq.codes.data(), sq.off.data(), sq.n(), pa.data(), pb.data(), nullptr, (int64_t)pa.size(), &t.cs, lim,
+                     score, err) == GA_OK, "score plan failed");
+    size_t q = 0;
+    for (const ga_batch_item& it : score.kernel) {
+        if (it.m < 2 || it.n < 2) continue;
+        CHECK(q < p.kernel.size() && p.kernel[q].out == it.out && p.kernel[q].T == it.T &&
+                  p.kernel[q].nstripes == it.nstripes && p.kernel[q].big == it.big, "work item %zu follows plan_batch", q);
+        q++;
+    }
+    CHECK(q == p.kernel.size() && q == 5, "five kernel pairs, got %zu", p.kernel.size());
+    CHECK(p.walk.size() == p.kernel.size(), "one walk item per work item");
+    // tables and level words: disjoint, in list order, large enough
+    int64_t tab = 0, ops = 0, tbw = 0;
+    for (size_t k = 0; k < p.kernel.size() && k < p.walk.size(); k++) {
+        const ga_batch_item& it = p.kernel[k];
+        CHECK(p.walk[k].tab_off == tab && p.walk[k].ops_off == ops, "offsets of work item %zu", k);
+        tab += it.m + it.n;
+        ops += (it.m + it.n + 15) / 16;
+        tbw = std::max(tbw, tb_slice_words(it.m, it.T, it.nstripes, p.CB));
+        CHECK(tb_slice_words(it.m, it.T, it.nstripes, p.CB) * 4 >= (int64_t)it.m * it.n * p.CB, "slice holds item %zu", k);
+    }
+    CHECK(p.tab_entries == tab && p.ops_words == ops && p.tb_words == tbw, "totals");
+    CHECK(p.CB == 1, "gap open 4: one-byte words");
+    // plan_batch itself still takes one-letter pairs
+    CHECK(score.kernel.size() == pa.size() && score.single.empty(), "plan_batch is unchanged");
+}
+
+void test_limits() {
+    Tables t(5, 5, 3, 4);
+    Seqs sq({100, 101});
+    std::vector<int32_t> pa{0, 1, 0}, pb{0, 1, 1};  // 10000, 10201, 10100 cells
+    AlignPlan p;
+    std::string err;
+    AlignLimits lim = wide_limits();
+    lim.max_cells = 10100;
+    CHECK(plan(sq, pa, pb, t, lim, p, err) == GA_OK, "plan failed: %s", err.c_str());
+    CHECK(p.single == std::vector<int64_t>{1} && p.kernel.size() == 2, "the cells limit is inclusive");
+    lim.max_cells = 0;
+    CHECK(plan(sq, pa, pb, t, lim, p, err) == GA_OK && p.kernel.empty() && p.single.size() == 3, "limit 0: all single");
+    CHECK(p.tab_entries == 0 && p.ops_words == 0 && p.tb_words == 0, "no kernel pair: no buffers");
+    // the traceback scratch cap: 100 rows of 128 padded columns, 4 rows to a u32 = 25 * 128 words
+    lim = wide_limits();
+    CHECK(tb_slice_words(100, 2, 1, 1) == 25 * 128 && tb_slice_words(101, 2, 1, 1) == 26 * 128, "slice words");
+    CHECK(tb_slice_words(101, 2, 1, 2) == 51 * 128 && tb_slice_words(101, 2, 1, 4) == 101 * 128, "slice words by CB");
+    lim.tb_words_cap = 25 * 128;
+    CHECK(plan(sq, pa, pb, t, lim, p, err) == GA_OK, "plan failed: %s", err.c_str());
+    CHECK(p.kernel.size() == 2 && p.single == std::vector<int64_t>{1}, "101 rows exceed a 25-row-word share");
+    CHECK(p.tb_words == 25 * 128, "the scratch is sized by the largest kernel pair");
+    lim.tb_words_cap = 25 * 128 - 1;
+    CHECK(plan(sq, pa, pb, t, lim, p, err) == GA_OK && p.kernel.empty(), "one word short: none fits");
+    CHECK(tb_slice_words_cap(2048) * 4 * 2048 == kTbScratchBytesCap, "a wave's share of the cap");
+}
+
+void test_word_widths() {
+    Seqs sq({10});
+    std::vector<int32_t> pa{0}, pb{0};
+    const int opens[] = {0, 6, 7, 126, 127, 300, 32766};
+    const int want[] = {1, 1, 2, 2, 4, 4, 4};
+    for (int q = 0; q < 7; q++) {
+        Tables t(5, 5, 3, opens[q]);
+        AlignPlan p;
+        std::string err;
+        CHECK(plan(sq, pa, pb, t, wide_limits(), p, err) == GA_OK, "plan failed: %s", err.c_str());
+        CHECK(p.CB == want[q] && p.CB == tb_word_bytes(opens[q]), "gap open %d: CB %d", opens[q], p.CB);
+    }
+    Tables t(5, 5, 3, 32767);
+    AlignPlan p;
+    std::string err;
+    CHECK(plan(sq, pa, pb, t, wide_limits(), p, err) == GA_E_RANGE && err.find("pair 0") == 0, "gap open 32767: %s",
+          err.c_str());
+    // errors are plan_batch's: the first failing pair in input order
+    Seqs two({3, 0});
+    Tables ok(5, 5, 3, 4);
+    std::vector<int32_t> a2{0, 1}, b2{0, 0};
+    CHECK(plan(two, a2, b2, ok, wide_limits(), p, err) == GA_E_ARG && err == "pair 1: sequences must be non-empty", "%s",
+          err.c_str());
+}
+
+// decode_levels against a character-by-character restatement of the reference's loop and tails
+void reference_strings(const std::vector<int>& lv, const std::string& a, const std::string& b, int reason,
+                       std::string& oa, std::string& om, std::string& ob, int64_t& i, int64_t& j) {
+    i = (int64_t)a.size();
+    j = (int64_t)b.size();
+    for (int l : lv) {
+        if (l == 0) {
+            oa += a[i - 1]; ob += b[j - 1]; om += a[i - 1] == b[j - 1] ? '|' : '*';
+            i--; j--;
+        } else if (l == 1) {
+            oa += '-'; om += ' '; ob += b[j - 1];
+            j--;
+        } else {
+            oa += a[i - 1]; om += ' '; ob += '-';
+            i--;
+        }
+    }
+    if (reason == 1) for (int64_t jj = j; jj > 0; jj--) { oa += '-'; om += ' '; ob += b[jj - 1]; }
+    if (reason == 2) for (int64_t ii = i; ii > 0; ii--) { oa += a[ii - 1]; om += ' '; ob += '-'; }
+    oa = std::string(oa.rbegin(), oa.rend());
+    om = std::string(om.rbegin(), om.rend());
+    ob = std::string(ob.rbegin(), ob.rend());
+}
+
+void test_decode() {
+    uint64_t x = 0x9e3779b97f4a7c15ull;
+    auto next = [&]() {
+        x ^= x << 13; x ^= x >> 7; x ^= x << 17;
+        return x;
+    };
+    int tails[3] = {0, 0, 0};
+    for (int rep = 0; rep < 400; rep++) {
+        const int m = 2 + (int)(next() % 40), n = 2 + (int)(next() % 40);
+        std::string a, b;
+        for (int k = 0; k < m; k++) a += "ACGT"[next() % 4];
+        for (int k = 0; k < n; k++) b += "ACGT"[next() % 4];
+        // a random walk from (m, n) to row 0 or column 0, biased so that both tails and the corner occur
+        std::vector<int> lv;
+        int i = m, j = n;
+        const int bias = rep % 3;
+        while (i > 0 && j > 0) {
+            const int r = (int)(next() % 4);
+            const int l = r < 2 ? 0 : bias == 0 ? r - 1 : bias;
+            lv.push_back(l);
+            i -= l != 1;
+            j -= l != 2;
+        }
+        const int reason = i == 0 ? (j == 0 ? 0 : 1) : 2;
+        tails[reason]++;
+        std::vector<uint32_t> ops((lv.size() + 15) / 16 + 1, 0xffffffffu);  // (bits past D are never read)
+        for (size_t k = 0; k < lv.size(); k++) {
+            ops[k >> 4] &= ~(3u << (30 - 2 * (k & 15)));
+            ops[k >> 4] |= (uint32_t)lv[k] << (30 - 2 * (k & 15));
+        }
+        std::string wa, wm, wb;
+        int64_t wi, wj;
+        reference_strings(lv, a, b, reason, wa, wm, wb, wi, wj);
+        const int64_t cap = m + n;
+        std::vector<char> oa((size_t)cap), om((size_t)cap), ob((size_t)cap);
+        const int64_t len = decode_levels(ops.data(), (int64_t)lv.size(), m, n, i, j, reason, a.data(), b.data(), oa.data(),
+                                          om.data(), ob.data(), cap);
+        CHECK(len == (int64_t)wa.size(), "length %lld, want %zu", (long long)len, wa.size());
+        if (len == (int64_t)wa.size())
+            CHECK(std::string(oa.data(), (size_t)len) == wa && std::string(om.data(), (size_t)len) == wm &&
+                      std::string(ob.data(), (size_t)len) == wb, "strings of walk %d", rep);
+        // too small a buffer, and an end cell the levels do not lead to
+        CHECK(decode_levels(ops.data(), (int64_t)lv.size(), m, n, i, j, reason, a.data(), b.data(), oa.data(), om.data(),
+                            ob.data(), len - 1) == -1, "capacity");
+        CHECK(decode_levels(ops.data(), (int64_t)lv.size(), m, n, i + 1, j, reason, a.data(), b.data(), oa.data(),
+                            om.data(), ob.data(), cap) == -2, "end cell");
+    }
+    CHECK(tails[0] > 0 && tails[1] > 0 && tails[2] > 0, "corner %d, row-0 %d and column-0 %d endings all occur", tails[0],
+          tails[1], tails[2]);
+    // a level 3, and levels that run past the matrix edge
+    const uint32_t bad = 0xc0000000u, diag[1] = {0};
+    char o1[8], o2[8], o3[8];
+    CHECK(decode_levels(&bad, 1, 2, 2, 1, 1, 0, "AC", "AC", o1, o2, o3, 8) == -2, "level 3");
+    CHECK(decode_levels(diag, 3, 2, 2, 0, 0, 0, "AC", "AC", o1, o2, o3, 8) == -2, "three diagonal steps in a 2 x 2 matrix");
+    CHECK(decode_levels(diag, 2, 2, 2, 0, 0, 0, "AC", "AG", o1, o2, o3, 8) == 2 && std::string(o2, 2) == "|*", "2 x 2");
+}
+
+void test_seed_and_tables() {
+    uint32_t st[garng::MTN + 1];
+    garng::seed_state(0, st);
+    CHECK(st[garng::MTN] == 624, "state index");
+    CHECK(st[0] == 2147483648u, "word 0 of every seeded state");
+    uint32_t st2[garng::MTN + 1];
+    garng::seed_state((uint64_t)1 << 32, st2);
+    bool differ = false;
+    for (int k = 1; k < garng::MTN; k++) differ |= st[k] != st2[k];
+    CHECK(differ, "seed 2^32 (key {0, 1}) differs from seed 0 (key {0})");
+    // the threaded build gives the sequential build's tables
+    Tables t(5, 5, 3, 4);
+    std::vector<int64_t> lens;
+    for (int k = 0; k < 300; k++) lens.push_back(2 + (k * 37) % 200);
+    Seqs sq(lens);
+    std::vector<int32_t> pa, pb;
+    std::vector<uint64_t> seeds;
+    for (int k = 0; k < 299; k++) {
+        pa.push_back(k);
+        pb.push_back(k + 1);
+        seeds.push_back(k % 7 == 0 ? 0 : ((uint64_t)k << 30) + (uint64_t)k);
+    }
+    AlignPlan p;
+    std::string err;
+    CHECK(plan(sq, pa, pb, t, wide_limits(), p, err) == GA_OK, "plan failed: %s", err.c_str());
+    std::vector<uint32_t> one((size_t)p.tab_entries, 0xdeadbeefu), many((size_t)p.tab_entries, 0xdeadbeefu);
+    build_pair_tables(p.kernel.data(), p.walk.data(), (int64_t)p.kernel.size(), seeds.data(), 1, one.data());
+    for (int nt : {2, 3, 8, 64}) {
+        std::fill(many.begin(), many.end(), 0xdeadbeefu);
+        build_pair_tables(p.kernel.data(), p.walk.data(), (int64_t)p.kernel.size(), seeds.data(), nt, many.data());
+        CHECK(one == many, "%d threads give the sequential tables", nt);
+    }
+    // a pair's table is build_rng's from its seeded state, whatever else the batch holds
+    for (size_t k = 0; k < p.kernel.size(); k += 50) {
+        garng::RngTable R;
+        garng::seed_state(seeds[(size_t)p.kernel[k].out], st);
+        const int64_t steps = p.kernel[k].m + p.kernel[k].n;
+        garng::build_rng(st, steps, R);
+        bool same = true;
+        for (int64_t d = 0; d < steps; d++) same &= R.tab[(size_t)d] == one[(size_t)(p.walk[k].tab_off + d)];
+        CHECK(same, "table of work item %zu", k);
+    }
+    CHECK(rng_threads(0, 1) == 1 && rng_threads(0, 64) == 1 && rng_threads(0, 1 << 20) <= kMaxRngThreads, "automatic");
+    CHECK(rng_threads(1, 1 << 20) == 1 && rng_threads(5, 10) == 5 && rng_threads(99, 10) == kMaxRngThreads, "requested");
+}
+
+}  // namespace
+
+int main() {
+    test_routing_and_order();
+    test_limits();
+    test_word_widths();
+    test_decode();
+    test_seed_and_tables();
+    if (failures) {
+        std::fprintf(stderr, "%d check(s) failed\n", failures);
+        return 1;
+    }
+    std::printf("all checks passed\n");
+    return 0;
+}

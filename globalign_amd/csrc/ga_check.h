@@ -48,6 +48,10 @@ inline int profile_bytes(const ga_costs* cs) {
     return subp_max <= 127 ? 1 : subp_max <= 32767 ? 2 : 0;
 }
 
+// bytes of a cell's traceback word by the gap-open cost (its fields hold values up to o + 1): 1 up to o = 6, 2 up to
+// 126, 4 up to 32766, 0 beyond
+inline int tb_word_bytes(int64_t o) { return (o + 1) < 8 ? 1 : (o + 1) < 128 ? 2 : (o + 1) < 32768 ? 4 : 0; }
+
 // GA_OK, or GA_E_ARG / GA_E_RANGE with the reason in err.  cb, ce: the column slab [cb, ce) of seq_2 this context
 // fills (the whole problem: 0, n_all); row0 / col0: caller-supplied boundary triples (both or neither).
 inline int check_problem(const uint8_t* a, int64_t m, const uint8_t* b_all, int64_t n_all, const ga_costs* cs,
@@ -82,7 +86,7 @@ inline int check_problem(const uint8_t* a, int64_t m, const uint8_t* b_all, int6
     out.qbytes = profile_bytes(cs);
     if (!out.qbytes) return fail(GA_E_RANGE, "substitution costs exceed the int16 query profile");
     const int o = cs->gap_open;
-    out.CB = (o + 1) < 8 ? 1 : (o + 1) < 128 ? 2 : (o + 1) < 32768 ? 4 : 0;
+    out.CB = tb_word_bytes(o);
     if (!out.CB) return fail(GA_E_RANGE, "gap_open cost too large for the traceback word");
     out.big = big;
     return GA_OK;

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 struct ga_batch_item;  // ga_batch.h
+struct ga_batch_walk_item;
 
 namespace ga {
 
@@ -213,5 +214,13 @@ void launch_lane_qprof(hipStream_t s, const uint8_t* a, int m, const int* subp, 
 void launch_batch_fill(hipStream_t s, const uint8_t* codes, const ga_batch_item* items, int nitems, const int* subp,
                        const int* gh, const int* gv, int K, int o, int qbytes, unsigned* ticket, long long* cost_out,
                        int2* scratch, long long scratch_rows, int waves);
+// many alignments with strings in one launch (batch_align_kernel): launch_batch_fill's arguments, then
+// CB (bytes of a traceback word), the walk items parallel to `items`, the pairs' tie-break entries, and the outputs:
+// packed levels, two int4 per pair ({dispatches, i, j, reason}, {fill ticks, walk ticks, 0, 0}), and the waves'
+// traceback scratch ([waves][tb_words] u32)
+void launch_batch_align(hipStream_t s, const uint8_t* codes, const ga_batch_item* items, int nitems, const int* subp,
+                        const int* gh, const int* gv, int K, int o, int qbytes, unsigned* ticket, long long* cost_out,
+                        int2* scratch, long long scratch_rows, int waves, int CB, const ga_batch_walk_item* witems,
+                        const uint32_t* rng, uint32_t* ops, int4* walk_out, uint32_t* tb, long long tb_words);
 
 }  // namespace ga

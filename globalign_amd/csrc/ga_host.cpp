@@ -30,6 +30,7 @@
 #include "ga_lane.h"
 #include "ga_check.h"
 #include "ga_batch.h"
+#include "ga_batch_align.h"
 #include "ga_rng.h"
 
 namespace {
@@ -207,6 +208,10 @@ struct ga_ctx {
     // ga_batch_costs: buffers of its own, so a loaded problem's stay as they are -- every sequence's
     // codes, the work list, sub' / gap tables, the ticket word, the costs, the waves' HBM edge columns
     DevBuf bt_codes, bt_items, bt_sub, bt_gh, bt_gv, bt_ticket, bt_out, bt_scratch;
+    // ga_batch_align adds the walk items, the pairs' tie-break tables, their packed levels and walk
+    // results, and the waves' traceback words; ga_batch_align_timings's figures of its last call
+    DevBuf bt_witems, bt_rng, bt_ops, bt_walk, bt_tb;
+    float batch_align_ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // [4], [5]: walk ns per dispatch, fill ns per cell
     int walk_jump_diag[3] = {0, 0, 0};  // the tie-to-tie walk's trips, region re-checks, ties (result[12..14])
     DevBuf jlut;           // the jump workers' LUT for gap open jlut_o (ga::jump_lut_build)
     int jlut_o = -1;
@@ -2264,7 +2269,8 @@ void ga_ctx_destroy(ga_ctx* c) {
                       &c->bnd_col, &c->meta, &c->hand, &c->flags, &c->tb, &c->out_last, &c->full, &c->rng, &c->ops,
                       &c->result, &c->halo_in, &c->dbg, &c->wdbg, &c->bscr, &c->ckpt, &c->colck, &c->stck,
                       &c->rc_tb, &c->rc_flags, &c->rc_pos, &c->rc_own, &c->link, &c->qprof, &c->bt_codes, &c->bt_items,
-                      &c->bt_sub, &c->bt_gh, &c->bt_gv, &c->bt_ticket, &c->bt_out, &c->bt_scratch})
+                      &c->bt_sub, &c->bt_gh, &c->bt_gv, &c->bt_ticket, &c->bt_out, &c->bt_scratch, &c->bt_witems, &c->bt_rng,
+                      &c->bt_ops, &c->bt_walk, &c->bt_tb})
         b->release();
     if (c->prog_host) (void)hipHostFree(c->prog_host);
     if (c->peer_link) (void)hipIpcCloseMemHandle(c->peer_link);
@@ -2402,6 +2408,163 @@ int ga_batch_costs_ex(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, i
             if (r) return fail(r, "pair " + std::to_string(k) + ": " + g_err);
         }
     }
+    return GA_OK;
+}
+
+int ga_batch_align(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                   const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                   const uint64_t* seeds, const char* chars, char* out_a, char* out_mid, char* out_b,
+                   const int64_t* out_off, int64_t* out_len, int32_t* tb_status, int64_t* cost_out) {
+    if (int r = check_ctx(c)) return r;
+    if (npairs == 0) return GA_OK;  // an empty batch: no launch
+    if (!seeds || !chars || !out_a || !out_mid || !out_b || !out_off || !out_len || !tb_status || !cost_out)
+        return fail(GA_E_ARG, "null argument");
+    const double t_call = now_ms();
+    for (float& x : c->batch_align_ms) x = 0.f;
+    const int64_t max_waves = (int64_t)c->num_cu * 4 * 2;  // as ga_batch_costs_ex
+    gabatch::AlignLimits lim;
+    if (const char* e = c->knob("GA_BATCH_ALIGN_MAX_CELLS")) lim.max_cells = std::max<int64_t>(0, atoll(e));
+    lim.scratch_rows_cap = gabatch::scratch_rows_cap(max_waves);
+    lim.tb_words_cap = gabatch::tb_slice_words_cap(max_waves);
+    gabatch::AlignPlan plan;
+    std::string why;
+    if (int r = gabatch::plan_batch_align(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim, plan,
+                                          why))
+        return fail(r, why);
+    auto len_of = [&](int64_t s) { return seq_off[s + 1] - seq_off[s]; };
+    for (int64_t k = 0; k < npairs; k++)
+        if (out_off[k] < 0 || out_off[k + 1] - out_off[k] < len_of(pair_a[k]) + len_of(pair_b[k]))
+            return fail(GA_E_ARG, "pair " + std::to_string(k) + ": output capacity too small");
+    if (!plan.single.empty() && c->slab)
+        return fail(GA_E_STATE, "pair " + std::to_string(plan.single[0]) +
+                                    ": needs the single-pair path, which a slab context cannot run");
+    const int K = cs->K;
+    if (!plan.kernel.empty()) {
+        const int nitems = (int)plan.kernel.size();
+        const int W = gabatch::kWavesPerGroup;
+        const int waves = (int)((std::min<int64_t>(max_waves, nitems) + W - 1) / W * W);
+        std::vector<int> subp((size_t)K * K);
+        for (int x = 0; x < K; x++)
+            for (int y = 0; y < K; y++) subp[x * K + y] = cs->sub[x * K + y] - cs->gap_v[x] - cs->gap_h[y];
+        const size_t ncodes = (size_t)seq_off[nseq];
+        HIPCHK(c->bt_codes.ensure(ncodes));
+        HIPCHK(c->bt_items.ensure(sizeof(ga_batch_item) * nitems));
+        HIPCHK(c->bt_witems.ensure(sizeof(ga_batch_walk_item) * nitems));
+        HIPCHK(c->bt_sub.ensure(sizeof(int) * K * K));
+        HIPCHK(c->bt_gh.ensure(sizeof(int) * K));
+        HIPCHK(c->bt_gv.ensure(sizeof(int) * K));
+        HIPCHK(c->bt_ticket.ensure(sizeof(unsigned)));
+        HIPCHK(c->bt_out.ensure(sizeof(long long) * npairs));
+        HIPCHK(c->bt_walk.ensure(sizeof(int4) * 2 * npairs));
+        HIPCHK(c->bt_rng.ensure(sizeof(uint32_t) * plan.tab_entries));
+        HIPCHK(c->bt_ops.ensure(sizeof(uint32_t) * plan.ops_words));
+        if (plan.scratch_rows > 0) HIPCHK(c->bt_scratch.ensure(sizeof(int2) * 2 * plan.scratch_rows * waves));
+        if (c->bt_tb.ensure(sizeof(uint32_t) * (size_t)plan.tb_words * waves) != hipSuccess)
+            return fail(GA_E_NOMEM, "no device memory for the batch's traceback words");
+        HIPCHK(hipMemcpyAsync(c->bt_codes.p, codes, ncodes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->bt_items.p, plan.kernel.data(), sizeof(ga_batch_item) * nitems, hipMemcpyHostToDevice,
+                              c->stream));
+        HIPCHK(hipMemcpyAsync(c->bt_witems.p, plan.walk.data(), sizeof(ga_batch_walk_item) * nitems,
+                              hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->bt_sub.p, subp.data(), sizeof(int) * K * K, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->bt_gh.p, cs->gap_h, sizeof(int) * K, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->bt_gv.p, cs->gap_v, sizeof(int) * K, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemsetAsync(c->bt_ticket.p, 0, sizeof(unsigned), c->stream));
+        // every pair's tie-break table from its own seed, on a few host threads
+        const double t_tab = now_ms();
+        std::vector<uint32_t> tab((size_t)plan.tab_entries);
+        const char* nt = c->knob("GA_BATCH_RNG_THREADS");
+        const int nthreads = gabatch::rng_threads(nt ? atoi(nt) : 0, nitems);
+        gabatch::build_pair_tables(plan.kernel.data(), plan.walk.data(), nitems, seeds, nthreads, tab.data());
+        c->batch_align_ms[1] = (float)(now_ms() - t_tab);
+        HIPCHK(hipMemcpyAsync(c->bt_rng.p, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipEventRecord(c->ev[0], c->stream));
+        ga::launch_batch_align(c->stream, c->bt_codes.as<uint8_t>(), c->bt_items.as<ga_batch_item>(), nitems,
+                               c->bt_sub.as<int>(), c->bt_gh.as<int>(), c->bt_gv.as<int>(), K, cs->gap_open, plan.qbytes,
+                               c->bt_ticket.as<unsigned>(), c->bt_out.as<long long>(),
+                               plan.scratch_rows > 0 ? c->bt_scratch.as<int2>() : nullptr, plan.scratch_rows, waves,
+                               plan.CB, c->bt_witems.as<ga_batch_walk_item>(), c->bt_rng.as<uint32_t>(),
+                               c->bt_ops.as<uint32_t>(), c->bt_walk.as<int4>(), c->bt_tb.as<uint32_t>(), plan.tb_words);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->ev[1], c->stream));
+        std::vector<long long> got((size_t)npairs);
+        std::vector<int4> walked((size_t)npairs * 2);
+        std::vector<uint32_t> ops((size_t)plan.ops_words);
+        HIPCHK(hipMemcpyAsync(got.data(), c->bt_out.p, sizeof(long long) * npairs, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(walked.data(), c->bt_walk.p, sizeof(int4) * 2 * npairs, hipMemcpyDeviceToHost,
+                              c->stream));
+        HIPCHK(hipMemcpyAsync(ops.data(), c->bt_ops.p, sizeof(uint32_t) * ops.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipEventElapsedTime(&c->fill_ms, c->ev[0], c->ev[1]));
+        c->batch_align_ms[0] = c->fill_ms;
+        // the strings, on the table build's threads (every pair writes its own outputs); out_len < 0: see below
+        const double t_dec = now_ms();
+        gabatch::run_shares(nitems, nthreads, [&](int64_t first, int64_t stride) {
+            for (int64_t t = first; t < nitems; t += stride) {
+                const ga_batch_item& it = plan.kernel[(size_t)t];
+                const size_t k = (size_t)it.out;
+                const int4 wr = walked[2 * k];
+                tb_status[k] = GA_TB_OK;
+                cost_out[k] = got[k];
+                out_len[k] =
+                    got[k] == INT64_MIN ? -3
+                    : wr.x < 0 || wr.x > (int64_t)it.m + it.n
+                        ? -2
+                        : gabatch::decode_levels(ops.data() + plan.walk[(size_t)t].ops_off, wr.x, it.m, it.n, wr.y,
+                                                 wr.z, wr.w, chars + it.a_off, chars + it.b_off, out_a + out_off[k],
+                                                 out_mid + out_off[k], out_b + out_off[k],
+                                                 out_off[k + 1] - out_off[k]);
+            }
+        });
+        c->batch_align_ms[2] = (float)(now_ms() - t_dec);
+        double fill_ticks = 0, walk_ticks = 0, steps = 0, cells = 0;
+        for (const ga_batch_item& it : plan.kernel) {
+            const size_t k = (size_t)it.out;
+            if (out_len[k] == -3)
+                return fail(GA_E_STATE, "pair " + std::to_string(k) + ": work item does not fit the batch launch");
+            if (out_len[k] < 0)
+                return fail(GA_E_STATE, "pair " + std::to_string(k) + ": the walk's levels do not decode");
+            fill_ticks += walked[2 * k + 1].x;
+            walk_ticks += walked[2 * k + 1].y;
+            steps += walked[2 * k].x;
+            cells += (double)it.m * it.n;
+        }
+        c->batch_align_ms[4] = (float)(10.0 * walk_ticks / std::max(steps, 1.0));  // (a tick is 10 ns)
+        c->batch_align_ms[5] = (float)(10.0 * fill_ticks / std::max(cells, 1.0));
+    }
+    if (!plan.single.empty()) {
+        // the single-pair path, one pair at a time, from that pair's seeded state (the state it leaves is dropped).
+        // It goes through the context's problem slot, so no problem is loaded afterwards.
+        c->rc_used = false;
+        uint32_t state[MTN + 1];
+        for (const int64_t k : plan.single) {
+            const int64_t sa = pair_a[k], sb = pair_b[k];
+            const int64_t m = len_of(sa), n = len_of(sb);
+            ga_costs own = *cs;  // this pair's sentinel comes from its own max_cost
+            if (pair_max_cost) own.max_cost = pair_max_cost[k];
+            seed_state(seeds[k], state);
+            int r = load_problem(c, codes + seq_off[sa], m, codes + seq_off[sb], n, &own, nullptr, nullptr, 0, n);
+            if (!r)
+                r = ga_problem_align(c, state, chars + seq_off[sa], chars + seq_off[sb], out_a + out_off[k],
+                                     out_mid + out_off[k], out_b + out_off[k], out_off[k + 1] - out_off[k], &out_len[k],
+                                     &tb_status[k], &cost_out[k]);
+            c->loaded = false;
+            if (r) return fail(r, "pair " + std::to_string(k) + ": " + g_err);
+        }
+    }
+    c->batch_align_ms[3] = (float)(now_ms() - t_call);
+    return GA_OK;
+}
+
+int ga_batch_align_timings(ga_ctx* c, float* out6) {
+    if (!c || !out6) return fail(GA_E_ARG, "null argument");
+    for (int q = 0; q < 6; q++) out6[q] = c->batch_align_ms[q];
+    return GA_OK;
+}
+
+int ga_debug_seed_state(uint64_t seed, uint32_t* state_out) {
+    if (!state_out) return fail(GA_E_ARG, "null argument");
+    seed_state(seed, state_out);
     return GA_OK;
 }
 

@@ -51,6 +51,45 @@ struct PyMT {
     }
 };
 
+// random.seed(seed) for an int seed, as the 625 words of random.getstate()[1] (Modules/_randommodule.c:
+// random_seed -> init_by_array over the seed's 32-bit little-endian chunks, one word below 2^32 -- {0} for seed 0 --
+// else two; the state index is 624, so the first draw twists).
+inline void seed_state(uint64_t seed, uint32_t out[MTN + 1]) {
+    struct Base {  // init_genrand(19650218), the same for every seed
+        uint32_t mt[MTN];
+        Base() {
+            mt[0] = 19650218u;
+            for (int k = 1; k < MTN; k++) mt[k] = 1812433253u * (mt[k - 1] ^ (mt[k - 1] >> 30)) + (uint32_t)k;
+        }
+    };
+    static const Base base;
+    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    const int klen = key[1] ? 2 : 1;
+    uint32_t* mt = out;
+    std::memcpy(mt, base.mt, sizeof(base.mt));
+    int i = 1, j = 0;
+    for (int k = MTN; k; k--) {  // MTN > klen
+        mt[i] = (mt[i] ^ ((mt[i - 1] ^ (mt[i - 1] >> 30)) * 1664525u)) + key[j] + (uint32_t)j;
+        i++;
+        j++;
+        if (i >= MTN) {
+            mt[0] = mt[MTN - 1];
+            i = 1;
+        }
+        if (j >= klen) j = 0;
+    }
+    for (int k = MTN - 1; k; k--) {
+        mt[i] = (mt[i] ^ ((mt[i - 1] ^ (mt[i - 1] >> 30)) * 1566083941u)) - (uint32_t)i;
+        i++;
+        if (i >= MTN) {
+            mt[0] = mt[MTN - 1];
+            i = 1;
+        }
+    }
+    mt[0] = 0x80000000u;
+    out[MTN] = MTN;
+}
+
 // ---------------------------------------------------------------- tie-break table
 // The dispatcher's 18 draws per step consume a variable number of MT words
 // (getrandbits(2) with rejection: r >= size -> draw again).  The scan below

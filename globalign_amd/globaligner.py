@@ -17,14 +17,16 @@ process-global ``random`` state exactly like the reference (18
 """
 import argparse
 import math
+import numbers
 import random
 import sys
+import types
 from pathlib import Path
 
 import numpy as np
 
 from . import _native
-from .results import AlignmentResults, BatchScores, final_cost_to_score
+from .results import AlignmentResults, BatchAlignments, BatchScores, final_cost_to_score
 from .scoring import MAX_SEQ_LEN_PROD, get_max_val, validate_and_transform_args
 
 __version__ = "0.1.0"
@@ -136,6 +138,44 @@ class GlobalAligner:
             seqs = seqs + seqs_2
         return self._score_batch(seqs, np.repeat(rows, len(cols)), np.tile(cols, len(rows)), (len(rows), len(cols)))
 
+    def align_pairs(self, seqs_1, seqs_2, seeds=0):
+        """Alignments of seqs_1[k] with seqs_2[k] for every k, strings included, in one call.  Pair k is aligned under
+        a random seed of its own: ``seeds`` is an int base (pair k uses base + k) or a sequence of one int per pair,
+        each in [0, 2**64).  Pair k's strings, cost and score are those of ``random.seed(s_k)`` followed by
+        ``GlobalAligner(**settings).align(seqs_1[k], seqs_2[k])``, whatever the batch's order or composition; the
+        process-global ``random`` state is left as it was.  Validation is score_pairs's.  A pair for which the single
+        call raises the reference's IndexError (possible only with a one-letter sequence) makes the call raise
+        IndexError("pair <k>: string index out of range") for the lowest such k.
+        -> BatchAlignments."""
+        seqs_1, seqs_2 = list(seqs_1), list(seqs_2)
+        if len(seqs_1) != len(seqs_2):
+            raise ValueError(f"align_pairs needs as many first as second sequences, got {len(seqs_1)} and "
+                             f"{len(seqs_2)}")
+        if not self.traceback:
+            raise ValueError("align_pairs returns alignment strings; an aligner made with traceback=False scores "
+                             "batches with score_pairs")
+        if len(self.devices) > 1:
+            raise ValueError(f"align_pairs runs on one GPU; this aligner was made with devices={self.devices}")
+        P = len(seqs_1)
+        seeds = _pair_seeds(seeds, P)
+        if P == 0:
+            e = self._empty_batch((0,))
+            return BatchAlignments([], [], [], e.costs, e.scores, *e[2:])
+        b = self._prepare_batch(seqs_1 + seqs_2, np.arange(P, dtype=np.int64), np.arange(P, 2 * P, dtype=np.int64))
+        if b.text is None:
+            raise ValueError("align_pairs takes sequences of one-byte (latin-1) letters")
+        eng = _native.default_engine(self.device)
+        costs, status, lengths, offsets, bufs = eng.batch_align(b.codes, b.seq_off, b.pair_a, b.pair_b, b.tables, seeds,
+                                                                np.frombuffer(b.text, dtype=np.uint8), b.pair_max_cost)
+        failed = np.flatnonzero(status == _native.GA_TB_INDEX_ERROR)
+        if failed.size:
+            raise IndexError(f"pair {int(failed[0])}: string index out of range")  # the reference's, SURVEY A.5
+        texts = [buf.tobytes().decode("latin-1") for buf in bufs]
+        lo, hi = offsets[:-1].tolist(), (offsets[:-1] + lengths).tolist()
+        strings = [[t[x:y] for x, y in zip(lo, hi)] for t in texts]
+        return BatchAlignments(strings[0], strings[1], strings[2], costs, b.scores(costs), b.scoring_mat, b.costing_mat,
+                               b.gap_open_score, b.gap_open_cost)
+
     def _empty_batch(self, shape):
         """No pairs: empty arrays, no launch.  The option checks still run, through the single call's validation of
         a placeholder pair; the matrices are reported only where they do not depend on the sequences (a named or
@@ -162,6 +202,18 @@ class GlobalAligner:
                              f"{self.devices}")
         if len(pair_a) == 0:
             return self._empty_batch(shape)
+        b = self._prepare_batch(seqs, pair_a, pair_b)
+        eng = _native.default_engine(self.device)
+        costs = eng.batch_costs(b.codes, b.seq_off, pair_a, pair_b, b.tables, b.pair_max_cost)
+        return BatchScores(costs.reshape(shape), b.scores(costs).reshape(shape), b.scoring_mat, b.costing_mat,
+                           b.gap_open_score, b.gap_open_cost)
+
+    def _prepare_batch(self, seqs, pair_a, pair_b):
+        """What a batch call needs before it asks for an engine (score_pairs, score_matrix, align_pairs): every pair
+        validated as the single call validates it, the batch's tables and codes, and the per-pair quantities of
+        one-letter pairs.  -> a namespace: pair_a, pair_b, codes, seq_off, tables, pair_max_cost, text (the
+        upper-cased sequences joined, as latin-1 bytes, or None), the matrices and gap-open values, and
+        scores(costs)."""
         try:
             joined = "".join(seqs)
         except TypeError:
@@ -238,12 +290,39 @@ class GlobalAligner:
             codes = np.frombuffer(text.translate(bytes(lut)), dtype=np.uint8)
         else:
             codes = np.fromiter((tables.code[ch] for ch in upper), dtype=np.uint8, count=len(upper))
-        eng = _native.default_engine(self.device)
-        costs = eng.batch_costs(codes, seq_off, pair_a, pair_b, tables, pair_max_cost)
-        scores = final_cost_to_score(cost=costs, m=lens[pair_a], n=lens[pair_b], max_score=max_score, delta_d=delta_d,
-                                     delta_i=delta_i)
-        return BatchScores(costs.reshape(shape), np.asarray(scores, dtype=np.int64).reshape(shape), scoring_mat,
-                           costing_mat, gap_open_score, gap_open_cost)
+
+        def scores(costs):
+            return np.asarray(final_cost_to_score(cost=costs, m=lens[pair_a], n=lens[pair_b], max_score=max_score,
+                                                  delta_d=delta_d, delta_i=delta_i), dtype=np.int64)
+
+        return types.SimpleNamespace(pair_a=pair_a, pair_b=pair_b, codes=codes, seq_off=seq_off, tables=tables,
+                                     pair_max_cost=pair_max_cost, text=text, scoring_mat=scoring_mat,
+                                     costing_mat=costing_mat, gap_open_score=gap_open_score,
+                                     gap_open_cost=gap_open_cost, scores=scores)
+
+
+def _pair_seeds(seeds, P):
+    """align_pairs's seeds as a uint64 array of P entries: an int base (pair k: base + k) or one int per pair, every
+    effective seed in [0, 2**64)."""
+    if isinstance(seeds, numbers.Integral):
+        values = [int(seeds), int(seeds) + max(P - 1, 0)]
+    else:
+        if isinstance(seeds, (str, bytes)):
+            raise TypeError("seeds must be an int or a sequence of ints")
+        try:
+            values = list(seeds)
+        except TypeError:
+            raise TypeError("seeds must be an int or a sequence of ints") from None
+        if len(values) != P:
+            raise ValueError(f"align_pairs needs one seed per pair, got {len(values)} seeds for {P} pairs")
+        if not all(isinstance(v, numbers.Integral) for v in values):
+            raise TypeError("seeds must be ints")
+        values = [int(v) for v in values]
+    if any(v < 0 or v >= 2 ** 64 for v in values):
+        raise ValueError("every seed must be in [0, 2**64)")
+    if isinstance(seeds, numbers.Integral):
+        return np.uint64(values[0]) + np.arange(P, dtype=np.uint64)
+    return np.array(values, dtype=np.uint64)
 
 
 def _one_letter_sequences(upper, text, seq_off):

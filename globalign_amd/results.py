@@ -129,3 +129,25 @@ class AlignmentResults(NamedTuple):
             out.append(f"{q - k}{ops[k]}")
             k = q
         return "".join(out)
+
+
+class BatchAlignments(NamedTuple):
+    """Alignments of many pairs (GlobalAligner.align_pairs): per pair the three strings, in lists, and the cost and
+    score, in numpy int64 arrays of shape (P,), with the settings every pair was aligned under.  The matrices are the
+    batch's -- for match / mismatch settings they span the letters of the whole batch --, not those the single call
+    builds over one pair's own letters; every entry a pair reads is the same in both."""
+    seq_1_aligned: list
+    middle_part: list
+    seq_2_aligned: list
+    costs: "numpy.ndarray"
+    scores: "numpy.ndarray"
+    scoring_mat: dict
+    costing_mat: dict
+    gap_open_score: int
+    gap_open_cost: int
+
+    def result(self, k):
+        """Pair k as an AlignmentResults (output=None), with the batch's matrices."""
+        return AlignmentResults(self.seq_1_aligned[k], self.middle_part[k], self.seq_2_aligned[k], int(self.costs[k]),
+                                int(self.scores[k]), self.scoring_mat, self.costing_mat, self.gap_open_score,
+                                self.gap_open_cost, None)

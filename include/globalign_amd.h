@@ -116,6 +116,43 @@ int ga_batch_costs_ex(ga_ctx* ctx, const uint8_t* codes, const int64_t* seq_off,
                       const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* costs,
                       int64_t* cost_out);
 
+/* Alignments of many pairs in one call, strings included, every pair with a
+ * random seed of its own.  For pair k this replaces random.seed(seeds[k])
+ * followed by find_global_alignment (globaligner.py:258-302: make_dp_array,
+ * dp_array_forward, dp_array_backward with cost_ranks_dispatcher's
+ * random.choice calls): the strings, the cost and the traceback status are
+ * what ga_problem_set + ga_problem_align give from the 625-word state
+ * ga_debug_seed_state(seeds[k]) makes.  No state is returned: the pairs do not
+ * share a random stream, so the results do not depend on the batch's order or
+ * composition.
+ * codes .. costs: as ga_batch_costs_ex, with the same checks and errors.
+ * chars: the upper-cased sequences' characters, concatenated as codes is (one
+ * byte each).  Pair k's strings go to out_a / out_mid / out_b at offset
+ * out_off[k] (npairs + 1 entries; out_off[k+1] - out_off[k] is the pair's
+ * capacity: m + n suffices for a pair whose sequences have two letters or
+ * more, m + n + 1 for any pair), unterminated, out_len[k] bytes each;
+ * tb_status[k] receives GA_TB_OK or GA_TB_INDEX_ERROR (possible only when a
+ * sequence has one letter; out_len[k] is then 0), cost_out[k] the cost.
+ * Short pairs share one kernel launch, one wave per pair filling and then
+ * walking it.  The single-pair path (ga_problem_align) takes a pair with a
+ * one-letter sequence, one above GA_BATCH_ALIGN_MAX_CELLS cells (a context
+ * option), or one that does not fit the kernel's LDS, edge
+ * scratch or traceback scratch; what ga_batch_costs says about loaded
+ * problems and slab contexts holds here too.  The pairs' tie-break tables are
+ * built on up to 8 host threads (option GA_BATCH_RNG_THREADS; 1: none).
+ * npairs = 0 returns GA_OK without a launch. */
+int ga_batch_align(ga_ctx* ctx, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                   const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* costs,
+                   const uint64_t* seeds, const char* chars, char* out_a, char* out_mid, char* out_b,
+                   const int64_t* out_off, int64_t* out_len, int32_t* tb_status, int64_t* cost_out);
+/* out6 = {kernel ms, host tie-break tables ms, host string decode ms, whole call wall ms, the walks' ns per
+ * dispatch, the fills' ns per cell} of the last ga_batch_align.  All but the call's cover the pairs that shared
+ * the kernel launch; the last two are averages of what each wave timed for its own pairs. */
+int ga_batch_align_timings(ga_ctx* ctx, float* out6);
+/* random.seed(seed) for an int seed (Modules/_randommodule.c random_seed): the 625 words of
+ * random.getstate()[1] it leaves.  CPU only. */
+int ga_debug_seed_state(uint64_t seed, uint32_t* state_out);
+
 /* Traceback walk (dp_array_backward :395-593, cost_ranks_dispatcher
  * :595-685, take_* :688-753) on the last GA_FILL_TRACEBACK fill.
  * mt_state: 625 words = random.getstate()[1] in, the state after the

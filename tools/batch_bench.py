@@ -1,11 +1,18 @@
-"""Throughput of the batched score-only calls (GlobalAligner.score_pairs / score_matrix): one JSON
-line per workload with pairs, cells, ms (median of 5 calls after 2 warm-ups), pairs_per_s and cells_per_s.
+"""Throughput of the batched calls (GlobalAligner.score_pairs / score_matrix; align_pairs, 5.11): one
+JSON line per workload with pairs, cells, ms (median of 5 calls after 2 warm-ups), pairs_per_s and cells_per_s.
 
     python tools/batch_bench.py                 B1, B2, B3
     python tools/batch_bench.py --loop K        K of B1's pairs through GlobalAligner(traceback=False).align, one at a
                                                 time (only API that predates the batch calls: runs on older trees too)
     python tools/batch_bench.py --crossover     one pair per call through the batch kernel and through the single-pair
                                                 fill, at growing sizes (the GA_BATCH_MAX_CELLS default)
+    python tools/batch_bench.py --align         B1 and B2 through align_pairs (strings included), with the kernel, host
+                                                table and host decode ms of the last call and us per pair; B1 also
+                                                with the tables built on one thread
+    python tools/batch_bench.py --align-loop K  K of B1's pairs through random.seed(s) + GlobalAligner.align, one at a
+                                                time (runs on older trees too)
+    python tools/batch_bench.py --align-crossover   one pair per align_pairs call through the batch kernel and through
+                                                the single-pair path, at growing sizes (GA_BATCH_ALIGN_MAX_CELLS)
 
 Workloads (SplitMix64 sequences of tests.conftest, lengths from a seeded random.Random):
   B1  4096 DNA pairs, lengths 200-400         B2  1024 BLOSUM62 pairs, lengths 100-600
@@ -92,13 +99,69 @@ def crossover():
         del _native.OPTIONS["GA_BATCH_MAX_CELLS"]
 
 
+def align_workloads():
+    def run(name, pairs, kw, **options):
+        _native.OPTIONS.update({k: str(v) for k, v in options.items()})
+        try:
+            al = GlobalAligner(max_seq_len_prod=None, **kw)
+            a, b = [p[0] for p in pairs], [p[1] for p in pairs]
+            ms = timed(lambda: al.align_pairs(a, b, seeds=1))
+            t = _native.default_engine(0).batch_align_timings()
+            report(name, len(pairs), sum(len(x) * len(y) for x, y in pairs), ms, us_per_pair=round(ms * 1e3 / len(pairs), 3),
+                   **{k: round(v, 4) for k, v in t.items()}, **options)
+        finally:
+            for k in options:
+                del _native.OPTIONS[k]
+
+    b1 = pairs_of(4096, 200, 400, "dna", 1)
+    run("B1-align", b1, DNA)
+    run("B1-align", b1, DNA, GA_BATCH_RNG_THREADS=1)
+    run("B2-align", pairs_of(1024, 100, 600, "protein", 2), BLOSUM)
+
+
+def align_loop(count):
+    """The per-pair loop a user writes without align_pairs: random.seed + one align per pair."""
+    b1 = pairs_of(count, 200, 400, "dna", 1)
+    al = GlobalAligner(max_seq_len_prod=None, **DNA)
+
+    def call():
+        for k, (x, y) in enumerate(b1):
+            random.seed(1 + k)
+            al.align(x, y)
+
+    ms = timed(call)
+    report("B1-align-loop", len(b1), sum(len(x) * len(y) for x, y in b1), ms, us_per_pair=round(ms * 1e3 / len(b1), 3))
+
+
+def align_crossover():
+    for side in (64, 128, 256, 384, 512, 768, 1024, 1536, 2048):
+        x, y = splitmix_seq(side, 1, "dna"), splitmix_seq(side, 2, "dna")
+        for route, limit in (("kernel", 1 << 40), ("single", 0)):
+            _native.OPTIONS["GA_BATCH_ALIGN_MAX_CELLS"] = str(limit)
+            al = GlobalAligner(max_seq_len_prod=None, **DNA)
+            ms = timed(lambda: al.align_pairs([x], [y], seeds=1))
+            t = _native.default_engine(0).batch_align_timings()
+            report(f"1x {side}x{side} align {route}", 1, side * side, ms,
+                   **{k: round(t[k], 4) for k in ("kernel_ms", "walk_ns_per_step", "fill_ns_per_cell")})
+        del _native.OPTIONS["GA_BATCH_ALIGN_MAX_CELLS"]
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--loop", type=int, default=0, metavar="K")
     ap.add_argument("--crossover", action="store_true")
+    ap.add_argument("--align", action="store_true")
+    ap.add_argument("--align-loop", type=int, default=0, metavar="K")
+    ap.add_argument("--align-crossover", action="store_true")
     args = ap.parse_args()
     if args.loop:
         loop(args.loop)
+    elif args.align:
+        align_workloads()
+    elif args.align_loop:
+        align_loop(args.align_loop)
+    elif args.align_crossover:
+        align_crossover()
     elif args.crossover:
         crossover()
     else:
