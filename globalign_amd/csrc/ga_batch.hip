@@ -23,20 +23,6 @@
 
 namespace ga {
 
-struct BatchArgs {
-    const uint8_t* codes;        // every sequence's codes, concatenated
-    const ga_batch_item* items;  // the work list
-    int nitems;
-    const int* subp;             // K x K: sub' = sub - gV - gH
-    const int* gh;               // K: horizontal gap costs
-    const int* gv;               // K: vertical gap costs
-    int K, o;
-    unsigned* ticket;            // zeroed by the host ahead of every launch
-    long long* cost_out;         // [npairs], indexed by ga_batch_item::out
-    int2* scratch;               // [waves][2][scratch_rows] edge columns (nullptr: no pair needs them)
-    long long scratch_rows;
-};
-
 // what a masked column contributes to the prefix-min: above every value the range guard admits (|v| < 2^29), and
 // INF + o still clear of overflow
 constexpr int BATCH_INF = 0x3f000000;
@@ -328,16 +314,6 @@ __global__ void __launch_bounds__(64 * gabatch::kWavesPerGroup) batch_fill_kerne
 // traceback words kept, then the traceback walk (dp_array_backward, globaligner.py:395-593) by the same wave, from
 // (m, n) to row 0 or column 0, under the pair's own tie-break table.  The work list holds only pairs with
 // min(m, n) >= 2: their walks stay inside the matrix (no first-step quirk, no IndexError).
-struct AlignArgs {
-    BatchArgs b;
-    const ga_batch_walk_item* witems;  // parallel to b.items
-    const uint32_t* rng;               // the pairs' tie-break entries (ga_rng.h), pair t at witems[t].tab_off
-    uint32_t* ops;                     // the chosen levels, 2 bits per dispatch, pair t at witems[t].ops_off
-    int4* walk_out;                    // [npairs][2] {dispatches, i, j, reason}, {fill ticks, walk ticks, 0, 0} (10 ns
-                                       // ticks of s_memrealtime), indexed by ga_batch_item::out
-    uint32_t* tb;                      // [waves][tb_words] traceback words
-    long long tb_words;
-};
 
 // The walk of one pair by one wave.  Groups of up to 7 steps: one vector load per lane fetches the 8 x 8 window
 // anchored at the current cell (lane r * 8 + c: cell (i - r, j - c), clamped at row / column 1 -- a clamped cell is
@@ -466,13 +442,7 @@ static void launch_batch_align_q(hipStream_t s, const AlignArgs& q, int CB, int 
     else batch_align_kernel<QT, 4><<<groups, threads, 0, s>>>(q);
 }
 
-// launch_batch_fill's arguments, then CB (the traceback word's bytes: 1, 2 or 4) and the walk's buffers
-void launch_batch_align(hipStream_t s, const uint8_t* codes, const ga_batch_item* items, int nitems, const int* subp,
-                        const int* gh, const int* gv, int K, int o, int qbytes, unsigned* ticket, long long* cost_out,
-                        int2* scratch, long long scratch_rows, int waves, int CB, const ga_batch_walk_item* witems,
-                        const uint32_t* rng, uint32_t* ops, int4* walk_out, uint32_t* tb, long long tb_words) {
-    const AlignArgs q{BatchArgs{codes, items, nitems, subp, gh, gv, K, o, ticket, cost_out, scratch, scratch_rows},
-                      witems, rng, ops, walk_out, tb, tb_words};
+void launch_batch_align(hipStream_t s, const AlignArgs& q, int qbytes, int CB, int waves) {
     const int groups = waves / gabatch::kWavesPerGroup;
     if (qbytes == 1) launch_batch_align_q<int8_t>(s, q, CB, groups);
     else if (qbytes == 2) launch_batch_align_q<int16_t>(s, q, CB, groups);
@@ -480,10 +450,7 @@ void launch_batch_align(hipStream_t s, const uint8_t* codes, const ga_batch_item
 }
 
 // waves: resident waves the host sized the grid (and the scratch) for; a multiple of kWavesPerGroup
-void launch_batch_fill(hipStream_t s, const uint8_t* codes, const ga_batch_item* items, int nitems, const int* subp,
-                       const int* gh, const int* gv, int K, int o, int qbytes, unsigned* ticket, long long* cost_out,
-                       int2* scratch, long long scratch_rows, int waves) {
-    BatchArgs p{codes, items, nitems, subp, gh, gv, K, o, ticket, cost_out, scratch, scratch_rows};
+void launch_batch_fill(hipStream_t s, const BatchArgs& p, int qbytes, int waves) {
     const int groups = waves / gabatch::kWavesPerGroup;
     if (qbytes == 1)
         batch_fill_kernel<int8_t><<<groups, 64 * gabatch::kWavesPerGroup, 0, s>>>(p);

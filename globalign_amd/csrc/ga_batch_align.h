@@ -3,7 +3,8 @@
 //
 // Every pair of the batch walks with a tie-break stream of its own, the one `random.seed(seed)` starts, so the walks
 // do not depend on each other: build_pair_tables makes the kernel pairs' tables (ga_rng.h) on a few threads, and
-// decode_levels turns a finished walk's packed levels into the three alignment strings.
+// decode_levels turns a finished walk's packed levels into the three alignment strings with the engine's one decoder
+// (ga_strings.h) in its strict mode, checking that the levels lead to the end cell the walk reported.
 #pragma once
 #include <stdint.h>
 
@@ -13,6 +14,7 @@
 
 #include "ga_batch.h"
 #include "ga_rng.h"
+#include "ga_strings.h"
 
 namespace gabatch {
 
@@ -57,39 +59,17 @@ inline void build_pair_tables(const ga_batch_item* items, const ga_batch_walk_it
     });
 }
 
-// The strings of one walk (dp_array_backward's output, globaligner.py:514-586): the levels of dispatches [0, D),
-// 2 bits each, dispatch k at bits 30 - 2 * (k & 15) of ops[k >> 4], walked from (m, n) -- level 0 takes a column of
-// both sequences, 1 a gap above seq_2's letter, 2 seq_1's letter above a gap --, then the reference's tail for a walk
-// that ended in row 0 (reason 1: the rest of seq_2 under gaps) or column 0 (reason 2: the rest of seq_1 over gaps),
-// then the reversal.  Returns the length, -1 when it exceeds cap, -2 when the levels do not lead to (i_end, j_end)
-// inside the matrix.
+// The strings of one walk from (m, n): the levels of dispatches [0, D) out of `ops` through ga_strings.h's strict
+// decode, then its tail for `reason` and the reversal.  Returns the length, -1 when it exceeds cap, -2 when the levels
+// do not lead to (i_end, j_end) inside the matrix.
 inline int64_t decode_levels(const uint32_t* ops, int64_t D, int64_t m, int64_t n, int64_t i_end, int64_t j_end,
                              int reason, const char* a_chr, const char* b_chr, char* oa, char* om, char* ob,
                              int64_t cap) {
-    int64_t i = m, j = n, len = 0;
-    auto put = [&](char x, char y, char z) {
-        if (len < cap) { oa[len] = x; om[len] = y; ob[len] = z; }
-        len++;
-    };
-    for (int64_t k = 0; k < D; k++) {
-        if (i < 1 || j < 1) return -2;
-        const char ca = a_chr[i - 1], cb = b_chr[j - 1];
-        const unsigned lv = (ops[k >> 4] >> (30 - 2 * (k & 15))) & 3u;
-        if (lv == 0) { put(ca, ca == cb ? '|' : '*', cb); i--; j--; }
-        else if (lv == 1) { put('-', ' ', cb); j--; }
-        else if (lv == 2) { put(ca, ' ', '-'); i--; }
-        else return -2;
-    }
-    if (i != i_end || j != j_end || (i > 0 && j > 0)) return -2;
-    if (reason == 1)
-        for (int64_t jj = j; jj > 0; jj--) put('-', ' ', b_chr[jj - 1]);
-    else if (reason == 2)
-        for (int64_t ii = i; ii > 0; ii--) put(a_chr[ii - 1], ' ', '-');
-    if (len > cap) return -1;
-    std::reverse(oa, oa + len);
-    std::reverse(om, om + len);
-    std::reverse(ob, ob + len);
-    return len;
+    gastr::Columns col{a_chr, m, b_chr, n, oa, om, ob, cap, m, n};
+    if (!col.decode<true>(ops, 0, 0, D)) return -2;
+    if (col.i != i_end || col.j != j_end || (col.i > 0 && col.j > 0)) return -2;
+    const int64_t len = gastr::finish_strings(reason, col.i, col.j, a_chr, b_chr, oa, om, ob, cap, col.len);
+    return len > cap ? -1 : len;
 }
 
 }  // namespace gabatch

@@ -1,5 +1,6 @@
 // ga_batch_align_selftest.cpp -- CPU self-test of the host's share of ga_batch_align: the align planner (ga_batch.h
-// plan_batch_align), the per-pair tie-break tables and the levels-to-strings decode (ga_batch_align.h), plain, under
+// plan_batch_align), the per-pair tie-break tables and the levels-to-strings decode (ga_batch_align.h's decode_levels
+// and, under it and under every single-pair walk, ga_strings.h's resumable decoder), plain, under
 // AddressSanitizer + UndefinedBehaviorSanitizer and -- for the threaded table build -- under ThreadSanitizer
 // (make -C globalign_amd/csrc batch_align_selftest batch_align_asan batch_align_tsan; run by
 // tests/test_batch_align_host.py).  No HIP: the kernel is tested on the GPU.
@@ -239,6 +240,132 @@ void test_decode() {
     CHECK(decode_levels(diag, 2, 2, 2, 0, 0, 0, "AC", "AG", o1, o2, o3, 8) == 2 && std::string(o2, 2) == "|*", "2 x 2");
 }
 
+// gastr::Columns (ga_strings.h), the decoder every walk of the engine goes through: a piece [D0, D1) out of a word array
+// that starts at word D0 >> 4, any chunking, and the lenient mode's Python-style indexing at i == 0 / j == 0.  Letters,
+// words and outputs live in heap buffers of exactly the size in use, so AddressSanitizer sees any index outside them.
+struct Decoded {
+    std::vector<char> oa, om, ob;
+    int64_t i, j, len;
+    int L;
+    bool ok;
+    bool operator==(const Decoded& o) const {
+        return oa == o.oa && om == o.om && ob == o.ob && i == o.i && j == o.j && len == o.len && L == o.L && ok == o.ok;
+    }
+};
+
+// dispatches [0, D) of `ops` from (m, n), in the given chunks (chunk <= 0: one call)
+template <bool STRICT>
+Decoded decode_chunked(const std::vector<uint32_t>& ops, int64_t D, const std::vector<char>& a, const std::vector<char>& b,
+                       int64_t cap, int64_t chunk) {
+    Decoded d{std::vector<char>((size_t)cap, '?'), std::vector<char>((size_t)cap, '?'), std::vector<char>((size_t)cap, '?'),
+              0, 0, 0, 0, true};
+    gastr::Columns col{a.data(), (int64_t)a.size(), b.data(), (int64_t)b.size(), d.oa.data(), d.om.data(), d.ob.data(),
+                       cap, (int64_t)a.size(), (int64_t)b.size()};
+    if (chunk <= 0) chunk = std::max<int64_t>(D, 1);
+    for (int64_t k = 0; k < D && d.ok; k += chunk) d.ok = col.decode<STRICT>(ops.data(), 0, k, std::min(D, k + chunk));
+    d.i = col.i;
+    d.j = col.j;
+    d.len = col.len;
+    d.L = col.L;
+    return d;
+}
+
+std::vector<uint32_t> pack_levels(const std::vector<int>& lv) {
+    std::vector<uint32_t> ops((lv.size() + 15) / 16, 0xffffffffu);  // (bits past the last dispatch are never read)
+    for (size_t k = 0; k < lv.size(); k++) ops[k >> 4] ^= (uint32_t)(3 - lv[k]) << (30 - 2 * (k & 15));
+    return ops;
+}
+
+void test_columns() {
+    uint64_t x = 0x2545f4914f6cdd1dull;
+    auto next = [&]() {
+        x ^= x << 13; x ^= x >> 7; x ^= x << 17;
+        return x;
+    };
+    int segments = 0;
+    for (int rep = 0; rep < 300; rep++) {
+        const int m = 2 + (int)(next() % 39), n = 2 + (int)(next() % 39);
+        std::vector<char> a((size_t)m), b((size_t)n);
+        for (char& ch : a) ch = "ACGT"[next() % 4];
+        for (char& ch : b) ch = "ACGT"[next() % 4];
+        std::vector<int> lv;
+        for (int i = m, j = n; i > 0 && j > 0;) {
+            const int r = (int)(next() % 4);
+            const int l = r < 2 ? 0 : r - 1;
+            lv.push_back(l);
+            i -= l != 1;
+            j -= l != 2;
+        }
+        const int64_t D = (int64_t)lv.size();
+        const std::vector<uint32_t> ops = pack_levels(lv);
+        const Decoded one = decode_chunked<false>(ops, D, a, b, D, 0);
+        CHECK(one.ok && one.len == D && one.L == lv.back() && (one.i == 0 || one.j == 0), "one-shot decode of walk %d", rep);
+        // a walk inside the matrix decodes alike in both modes
+        CHECK(decode_chunked<true>(ops, D, a, b, D, 0) == one, "strict = lenient inside the matrix (walk %d)", rep);
+        // chunks of 1, 7, 16 and 17 dispatches: the same strings and end state
+        for (int64_t chunk : {1, 7, 16, 17}) {
+            CHECK(decode_chunked<false>(ops, D, a, b, D, chunk) == one, "chunks of %lld (walk %d)", (long long)chunk, rep);
+            CHECK(decode_chunked<true>(ops, D, a, b, D, chunk) == one, "strict chunks of %lld (walk %d)", (long long)chunk, rep);
+        }
+        // too small a buffer: len counts on, nothing is written past cap
+        const Decoded small = decode_chunked<false>(ops, D, a, b, D - 1, 7);
+        CHECK(small.len == D && small.i == one.i && small.j == one.j &&
+                  std::equal(small.oa.begin(), small.oa.end(), one.oa.begin()), "capacity (walk %d)", rep);
+        // a segment [D0, D1), D0 not a multiple of 16, out of the words from D0 >> 4 on, started at the state the
+        // dispatches before D0 leave: the matching slice of the one-shot columns
+        if (D < 3) continue;
+        int64_t D0 = 1 + (int64_t)(next() % (uint64_t)(D - 1));
+        if ((D0 & 15) == 0) D0--;
+        const int64_t D1 = D0 + 1 + (int64_t)(next() % (uint64_t)(D - D0));
+        int64_t i0 = m, j0 = n;
+        for (int64_t k = 0; k < D0; k++) {
+            i0 -= lv[(size_t)k] != 1;
+            j0 -= lv[(size_t)k] != 2;
+        }
+        const int64_t w0 = D0 >> 4, w1 = (D1 + 15) >> 4;
+        const std::vector<uint32_t> part(ops.begin() + w0, ops.begin() + w1);
+        const int64_t cap = D1 - D0;
+        std::vector<char> oa((size_t)cap), om((size_t)cap), ob((size_t)cap);
+        gastr::Columns col{a.data(), m, b.data(), n, oa.data(), om.data(), ob.data(), cap, i0, j0, lv[(size_t)D0 - 1]};
+        CHECK(col.decode<false>(part.data(), w0, D0, D1) && col.len == cap, "segment decode (walk %d)", rep);
+        CHECK(std::equal(oa.begin(), oa.end(), one.oa.begin() + D0) && std::equal(om.begin(), om.end(), one.om.begin() + D0) &&
+                  std::equal(ob.begin(), ob.end(), one.ob.begin() + D0), "segment [%lld, %lld) of walk %d", (long long)D0,
+              (long long)D1, rep);
+        segments++;
+    }
+    CHECK(segments > 250, "segments decoded: %d", segments);
+    // Python's seq[-1]: a step taken from i == 0 (j == 0) reads the last letter of seq_1 (seq_2) in lenient mode, as the
+    // reference's first step at m == 1 / n == 1 does; strict mode stops there, having read nothing for that step
+    for (int side = 0; side < 2; side++)
+        for (int m = 1; m <= 5; m++)
+            for (int n = 1; n <= 5; n++) {
+                std::vector<char> a((size_t)m), b((size_t)n);
+                for (int k = 0; k < m; k++) a[(size_t)k] = (char)('a' + k);
+                for (int k = 0; k < n; k++) b[(size_t)k] = (char)('p' + k);
+                // down column n to row 0 (side 1: along row m to column 0), then one more diagonal step
+                std::vector<int> lv((size_t)(side == 0 ? m : n), side == 0 ? 2 : 1);
+                lv.push_back(0);
+                const int64_t D = (int64_t)lv.size(), edge = D - 1;
+                const std::vector<uint32_t> ops = pack_levels(lv);
+                // that step, from (0, n) [(m, 0)], pairs the last letters of both sequences: one of them is seq[-1]
+                const Decoded py = decode_chunked<false>(ops, D, a, b, D, 0);
+                CHECK(py.ok && py.len == D && py.oa[(size_t)edge] == a[(size_t)m - 1] && py.om[(size_t)edge] == '*' &&
+                          py.ob[(size_t)edge] == b[(size_t)n - 1], "wrapped step, side %d, %d x %d", side, m, n);
+                CHECK(side == 0 ? (py.i == -1 && py.j == n - 1) : (py.i == m - 1 && py.j == -1), "end cell past the edge");
+                const Decoded st = decode_chunked<true>(ops, D, a, b, D, 0);
+                CHECK(!st.ok && st.len == edge && (side == 0 ? st.i == 0 && st.j == n : st.i == m && st.j == 0),
+                      "strict mode stops at the edge, side %d, %d x %d", side, m, n);
+                CHECK(std::equal(st.oa.begin(), st.oa.begin() + edge, py.oa.begin()) && st.oa[(size_t)edge] == '?',
+                      "strict mode wrote the steps before the edge only");
+            }
+    // a level 3: level 2 in lenient mode, refused in strict mode
+    const std::vector<char> a{'A', 'C'}, b{'G', 'T'};
+    const std::vector<uint32_t> three{0xc0000000u};
+    const Decoded l3 = decode_chunked<false>(three, 1, a, b, 1, 0);
+    CHECK(l3.ok && l3.oa[0] == 'C' && l3.om[0] == ' ' && l3.ob[0] == '-' && l3.i == 1 && l3.j == 2 && l3.L == 3, "lenient level 3");
+    CHECK(!decode_chunked<true>(three, 1, a, b, 1, 0).ok, "strict level 3");
+}
+
 void test_seed_and_tables() {
     uint32_t st[garng::MTN + 1];
     garng::seed_state(0, st);
@@ -292,6 +419,7 @@ int main() {
     test_limits();
     test_word_widths();
     test_decode();
+    test_columns();
     test_seed_and_tables();
     if (failures) {
         std::fprintf(stderr, "%d check(s) failed\n", failures);

@@ -208,19 +208,35 @@ void launch_fill_lane(hipStream_t s, const FillArgs& p, int CB);
 size_t fill_lane_lds_bytes(int nwc, int K, int qrows);
 // the lane fill's query profile (FillArgs::qprof) of rows a[0 .. m-1]: K x (m + 4) dwords at out
 void launch_lane_qprof(hipStream_t s, const uint8_t* a, int m, const int* subp, int K, uint32_t* out);
-// many score-only pairs in one launch, one wave per pair (ga_batch.hip): `items` is the planner's
-// work list (ga_batch.h), `waves` the resident waves the grid and the edge scratch ([waves][2][scratch_rows] int2,
-// nullptr when no pair needs it) are sized for, `ticket` a word the caller zeroes ahead of every launch
-void launch_batch_fill(hipStream_t s, const uint8_t* codes, const ga_batch_item* items, int nitems, const int* subp,
-                       const int* gh, const int* gv, int K, int o, int qbytes, unsigned* ticket, long long* cost_out,
-                       int2* scratch, long long scratch_rows, int waves);
-// many alignments with strings in one launch (batch_align_kernel): launch_batch_fill's arguments, then
-// CB (bytes of a traceback word), the walk items parallel to `items`, the pairs' tie-break entries, and the outputs:
-// packed levels, two int4 per pair ({dispatches, i, j, reason}, {fill ticks, walk ticks, 0, 0}), and the waves'
-// traceback scratch ([waves][tb_words] u32)
-void launch_batch_align(hipStream_t s, const uint8_t* codes, const ga_batch_item* items, int nitems, const int* subp,
-                        const int* gh, const int* gv, int K, int o, int qbytes, unsigned* ticket, long long* cost_out,
-                        int2* scratch, long long scratch_rows, int waves, int CB, const ga_batch_walk_item* witems,
-                        const uint32_t* rng, uint32_t* ops, int4* walk_out, uint32_t* tb, long long tb_words);
+// many score-only pairs in one launch, one wave per pair (ga_batch.hip): the planner's work list
+// (ga_batch.h) and the buffers of batch_fill_kernel
+struct BatchArgs {
+    const uint8_t* codes;        // every sequence's codes, concatenated
+    const ga_batch_item* items;  // the work list
+    int nitems;
+    const int* subp;             // K x K: sub' = sub - gV - gH
+    const int* gh;               // K: horizontal gap costs
+    const int* gv;               // K: vertical gap costs
+    int K, o;
+    unsigned* ticket;            // zeroed by the host ahead of every launch
+    long long* cost_out;         // [npairs], indexed by ga_batch_item::out
+    int2* scratch;               // [waves][2][scratch_rows] edge columns (nullptr: no pair needs them)
+    long long scratch_rows;
+};
+// many alignments with strings in one launch (batch_align_kernel)
+struct AlignArgs {
+    BatchArgs b;
+    const ga_batch_walk_item* witems;  // parallel to b.items
+    const uint32_t* rng;               // the pairs' tie-break entries (ga_rng.h), pair t at witems[t].tab_off
+    uint32_t* ops;                     // the chosen levels, 2 bits per dispatch, pair t at witems[t].ops_off
+    int4* walk_out;                    // [npairs][2] {dispatches, i, j, reason}, {fill ticks, walk ticks, 0, 0} (10 ns
+                                       // ticks of s_memrealtime), indexed by ga_batch_item::out
+    uint32_t* tb;                      // [waves][tb_words] traceback words
+    long long tb_words;
+};
+// qbytes: the sub' table's entry width in LDS; waves: the resident waves the host sized the grid (and the scratch) for,
+// a multiple of gabatch::kWavesPerGroup; CB: bytes of a traceback word (1, 2 or 4)
+void launch_batch_fill(hipStream_t s, const BatchArgs& p, int qbytes, int waves);
+void launch_batch_align(hipStream_t s, const AlignArgs& q, int qbytes, int CB, int waves);
 
 }  // namespace ga

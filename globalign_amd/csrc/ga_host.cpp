@@ -9,7 +9,7 @@
 //     _randbelow_with_getrandbits exactly, starting from random.getstate(),
 //     while the device fill runs;
 //   * string assembly from the walk's per-step levels (take_* :688-753,
-//     the i==0 / j==0 tails :542-581 and the final reverse :584-586).
+//     the i==0 / j==0 tails :542-581 and the final reverse :584-586): ga_strings.h.
 #include <hip/hip_runtime.h>
 #include <unistd.h>
 
@@ -32,6 +32,7 @@
 #include "ga_batch.h"
 #include "ga_batch_align.h"
 #include "ga_rng.h"
+#include "ga_strings.h"
 
 namespace {
 
@@ -50,10 +51,16 @@ int fail(int code, const std::string& msg) {
     } while (0)
 
 // ------------------------------------------------------------------ buffers
+// Device memory that grows on demand and is released with its owner (a context or a pipeline slot): nothing copies
+// one, Band and the launches' argument structs hold pointers into it.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
     bool uncached = false;
+    explicit DevBuf(bool uncached_ = false) : uncached(uncached_) {}
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     hipError_t ensure(size_t bytes) {
         if (bytes <= cap && p) return hipSuccess;
         if (p) (void)hipFree(p);
@@ -71,6 +78,39 @@ struct DevBuf {
     }
     template <typename T>
     T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// Its pinned-host counterpart: plain pinned memory (staging for asynchronous copies), or mapped and coherent, which the
+// device reads and writes in place through dev().  It grows by free-then-allocate at the ensure() call, never later: a
+// free while a persistent kernel polls host memory would wait for that kernel (align_chain).
+struct PinBuf {
+    void* p = nullptr;
+    void* dp = nullptr;  // the same memory as the device sees it (mapped buffers), looked up once per allocation
+    size_t cap = 0;
+    bool mapped = false;
+    explicit PinBuf(bool mapped_ = false) : mapped(mapped_) {}
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    ~PinBuf() {
+        if (p) (void)hipHostFree(p);
+    }
+    hipError_t ensure(size_t bytes) {
+        if (bytes <= cap && p) return hipSuccess;
+        void* old = p;
+        p = dp = nullptr;
+        cap = 0;
+        if (old)
+            if (hipError_t e = hipHostFree(old); e != hipSuccess) return e;
+        const unsigned flags = mapped ? hipHostMallocMapped | hipHostMallocCoherent : hipHostMallocDefault;
+        hipError_t e = hipHostMalloc(&p, bytes, flags);
+        if (e == hipSuccess && mapped) e = hipHostGetDevicePointer(&dp, p, 0);
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    template <typename T>
+    T* host() const { return static_cast<T*>(p); }
+    template <typename T>
+    T* dev() const { return static_cast<T*>(dp); }
 };
 
 using namespace garng;
@@ -131,9 +171,8 @@ struct ga_ctx {
     int64_t gv_total = 0;      // GV(m): the sum of the vertical gap costs of seq_1
     // a streamed single call's small results in pinned, coherent host memory (no copy after the walk): [0, 16) the
     // walk's result words (it writes them there), [16, 20) the fill's H'(m, n) words, [20] its abort word (copied on
-    // the upload stream while the walk runs); res_dev: the same memory as the device sees it
-    int* res_pin = nullptr;
-    int* res_dev = nullptr;
+    // the upload stream while the walk runs)
+    PinBuf res_pin{true};
     hipEvent_t ev_fill = nullptr, ev_res = nullptr;
     bool rc_pos_zeroed = false;  // rc_pos was cleared on the fill's stream before the fill (rc_align)
     int nstripes = 0, nslabs = 0, TC = 0, nwc = 4, qrows = 1024, num_cu = 256;
@@ -149,12 +188,11 @@ struct ga_ctx {
     DevBuf a, b, sub, gh, gv, qp, GVp, GHp, top, left, bnd_row, bnd_col, meta, hand, flags, tb, out_last, full, rng, bscr,
         ckpt,
         ops, result;
-    DevBuf halo_in{nullptr, 0, true};
+    DevBuf halo_in{true};  // uncached
     bool slab = false;
     // slab progress words in pinned, coherent host memory: [0] halo_in rows (written by the host
     // when a band has arrived), [1] halo_out rows (written by the fill's IO wave)
-    uint32_t* prog_host = nullptr;
-    uint32_t* prog_dev = nullptr;
+    PinBuf prog{true};
     int2* halo_in_ext = nullptr;   // caller-bound halo buffers (e.g. tensors RCCL sends from / receives into)
     int2* halo_out_ext = nullptr;
     // caller-bound progress words (device-visible; e.g. on the reading GPU, written over xGMI by the
@@ -169,8 +207,7 @@ struct ga_ctx {
         // each pipelined alignment computes its own boundary (make_dp_array) into its slot
         DevBuf GVp, GHp, top, left, bnd_row, bnd_col, meta, bscr;
         hipEvent_t f0 = nullptr, f1 = nullptr, fdone = nullptr, w0 = nullptr, w1 = nullptr;
-        uint32_t* tab_pin = nullptr;  // pinned staging of the walk's table slice
-        int64_t tab_cap = 0;
+        PinBuf tab_pin;  // pinned staging of the walk's table slice
     } pipe[6];
     hipStream_t wstream = nullptr, fstream[4] = {nullptr, nullptr, nullptr, nullptr};  // [0] unused: ctx->stream
     // CU-masked pipeline streams (GA_PIPE_WALK_CUS > 0): the walk keeps CUs of its own, the fills the rest
@@ -179,24 +216,21 @@ struct ga_ctx {
     // hardware queues, the walk stream keeping the greatest priority (it takes the next free CU)
     hipStream_t nfstream[4] = {nullptr, nullptr, nullptr, nullptr};
     int walk_cus = -1;  // CUs reserved for the walk (0: no masks; -1: not yet set up)
-    int* pipe_pin = nullptr;       // pinned: per slot {out_last[4], GV(m), GH(n), abort, pad}
+    PinBuf pipe_pin;               // pinned: per slot {out_last[4], GV(m), GH(n), abort, pad}
     int pipe_fills = 2, pipe_slots = 3;  // fills in flight (one stream each) and slots (fills + the walked one)
     int hw_queues = 4;                   // GPU_MAX_HW_QUEUES as the process first saw it (ga_ctx_create)
     int pipe_lane_td = 0, pipe_lane_nwc = 0;  // the pipeline's lane-kernel fill geometry (0: the row scan)
     RngTable many_rng;
     // chained pipeline walks (walk_chain_kernel): the tie-break stream in pinned, coherent host memory
     // and the control words {fills done, walks done, abort, timed out, entries written (8 B at [4])}
-    uint32_t* chain_tab = nullptr;
-    int64_t chain_tab_cap = 0;
-    unsigned* chain_ctl = nullptr;
+    PinBuf chain_tab{true}, chain_ctl{true};
     // the chain's stream, at the LEAST priority: HIP gives each priority its own pool of hardware
     // queues, and no other stream of the process uses this pool, so no fill can ever be queued behind
     // the persistent chain on an in-order queue it shares (the chain waits for those fills)
     hipStream_t cwstream = nullptr;
     // per slot, pinned and coherent: the walk's result words and levels, written by the chain straight
     // into host memory (a hipMemcpy would wait for a CU, and the fills hold them all)
-    uint8_t* chain_io = nullptr;
-    size_t chain_io_cap = 0;
+    PinBuf chain_io{true};
     bool walk_rng_ready = false;
     float fill_ms = 0.f, walk_ms = 0.f, rng_ms = 0.f, call_ms = 0.f;
     bool dbg_on = false;
@@ -224,13 +258,10 @@ struct ga_ctx {
     unsigned rc_epoch = 0;
     bool rc_used = false;  // the last fill was the recompute path's (ga_problem_align or a slab's)
     // rc_align's walk levels in pinned host memory and the helper's progress word: decoded while the walk runs
-    uint32_t* rc_ops_pin = nullptr;
-    int64_t rc_ops_cap = 0;  // words
-    unsigned* rc_ops_prog = nullptr;
+    PinBuf rc_ops_pin{true}, rc_ops_prog{true};
     // rc_align's tie-break table: pinned staging, uploaded on a stream of its own while the fill runs, so that the walk
     // is queued behind the fill at once (a pageable copy on the fill's stream held the calling thread to the fill's end)
-    uint32_t* up_pin = nullptr;
-    int64_t up_cap = 0;  // entries
+    PinBuf up_pin;
     hipStream_t ustream = nullptr;
     hipEvent_t ev_up = nullptr;
     int rc_T = 0;          // its fill stripe width (64-column tiles per block)
@@ -355,6 +386,15 @@ bool lane_geometry(ga_ctx* c, int64_t ncol, int* qrows_out, bool tb, int force_T
     return true;
 }
 
+// sub' = sub - gV - gH, K x K: what every fill adds per cell in the shifted domain
+std::vector<int> shifted_sub(const ga_costs* cs) {
+    const int K = cs->K;
+    std::vector<int> subp((size_t)K * K);
+    for (int x = 0; x < K; x++)
+        for (int y = 0; y < K; y++) subp[x * K + y] = cs->sub[x * K + y] - cs->gap_v[x] - cs->gap_h[y];
+    return subp;
+}
+
 int load_problem(ga_ctx* c, const uint8_t* a, int64_t m, const uint8_t* b_all, int64_t n_all, const ga_costs* cs,
                  const int32_t* row0, const int32_t* col0, int64_t cb, int64_t ce) {
     ProblemShape ps;
@@ -399,10 +439,8 @@ int load_problem(ga_ctx* c, const uint8_t* a, int64_t m, const uint8_t* b_all, i
         HIPCHK(hipMemcpyAsync(c->bnd_col.p, col0, sizeof(int) * 3 * (m + 1), hipMemcpyHostToDevice, c->stream));
     }
     {
-        // sub' = sub - gV - gH, read by the fill's IO wave into its LDS query profile
-        std::vector<int> subp((size_t)K * K);
-        for (int x = 0; x < K; x++)
-            for (int y = 0; y < K; y++) subp[x * K + y] = cs->sub[x * K + y] - cs->gap_v[x] - cs->gap_h[y];
+        // sub', read by the fill's IO wave into its LDS query profile
+        const std::vector<int> subp = shifted_sub(cs);
         HIPCHK(c->qp.ensure(sizeof(int) * K * K));
         HIPCHK(hipMemcpy(c->qp.p, subp.data(), sizeof(int) * K * K, hipMemcpyHostToDevice));
         // query-profile ring: as many rows as fit 64 KB (at least 128)
@@ -714,7 +752,7 @@ int enqueue_fill(ga_ctx* c, int32_t flags, const Band& bd = Band()) {
     p.top = (bd.top ? bd.top : btop.as<int2>()) + c->col0;
     if (c->slab && c->col0 > 0) {
         p.left = c->halo_in_ext ? c->halo_in_ext : c->halo_in.as<int2>();
-        p.left_prog = c->in_prog_ext ? c->in_prog_ext : c->prog_dev;  // [0]: halo_in rows
+        p.left_prog = c->in_prog_ext ? c->in_prog_ext : c->prog.dev<uint32_t>();  // [0]: halo_in rows
     } else {
         p.left = bleft.as<int2>() + bd.r0;
         p.left_prog = nullptr;
@@ -724,7 +762,7 @@ int enqueue_fill(ga_ctx* c, int32_t flags, const Band& bd = Band()) {
     p.abort_word = fl + 1;
     p.tb = tb ? tbb.as<uint8_t>() : nullptr;
     p.out_last = ob.as<int>();
-    p.edge_prog = c->slab ? (c->out_prog_ext ? c->out_prog_ext : c->prog_dev + 1) : nullptr;  // [1]: halo_out rows
+    p.edge_prog = c->slab ? (c->out_prog_ext ? c->out_prog_ext : c->prog.dev<uint32_t>() + 1) : nullptr;  // [1]: halo_out rows
     p.edge_out = c->slab ? c->halo_out_ext : nullptr;
     p.full = full ? c->full.as<int>() : nullptr;
     p.m = (int)m;
@@ -897,7 +935,30 @@ int run_walk(ga_ctx* c, const uint32_t* tab, int64_t ntab, const WalkStart& st, 
     return GA_OK;
 }
 
-inline int64_t pywrap(int64_t k, int64_t L) { return k < 0 ? k + L : k; }
+// The walk's result words [4, 15) into the context's diagnostic fields (ga_debug_walk, ga_debug_walk_jump).
+void take_walk_diag(ga_ctx* c, const int* res) {
+    c->walk_waits = res[4];
+    c->walk_tiles = res[5];
+    c->walk_t_tile = res[6];
+    c->walk_t_ring = res[7];
+    c->walk_t_total = res[8];
+    c->walk_c_total = res[9];
+    c->walk_load_ticks = res[10];
+    c->walk_load_count = res[11];
+    for (int q = 0; q < 3; q++) c->walk_jump_diag[q] = res[12 + q];
+}
+
+// The walk state after the dispatches up to D1, whose columns `col` holds (ga_strings.h).
+void advance_walk(WalkStart& st, const gastr::Columns& col, int64_t D1) {
+    if (D1 > st.D) {
+        st.h += (D1 - st.D) - (st.first ? 1 : 0);
+        st.first = 0;
+    }
+    st.i = col.i;
+    st.j = col.j;
+    st.L = col.L;
+    st.D = D1;
+}
 
 // Wait for the walk; decode the levels of dispatches [st.D, D_end) into alignment columns in walk
 // order starting at (st.i, st.j) (global columns).  Returns the end state through `st` and `reason`.
@@ -921,19 +982,11 @@ int walk_segment(ga_ctx* c, WalkStart& st, int& reason, const char* a_chr, const
 int decode_segment(ga_ctx* c, const int* res, WalkStart& st, int& reason, const char* a_chr, const char* b_chr,
                    char* oa, char* om, char* ob, int64_t cap, int64_t& len, const WalkBufs& wb, bool synced,
                    const uint32_t* host_ops) {
-    c->walk_waits = res[4];
-    c->walk_tiles = res[5];
-    c->walk_t_tile = res[6];
-    c->walk_t_ring = res[7];
-    c->walk_t_total = res[8];
-    c->walk_c_total = res[9];
-    c->walk_load_ticks = res[10];
-    c->walk_load_count = res[11];
-    for (int q = 0; q < 3; q++) c->walk_jump_diag[q] = res[12 + q];
+    take_walk_diag(c, res);
     if (!synced) HIPCHK(hipEventElapsedTime(&c->walk_ms, wb.ev0, wb.ev1));
     const int64_t D0 = st.D, D1 = res[0];
     reason = res[3];
-    // levels are packed 2 bits per dispatch, dispatch k at bits 30 - 2*(k & 15) of u32 word k >> 4
+    // the level words that hold dispatches [D0, D1): 16 dispatches to a u32
     const int64_t w0 = D0 >> 4, w1 = (D1 + 15) >> 4;
     std::vector<uint32_t> ops((size_t)std::max<int64_t>(w1 - w0, 0));
     if (host_ops) {  // the levels in pinned host memory (the walk chain writes them there)
@@ -946,32 +999,10 @@ int decode_segment(ga_ctx* c, const int* res, WalkStart& st, int& reason, const 
                                   wb.stream));
         HIPCHK(hipStreamSynchronize(wb.stream));
     }
-    const int64_t m = c->m, n = c->n_global;
-    int64_t i = st.i, j = st.j;
-    int L = st.L;
-    len = 0;
-    auto put = [&](char x, char y, char z) {
-        if (len < cap) { oa[len] = x; om[len] = y; ob[len] = z; }
-        len++;
-    };
-    if (reason != 4) {
-        for (int64_t k = D0; k < D1; k++) {
-            const char ca = a_chr[pywrap(i - 1, m)], cbb = b_chr[pywrap(j - 1, n)];
-            const unsigned lv = (ops[(k >> 4) - w0] >> (30 - 2 * (k & 15))) & 3u;
-            if (lv == 0) { put(ca, ca == cbb ? '|' : '*', cbb); i--; j--; }
-            else if (lv == 1) { put('-', ' ', cbb); j--; }
-            else { put(ca, ' ', '-'); i--; }
-            L = (int)lv;
-        }
-    }
-    if (D1 > D0) {
-        st.h += (D1 - D0) - (st.first ? 1 : 0);
-        st.first = 0;
-    }
-    st.i = i;
-    st.j = j;
-    st.L = L;
-    st.D = D1;
+    gastr::Columns col{a_chr, c->m, b_chr, c->n_global, oa, om, ob, cap, st.i, st.j, st.L};
+    if (reason != 4) col.decode<false>(ops.data(), w0, D0, D1);  // (4: the reference's IndexError, no columns)
+    advance_walk(st, col, D1);
+    len = col.len;
     if (len > cap) return fail(GA_E_ARG, "output capacity too small");
     return GA_OK;
 }
@@ -1000,18 +1031,8 @@ int conclude_walk(const RngTable& snaps, const WalkStart& st, int reason, uint32
         *out_len = 0;
         return GA_OK;
     }
-    auto put = [&](char x, char y, char z) {
-        if (len < cap) { oa[len] = x; om[len] = y; ob[len] = z; }
-        len++;
-    };
-    if (reason == 1)
-        for (int64_t jj = st.j; jj > 0; jj--) put('-', ' ', b_chr[jj - 1]);
-    else if (reason == 2)
-        for (int64_t ii = st.i; ii > 0; ii--) put(a_chr[ii - 1], ' ', '-');
+    len = gastr::finish_strings(reason, st.i, st.j, a_chr, b_chr, oa, om, ob, cap, len);
     if (len > cap) return fail(GA_E_ARG, "output capacity too small");
-    std::reverse(oa, oa + len);
-    std::reverse(om, om + len);
-    std::reverse(ob, ob + len);
     *out_len = len;
     *tb_status = GA_TB_OK;
     return GA_OK;
@@ -1309,40 +1330,16 @@ bool rc_slab_eligible(ga_ctx* c) {
 int pinned_walk_levels(ga_ctx* c, WalkBufs& wb) {
     const int64_t m = c->m, n = c->n;
     const int64_t nwords = (m + n + 1 + 15) / 16 + 64;
-    if (c->rc_ops_cap < nwords) {
-        if (c->rc_ops_pin) HIPCHK(hipHostFree(c->rc_ops_pin));
-        c->rc_ops_pin = nullptr;
-        c->rc_ops_cap = 0;
-        void* hp = nullptr;
-        HIPCHK(hipHostMalloc(&hp, sizeof(uint32_t) * nwords, hipHostMallocMapped | hipHostMallocCoherent));
-        c->rc_ops_pin = static_cast<uint32_t*>(hp);
-        c->rc_ops_cap = nwords;
-    }
-    if (!c->rc_ops_prog) {
-        void* hp = nullptr;
-        HIPCHK(hipHostMalloc(&hp, 256, hipHostMallocMapped | hipHostMallocCoherent));
-        c->rc_ops_prog = static_cast<unsigned*>(hp);
-    }
-    __atomic_store_n(c->rc_ops_prog, 0u, __ATOMIC_SEQ_CST);
-    {
-        void* dp = nullptr;
-        HIPCHK(hipHostGetDevicePointer(&dp, c->rc_ops_pin, 0));
-        wb.ops = static_cast<uint32_t*>(dp);
-        HIPCHK(hipHostGetDevicePointer(&dp, c->rc_ops_prog, 0));
-        wb.ops_prog = static_cast<unsigned*>(dp);
-    }
+    HIPCHK(c->rc_ops_pin.ensure(sizeof(uint32_t) * nwords));
+    HIPCHK(c->rc_ops_prog.ensure(256));
+    __atomic_store_n(c->rc_ops_prog.host<unsigned>(), 0u, __ATOMIC_SEQ_CST);
+    wb.ops = c->rc_ops_pin.dev<uint32_t>();
+    wb.ops_prog = c->rc_ops_prog.dev<unsigned>();
     // the walk's result words to pinned memory too: no hipMemcpy after the walk (round 6: the call's tail after the
     // walk held five small copies, ~0.1 ms)
-    if (!c->res_pin) {
-        void* hp = nullptr;
-        HIPCHK(hipHostMalloc(&hp, 64 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
-        c->res_pin = static_cast<int*>(hp);
-        void* dp = nullptr;
-        HIPCHK(hipHostGetDevicePointer(&dp, hp, 0));
-        c->res_dev = static_cast<int*>(dp);
-    }
-    std::memset(c->res_pin, 0, 64 * sizeof(int));
-    wb.result = c->res_dev;
+    HIPCHK(c->res_pin.ensure(64 * sizeof(int)));
+    std::memset(c->res_pin.p, 0, 64 * sizeof(int));
+    wb.result = c->res_pin.dev<int>();
     return GA_OK;
 }
 
@@ -1355,9 +1352,9 @@ int fill_results_async(ga_ctx* c) {
     if (!c->ev_res) HIPCHK(hipEventCreateWithFlags(&c->ev_res, hipEventDisableTiming));
     HIPCHK(hipEventRecord(c->ev_fill, c->stream));
     HIPCHK(hipStreamWaitEvent(c->ustream, c->ev_fill, 0));
-    HIPCHK(hipMemcpyAsync(c->res_pin + 16, c->out_last.p, sizeof(int) * 4, hipMemcpyDeviceToHost, c->ustream));
-    HIPCHK(hipMemcpyAsync(c->res_pin + 20, c->flags.as<unsigned>() + 1, sizeof(unsigned), hipMemcpyDeviceToHost,
-                          c->ustream));
+    int* res = c->res_pin.host<int>();
+    HIPCHK(hipMemcpyAsync(res + 16, c->out_last.p, sizeof(int) * 4, hipMemcpyDeviceToHost, c->ustream));
+    HIPCHK(hipMemcpyAsync(res + 20, c->flags.as<unsigned>() + 1, sizeof(unsigned), hipMemcpyDeviceToHost, c->ustream));
     HIPCHK(hipEventRecord(c->ev_res, c->ustream));
     return GA_OK;
 }
@@ -1365,9 +1362,10 @@ int fill_results_async(ga_ctx* c) {
 int fill_results_finish(ga_ctx* c, int64_t* cost_out) {
     HIPCHK(hipEventSynchronize(c->ev_res));
     HIPCHK(hipEventElapsedTime(&c->fill_ms, c->ev[0], c->ev[1]));
-    if (c->res_pin[20]) return fail(GA_E_TIMEOUT, "fill kernel hand-off wait timed out");
+    const int* res = c->res_pin.host<int>();
+    if (res[20]) return fail(GA_E_TIMEOUT, "fill kernel hand-off wait timed out");
     c->GV_m = (int)c->gv_total;
-    if (cost_out) *cost_out = (int64_t)c->res_pin[16] + c->gv_total + c->gh_total;
+    if (cost_out) *cost_out = (int64_t)res[16] + c->gv_total + c->gh_total;
     return GA_OK;
 }
 
@@ -1384,23 +1382,13 @@ int streamed_walk_finish(ga_ctx* c, const RngTable& R, const WalkBufs& wb, const
     int64_t len = 0;
     {
         // decode dispatches [D, D1) of the levels (dp_array_backward's column output, in walk order)
-        const uint32_t* ops = c->rc_ops_pin;
-        int64_t i = st.i, j = st.j, D = st.D;
-        int L = st.L;
+        const uint32_t* ops = c->rc_ops_pin.host<uint32_t>();
+        const unsigned* prog = c->rc_ops_prog.host<unsigned>();
+        gastr::Columns col{a_chr, m, b_chr, n, oa, om, ob, cap, st.i, st.j, st.L};
+        int64_t D = st.D;
         auto decode_to = [&](int64_t D1) {
-            for (; D < D1; D++) {
-                const char ca = a_chr[pywrap(i - 1, m)], cbb = b_chr[pywrap(j - 1, n)];
-                const unsigned lv = (ops[D >> 4] >> (30 - 2 * (D & 15))) & 3u;
-                const int64_t k = len++;
-                if (k < cap) {
-                    if (lv == 0) { oa[k] = ca; om[k] = ca == cbb ? '|' : '*'; ob[k] = cbb; }
-                    else if (lv == 1) { oa[k] = '-'; om[k] = ' '; ob[k] = cbb; }
-                    else { oa[k] = ca; om[k] = ' '; ob[k] = '-'; }
-                }
-                i -= lv != 1;
-                j -= lv != 2;
-                L = (int)lv;
-            }
+            col.decode<false>(ops, 0, D, D1);
+            D = std::max(D, D1);
         };
         const int64_t lag = [c] {
             const char* e = c->knob("GA_RC_DECODE_LAG");  // (diagnostics) blocks of 512 dispatches held back
@@ -1410,7 +1398,7 @@ int streamed_walk_finish(ga_ctx* c, const RngTable& R, const WalkBufs& wb, const
         const bool check = c->knob("GA_RC_DECODE_CHECK") != nullptr;
         if (check) seen.assign((size_t)nwords, 0u);
         for (;;) {
-            const unsigned pr = __atomic_load_n(c->rc_ops_prog, __ATOMIC_ACQUIRE);
+            const unsigned pr = __atomic_load_n(prog, __ATOMIC_ACQUIRE);
             if ((int64_t)pr - lag > D) {
                 if (check)
                     for (int64_t q = D >> 4; q < (((int64_t)pr - lag + 15) >> 4); q++) seen[q] = ops[q];
@@ -1426,17 +1414,9 @@ int streamed_walk_finish(ga_ctx* c, const RngTable& R, const WalkBufs& wb, const
         // (written to pinned memory by the walk): no copy here
         if (int rr = fill_results_finish(c, cost_out)) return rr;
         int res[16];
-        std::memcpy(res, c->res_pin, sizeof(res));
+        std::memcpy(res, c->res_pin.p, sizeof(res));
         HIPCHK(hipEventElapsedTime(&c->walk_ms, wb.ev0, wb.ev1));
-        c->walk_waits = res[4];
-        c->walk_tiles = res[5];
-        c->walk_t_tile = res[6];
-        c->walk_t_ring = res[7];
-        c->walk_t_total = res[8];
-        c->walk_c_total = res[9];
-        c->walk_load_ticks = res[10];
-        c->walk_load_count = res[11];
-        for (int q = 0; q < 3; q++) c->walk_jump_diag[q] = res[12 + q];
+        take_walk_diag(c, res);
         reason = res[3];
         if (reason == 7) return fail(GA_E_TIMEOUT, "recompute walk: a tile was never recomputed");
         const int64_t D1 = res[0];
@@ -1455,18 +1435,12 @@ int streamed_walk_finish(ga_ctx* c, const RngTable& R, const WalkBufs& wb, const
         }
         decode_to(D1);
         if (reason == 4) {  // (never here: such walks are degenerate, reason 7) the reference's IndexError
-            len = 0;
-            i = st.i;
-            j = st.j;
+            col.len = 0;
+            col.i = st.i;
+            col.j = st.j;
         }
-        if (D1 > st.D) {
-            st.h += (D1 - st.D) - (st.first ? 1 : 0);
-            st.first = 0;
-        }
-        st.i = i;
-        st.j = j;
-        st.L = L;
-        st.D = D1;
+        advance_walk(st, col, D1);
+        len = col.len;
         if (len > cap) return fail(GA_E_ARG, "output capacity too small");
     }
     const int rc = conclude_walk(R, st, reason, mt_state, a_chr, b_chr, oa, om, ob, cap, len, out_len, tb_status);
@@ -1495,20 +1469,12 @@ int rc_align(ga_ctx* c, uint32_t* mt_state, const char* a_chr, const char* b_chr
     const int64_t ntab = (int64_t)R.tab.size();
     // the table goes up on a stream of its own while the fill still runs (pinned staging: the copy is asynchronous),
     // and the walk's stream waits for it: the walk launch below is then queued behind the fill at once
-    if (c->up_cap < ntab) {
-        if (c->up_pin) HIPCHK(hipHostFree(c->up_pin));
-        c->up_pin = nullptr;
-        c->up_cap = 0;
-        void* hp = nullptr;
-        HIPCHK(hipHostMalloc(&hp, sizeof(uint32_t) * ntab, hipHostMallocDefault));
-        c->up_pin = static_cast<uint32_t*>(hp);
-        c->up_cap = ntab;
-    }
+    HIPCHK(c->up_pin.ensure(sizeof(uint32_t) * ntab));
     if (!c->ustream) HIPCHK(hipStreamCreateWithPriority(&c->ustream, hipStreamNonBlocking, c->priority));
     if (!c->ev_up) HIPCHK(hipEventCreateWithFlags(&c->ev_up, hipEventDisableTiming));
     // (the last call's copy out of the staging buffer has ended: its walk waited for it, and the call for its walk)
-    std::memcpy(c->up_pin, R.tab.data(), sizeof(uint32_t) * ntab);
-    HIPCHK(hipMemcpyAsync(wb.rng, c->up_pin, sizeof(uint32_t) * ntab, hipMemcpyHostToDevice, c->ustream));
+    std::memcpy(c->up_pin.p, R.tab.data(), sizeof(uint32_t) * ntab);
+    HIPCHK(hipMemcpyAsync(wb.rng, c->up_pin.p, sizeof(uint32_t) * ntab, hipMemcpyHostToDevice, c->ustream));
     HIPCHK(hipEventRecord(c->ev_up, c->ustream));
     HIPCHK(hipStreamWaitEvent(wb.stream, c->ev_up, 0));
     // the walk's levels go to pinned host memory, and this thread decodes them while the walk runs
@@ -1550,24 +1516,14 @@ int pipe_setup(ga_ctx* c) {
             for (int f = 0; f < 4; f++) HIPCHK(hipExtStreamCreateWithCUMask(&c->mfstream[f], (uint32_t)words, fm.data()));
         }
     }
-    if (!c->pipe_pin) {
-        void* hp = nullptr;
-        HIPCHK(hipHostMalloc(&hp, sizeof(int) * 8 * 6, hipHostMallocDefault));
-        c->pipe_pin = static_cast<int*>(hp);
-    }
+    HIPCHK(c->pipe_pin.ensure(sizeof(int) * 8 * 6));
     const int64_t per = c->m + c->n + 1;
     for (int s = 0; s < c->pipe_slots; s++) {
         auto& sl = c->pipe[s];
         for (hipEvent_t* e : {&sl.f0, &sl.f1, &sl.w0, &sl.w1})
             if (!*e) HIPCHK(hipEventCreate(e));
         if (!sl.fdone) HIPCHK(hipEventCreateWithFlags(&sl.fdone, hipEventDisableTiming));
-        if (sl.tab_cap < per) {
-            if (sl.tab_pin) HIPCHK(hipHostFree(sl.tab_pin));
-            void* hp = nullptr;
-            HIPCHK(hipHostMalloc(&hp, sizeof(uint32_t) * per, hipHostMallocDefault));
-            sl.tab_pin = static_cast<uint32_t*>(hp);
-            sl.tab_cap = per;
-        }
+        HIPCHK(sl.tab_pin.ensure(sizeof(uint32_t) * per));
         HIPCHK(sl.rng.ensure(sizeof(uint32_t) * (per + 64)));  // + the walk's entry look-ahead (SLD)
         HIPCHK(sl.ops.ensure(c->m + c->n + 1024));
         HIPCHK(sl.result.ensure(sizeof(int) * 16));
@@ -1613,7 +1569,7 @@ int pipe_fill(ga_ctx* c, int slot, hipStream_t st, bool row = false) {
     bd.lane_td = row ? 0 : c->pipe_lane_td;
     bd.lane_nwc = row ? 0 : c->pipe_lane_nwc;
     if (int r = enqueue_fill(c, GA_FILL_TRACEBACK, bd)) return r;
-    int* pin = c->pipe_pin + 8 * slot;
+    int* pin = c->pipe_pin.host<int>() + 8 * slot;
     HIPCHK(hipMemcpyAsync(pin, sl.out_last.p, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(pin + 4, sl.meta.p, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(pin + 5, sl.GHp.as<int>() + c->col0 + c->n, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1627,19 +1583,9 @@ int pipe_fill(ga_ctx* c, int slot, hipStream_t st, bool row = false) {
 // the fills hold them all).  Returns the slot stride and the area's device address.
 int pipe_io(ga_ctx* c, int S, size_t* stride, uint8_t** dev) {
     const size_t ops_bytes = (((size_t)(c->m + c->n + 1024) + 255) / 256) * 256, io_stride = 256 + ops_bytes;
-    if (c->chain_io_cap < io_stride * S) {
-        if (c->chain_io) HIPCHK(hipHostFree(c->chain_io));
-        c->chain_io = nullptr;
-        c->chain_io_cap = 0;
-        void* hp = nullptr;
-        HIPCHK(hipHostMalloc(&hp, io_stride * S, hipHostMallocMapped | hipHostMallocCoherent));
-        c->chain_io = static_cast<uint8_t*>(hp);
-        c->chain_io_cap = io_stride * S;
-    }
-    void* d = nullptr;
-    HIPCHK(hipHostGetDevicePointer(&d, c->chain_io, 0));
+    HIPCHK(c->chain_io.ensure(io_stride * S));
     *stride = io_stride;
-    *dev = static_cast<uint8_t*>(d);
+    *dev = c->chain_io.dev<uint8_t>();
     return GA_OK;
 }
 
@@ -1663,31 +1609,20 @@ int align_chain(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, con
     }
     hipStream_t ws = c->cwstream;
     const int64_t need = (int64_t)count * per;
-    if (c->chain_tab_cap < need) {
-        if (c->chain_tab) HIPCHK(hipHostFree(c->chain_tab));
-        c->chain_tab = nullptr;
-        c->chain_tab_cap = 0;
-        void* hp = nullptr;
-        HIPCHK(hipHostMalloc(&hp, sizeof(uint32_t) * need, hipHostMallocMapped | hipHostMallocCoherent));
-        c->chain_tab = static_cast<uint32_t*>(hp);
-        c->chain_tab_cap = need;
-    }
-    if (!c->chain_ctl) {
-        void* hp = nullptr;
-        HIPCHK(hipHostMalloc(&hp, 64, hipHostMallocMapped | hipHostMallocCoherent));
-        c->chain_ctl = static_cast<unsigned*>(hp);
-    }
+    HIPCHK(c->chain_tab.ensure(sizeof(uint32_t) * need));
+    HIPCHK(c->chain_ctl.ensure(64));
     size_t io_stride = 0;
     uint8_t* io_dev = nullptr;
     if (int r = pipe_io(c, S, &io_stride, &io_dev)) return r;
-    auto res_host = [&](int s) { return reinterpret_cast<int*>(c->chain_io + io_stride * s); };
-    auto ops_host = [&](int s) { return reinterpret_cast<uint32_t*>(c->chain_io + io_stride * s + 256); };
-    unsigned* ctl = c->chain_ctl;
+    uint8_t* const io_host = c->chain_io.host<uint8_t>();
+    auto res_host = [&](int s) { return reinterpret_cast<int*>(io_host + io_stride * s); };
+    auto ops_host = [&](int s) { return reinterpret_cast<uint32_t*>(io_host + io_stride * s + 256); };
+    uint32_t* const chain_tab = c->chain_tab.host<uint32_t>();
+    unsigned* ctl = c->chain_ctl.host<unsigned>();
     long long* tab_ready = reinterpret_cast<long long*>(ctl + 4);
     std::memset(ctl, 0, 64);
-    void *tab_dev = nullptr, *ctl_dev = nullptr;
-    HIPCHK(hipHostGetDevicePointer(&tab_dev, c->chain_tab, 0));
-    HIPCHK(hipHostGetDevicePointer(&ctl_dev, ctl, 0));
+    const uint32_t* tab_dev = c->chain_tab.dev<uint32_t>();
+    unsigned* ctl_dev = c->chain_ctl.dev<unsigned>();
 
     // the tie-break stream: a host thread extends it ahead of the walks, into pinned memory; started
     // before the fills are enqueued (C2 / C5: the first walk waited 2.1 / 4.0 ms for its entries)
@@ -1724,7 +1659,7 @@ int align_chain(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, con
             for (int64_t to = from; to < want;) {
                 const int64_t nx = std::min(want, to + std::max<int64_t>(per / 2, 4096));
                 R.extend(nx);
-                std::memcpy(c->chain_tab + to, R.tab.data() + to, sizeof(uint32_t) * (nx - to));
+                std::memcpy(chain_tab + to, R.tab.data() + to, sizeof(uint32_t) * (nx - to));
                 __atomic_store_n(tab_ready, (long long)nx, __ATOMIC_RELEASE);
                 to = nx;
             }
@@ -1776,9 +1711,9 @@ int align_chain(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, con
             A.w[s].result = reinterpret_cast<int*>(static_cast<uint8_t*>(io_dev) + io_stride * s);
             A.w[s].ops = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(io_dev) + io_stride * s + 256);
         }
-        A.tab = static_cast<const uint32_t*>(tab_dev);
-        A.ctl = static_cast<unsigned*>(ctl_dev);
-        A.tab_ready = reinterpret_cast<const long long*>(static_cast<unsigned*>(ctl_dev) + 4);
+        A.tab = tab_dev;
+        A.ctl = ctl_dev;
+        A.tab_ready = reinterpret_cast<const long long*>(ctl_dev + 4);
         A.per = per;
         A.wait_limit = 100ull * 1000 * 1000 * 60;  // 60 s of s_memrealtime (100 MHz)
         A.count = count;
@@ -1823,7 +1758,7 @@ int align_chain(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, con
             target = std::max(target, G + Dk + 2 * per + per / 8);
         }
         cv.notify_all();
-        const int* pin = c->pipe_pin + 8 * (k % S);
+        const int* pin = c->pipe_pin.host<int>() + 8 * (k % S);
         if (pin[6]) {
             rc = fail(GA_E_TIMEOUT, "fill kernel hand-off wait timed out");
             break;
@@ -2053,9 +1988,9 @@ int align_many(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, cons
             cv.wait(lk, [&] { return ready >= G + per; });
         }
         HIPCHK(hipStreamWaitEvent(ws, sl.fdone, 0));
-        std::memcpy(sl.tab_pin, tabp + G, sizeof(uint32_t) * per);
+        std::memcpy(sl.tab_pin.p, tabp + G, sizeof(uint32_t) * per);
         const WalkBufs wb = walk_bufs(walk_slot[k]);
-        return run_walk(c, sl.tab_pin, per, WalkStart{m, n, 0, 0, 0, 1}, 0, -1, false, true, &wb);
+        return run_walk(c, sl.tab_pin.host<uint32_t>(), per, WalkStart{m, n, 0, 0, 0, 1}, 0, -1, false, true, &wb);
     };
     int rc = start_walk(0, 0);
     walk_launch_host = now_ms() - h0;
@@ -2065,8 +2000,9 @@ int align_many(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, cons
     for (int k = 0; k < count && rc == GA_OK; k++) {
         auto& sl = c->pipe[walk_slot[k]];
         const WalkBufs wb = walk_bufs(walk_slot[k]);
-        const int* res_pin = reinterpret_cast<const int*>(c->chain_io + io_stride * walk_slot[k]);
-        const uint32_t* ops_pin = reinterpret_cast<const uint32_t*>(c->chain_io + io_stride * walk_slot[k] + 256);
+        const uint8_t* io_pin = c->chain_io.host<uint8_t>() + io_stride * walk_slot[k];
+        const int* res_pin = reinterpret_cast<const int*>(io_pin);
+        const uint32_t* ops_pin = reinterpret_cast<const uint32_t*>(io_pin + 256);
         auto step = [&]() -> int {
             // walk k done: its dispatch count fixes where walk k+1's table slice starts
             HIPCHK(hipEventSynchronize(sl.w1));
@@ -2098,7 +2034,7 @@ int align_many(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, cons
             }
             // alignment k's cost (fill k finished before walk k started) and walk time, before slot k's
             // pinned words and events are reused
-            const int* pin = c->pipe_pin + 8 * walk_slot[k];
+            const int* pin = c->pipe_pin.host<int>() + 8 * walk_slot[k];
             if (pin[6]) return fail(GA_E_TIMEOUT, "fill kernel hand-off wait timed out");
             cost_out[k] = (int64_t)pin[0] + pin[4] + pin[5];
             float f = 0.f;
@@ -2146,6 +2082,64 @@ int align_many(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, cons
     c->rng_ms = (float)(rng_ms / count);
     c->call_ms = (float)(now_ms() - t0);
     c->filled_tb = false;  // ctx->tb does not hold the last fill's words
+    return GA_OK;
+}
+
+// ---------------------------------------------------------------- batches
+// resident waves of a batch launch: two per SIMD on every CU
+int64_t batch_max_waves(const ga_ctx* c) { return (int64_t)c->num_cu * 4 * 2; }
+
+// What ga_batch_costs_ex and ga_batch_align stage alike for the planner's work list, on the context's stream: the
+// launch's waves, and the codes, work list, sub' / gap tables, zeroed ticket, cost and edge-scratch buffers behind
+// `args`.  subp is the upload's source: it lives until the caller has synchronised the stream.
+struct BatchStage {
+    std::vector<int> subp;
+    ga::BatchArgs args{};
+    int waves = 0;
+};
+int stage_batch(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, int64_t npairs, const ga_costs* cs,
+                const std::vector<ga_batch_item>& items, int64_t scratch_rows, BatchStage& bs) {
+    const int K = cs->K, nitems = (int)items.size();
+    // never more waves than pairs; whole workgroups
+    const int W = gabatch::kWavesPerGroup;
+    const int waves = bs.waves = (int)((std::min<int64_t>(batch_max_waves(c), nitems) + W - 1) / W * W);
+    bs.subp = shifted_sub(cs);
+    const size_t ncodes = (size_t)seq_off[nseq];
+    HIPCHK(c->bt_codes.ensure(ncodes));
+    HIPCHK(c->bt_items.ensure(sizeof(ga_batch_item) * nitems));
+    HIPCHK(c->bt_sub.ensure(sizeof(int) * K * K));
+    HIPCHK(c->bt_gh.ensure(sizeof(int) * K));
+    HIPCHK(c->bt_gv.ensure(sizeof(int) * K));
+    HIPCHK(c->bt_ticket.ensure(sizeof(unsigned)));
+    HIPCHK(c->bt_out.ensure(sizeof(long long) * npairs));
+    if (scratch_rows > 0) HIPCHK(c->bt_scratch.ensure(sizeof(int2) * 2 * scratch_rows * waves));
+    HIPCHK(hipMemcpyAsync(c->bt_codes.p, codes, ncodes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->bt_items.p, items.data(), sizeof(ga_batch_item) * nitems, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->bt_sub.p, bs.subp.data(), sizeof(int) * K * K, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->bt_gh.p, cs->gap_h, sizeof(int) * K, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->bt_gv.p, cs->gap_v, sizeof(int) * K, hipMemcpyHostToDevice, c->stream));
+    // the ticket starts at zero for every launch (no last-arriver reset to rely on)
+    HIPCHK(hipMemsetAsync(c->bt_ticket.p, 0, sizeof(unsigned), c->stream));
+    bs.args = ga::BatchArgs{c->bt_codes.as<uint8_t>(), c->bt_items.as<ga_batch_item>(), nitems, c->bt_sub.as<int>(),
+                            c->bt_gh.as<int>(), c->bt_gv.as<int>(), K, cs->gap_open, c->bt_ticket.as<unsigned>(),
+                            c->bt_out.as<long long>(), scratch_rows > 0 ? c->bt_scratch.as<int2>() : nullptr,
+                            scratch_rows};
+    return GA_OK;
+}
+
+// Pair k of a batch through the single-pair path: loaded into the context's problem slot under the pair's own
+// max_cost (its sentinel), then run(sa, sb) on its two sequences' indices.  No problem is loaded afterwards.
+template <typename Run>
+int batch_single_pair(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, const int32_t* pair_a,
+                      const int32_t* pair_b, const int32_t* pair_max_cost, const ga_costs* cs, int64_t k, Run run) {
+    const int64_t sa = pair_a[k], sb = pair_b[k];
+    const int64_t m = seq_off[sa + 1] - seq_off[sa], n = seq_off[sb + 1] - seq_off[sb];
+    ga_costs own = *cs;
+    if (pair_max_cost) own.max_cost = pair_max_cost[k];
+    int r = load_problem(c, codes + seq_off[sa], m, codes + seq_off[sb], n, &own, nullptr, nullptr, 0, n);
+    if (!r) r = run(sa, sb);
+    c->loaded = false;
+    if (r) return fail(r, "pair " + std::to_string(k) + ": " + g_err);
     return GA_OK;
 }
 
@@ -2265,35 +2259,14 @@ void ga_ctx_destroy(ga_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    for (DevBuf* b : {&c->a, &c->b, &c->sub, &c->gh, &c->gv, &c->qp, &c->GVp, &c->GHp, &c->top, &c->left, &c->bnd_row,
-                      &c->bnd_col, &c->meta, &c->hand, &c->flags, &c->tb, &c->out_last, &c->full, &c->rng, &c->ops,
-                      &c->result, &c->halo_in, &c->dbg, &c->wdbg, &c->bscr, &c->ckpt, &c->colck, &c->stck,
-                      &c->rc_tb, &c->rc_flags, &c->rc_pos, &c->rc_own, &c->link, &c->qprof, &c->bt_codes, &c->bt_items,
-                      &c->bt_sub, &c->bt_gh, &c->bt_gv, &c->bt_ticket, &c->bt_out, &c->bt_scratch, &c->bt_witems, &c->bt_rng,
-                      &c->bt_ops, &c->bt_walk, &c->bt_tb})
-        b->release();
-    if (c->prog_host) (void)hipHostFree(c->prog_host);
     if (c->peer_link) (void)hipIpcCloseMemHandle(c->peer_link);
-    if (c->rc_ops_pin) (void)hipHostFree(c->rc_ops_pin);
-    if (c->rc_ops_prog) (void)hipHostFree(c->rc_ops_prog);
-    if (c->up_pin) (void)hipHostFree(c->up_pin);
     if (c->ev_up) (void)hipEventDestroy(c->ev_up);
-    if (c->res_pin) (void)hipHostFree(c->res_pin);
     if (c->ev_fill) (void)hipEventDestroy(c->ev_fill);
     if (c->ev_res) (void)hipEventDestroy(c->ev_res);
     if (c->ustream) (void)hipStreamDestroy(c->ustream);
-    for (auto& sl : c->pipe) {
-        for (DevBuf* b : {&sl.tb, &sl.hand, &sl.flags, &sl.out_last, &sl.rng, &sl.ops, &sl.result, &sl.GVp, &sl.GHp,
-                          &sl.top, &sl.left, &sl.bnd_row, &sl.bnd_col, &sl.meta, &sl.bscr})
-            b->release();
+    for (auto& sl : c->pipe)
         for (hipEvent_t e : {sl.f0, sl.f1, sl.fdone, sl.w0, sl.w1})
             if (e) (void)hipEventDestroy(e);
-        if (sl.tab_pin) (void)hipHostFree(sl.tab_pin);
-    }
-    if (c->pipe_pin) (void)hipHostFree(c->pipe_pin);
-    if (c->chain_tab) (void)hipHostFree(c->chain_tab);
-    if (c->chain_ctl) (void)hipHostFree(c->chain_ctl);
-    if (c->chain_io) (void)hipHostFree(c->chain_io);
     if (c->wstream) (void)hipStreamDestroy(c->wstream);
     if (c->cwstream) (void)hipStreamDestroy(c->cwstream);
     if (c->mwstream) (void)hipStreamDestroy(c->mwstream);
@@ -2307,7 +2280,7 @@ void ga_ctx_destroy(ga_ctx* c) {
         if (e) (void)hipEventDestroy(e);
     if (c->ev_dep) (void)hipEventDestroy(c->ev_dep);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // the device and pinned buffers free themselves (DevBuf, PinBuf)
 }
 
 int ga_problem_set(ga_ctx* c, const uint8_t* a, int64_t m, const uint8_t* b, int64_t n, const ga_costs* cs,
@@ -2337,46 +2310,19 @@ int ga_batch_costs_ex(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, i
     if (int r = check_ctx(c)) return r;
     if (npairs == 0) return GA_OK;  // an empty batch: no launch
     if (!cost_out) return fail(GA_E_ARG, "null argument");
-    // resident waves: two per SIMD on every CU, and the planner's routing limits
-    const int64_t max_waves = (int64_t)c->num_cu * 4 * 2;
+    // the planner's routing limits
     gabatch::Limits lim;
     if (const char* e = c->knob("GA_BATCH_MAX_CELLS")) lim.max_cells = std::max<int64_t>(0, atoll(e));
-    lim.scratch_rows_cap = gabatch::scratch_rows_cap(max_waves);
+    lim.scratch_rows_cap = gabatch::scratch_rows_cap(batch_max_waves(c));
     gabatch::Plan plan;
     std::string why;
     if (int r = gabatch::plan_batch(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim, plan, why))
         return fail(r, why);
-    const int K = cs->K;
     if (!plan.kernel.empty()) {
-        const int nitems = (int)plan.kernel.size();
-        // never more waves than pairs; whole workgroups
-        const int W = gabatch::kWavesPerGroup;
-        const int waves = (int)((std::min<int64_t>(max_waves, nitems) + W - 1) / W * W);
-        std::vector<int> subp((size_t)K * K);
-        for (int x = 0; x < K; x++)
-            for (int y = 0; y < K; y++) subp[x * K + y] = cs->sub[x * K + y] - cs->gap_v[x] - cs->gap_h[y];
-        const size_t ncodes = (size_t)seq_off[nseq];
-        HIPCHK(c->bt_codes.ensure(ncodes));
-        HIPCHK(c->bt_items.ensure(sizeof(ga_batch_item) * nitems));
-        HIPCHK(c->bt_sub.ensure(sizeof(int) * K * K));
-        HIPCHK(c->bt_gh.ensure(sizeof(int) * K));
-        HIPCHK(c->bt_gv.ensure(sizeof(int) * K));
-        HIPCHK(c->bt_ticket.ensure(sizeof(unsigned)));
-        HIPCHK(c->bt_out.ensure(sizeof(long long) * npairs));
-        if (plan.scratch_rows > 0) HIPCHK(c->bt_scratch.ensure(sizeof(int2) * 2 * plan.scratch_rows * waves));
-        HIPCHK(hipMemcpyAsync(c->bt_codes.p, codes, ncodes, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->bt_items.p, plan.kernel.data(), sizeof(ga_batch_item) * nitems, hipMemcpyHostToDevice,
-                              c->stream));
-        HIPCHK(hipMemcpyAsync(c->bt_sub.p, subp.data(), sizeof(int) * K * K, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->bt_gh.p, cs->gap_h, sizeof(int) * K, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->bt_gv.p, cs->gap_v, sizeof(int) * K, hipMemcpyHostToDevice, c->stream));
-        // the ticket starts at zero for every launch (no last-arriver reset to rely on)
-        HIPCHK(hipMemsetAsync(c->bt_ticket.p, 0, sizeof(unsigned), c->stream));
+        BatchStage bs;
+        if (int r = stage_batch(c, codes, seq_off, nseq, npairs, cs, plan.kernel, plan.scratch_rows, bs)) return r;
         HIPCHK(hipEventRecord(c->ev[0], c->stream));
-        ga::launch_batch_fill(c->stream, c->bt_codes.as<uint8_t>(), c->bt_items.as<ga_batch_item>(), nitems,
-                              c->bt_sub.as<int>(), c->bt_gh.as<int>(), c->bt_gv.as<int>(), K, cs->gap_open, plan.qbytes,
-                              c->bt_ticket.as<unsigned>(), c->bt_out.as<long long>(),
-                              plan.scratch_rows > 0 ? c->bt_scratch.as<int2>() : nullptr, plan.scratch_rows, waves);
+        ga::launch_batch_fill(c->stream, bs.args, plan.qbytes, bs.waves);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(c->ev[1], c->stream));
         std::vector<long long> got((size_t)npairs);
@@ -2397,15 +2343,11 @@ int ga_batch_costs_ex(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, i
                                         ": needs the single-pair fill, which a slab context cannot run");
         c->rc_used = false;
         for (const int64_t k : plan.single) {
-            const int64_t sa = pair_a[k], sb = pair_b[k];
-            const int64_t m = seq_off[sa + 1] - seq_off[sa], n = seq_off[sb + 1] - seq_off[sb];
-            ga_costs own = *cs;  // this pair's sentinel comes from its own max_cost
-            if (pair_max_cost) own.max_cost = pair_max_cost[k];
-            int r = load_problem(c, codes + seq_off[sa], m, codes + seq_off[sb], n, &own, nullptr, nullptr, 0, n);
-            if (!r) r = enqueue_fill(c, 0);
-            if (!r) r = finish_fill(c, &cost_out[k], nullptr);
-            c->loaded = false;
-            if (r) return fail(r, "pair " + std::to_string(k) + ": " + g_err);
+            auto fill = [&](int64_t, int64_t) {
+                const int e = enqueue_fill(c, 0);
+                return e ? e : finish_fill(c, &cost_out[k], nullptr);
+            };
+            if (int r = batch_single_pair(c, codes, seq_off, pair_a, pair_b, pair_max_cost, cs, k, fill)) return r;
         }
     }
     return GA_OK;
@@ -2421,7 +2363,7 @@ int ga_batch_align(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int6
         return fail(GA_E_ARG, "null argument");
     const double t_call = now_ms();
     for (float& x : c->batch_align_ms) x = 0.f;
-    const int64_t max_waves = (int64_t)c->num_cu * 4 * 2;  // as ga_batch_costs_ex
+    const int64_t max_waves = batch_max_waves(c);
     gabatch::AlignLimits lim;
     if (const char* e = c->knob("GA_BATCH_ALIGN_MAX_CELLS")) lim.max_cells = std::max<int64_t>(0, atoll(e));
     lim.scratch_rows_cap = gabatch::scratch_rows_cap(max_waves);
@@ -2438,38 +2380,21 @@ int ga_batch_align(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int6
     if (!plan.single.empty() && c->slab)
         return fail(GA_E_STATE, "pair " + std::to_string(plan.single[0]) +
                                     ": needs the single-pair path, which a slab context cannot run");
-    const int K = cs->K;
     if (!plan.kernel.empty()) {
         const int nitems = (int)plan.kernel.size();
-        const int W = gabatch::kWavesPerGroup;
-        const int waves = (int)((std::min<int64_t>(max_waves, nitems) + W - 1) / W * W);
-        std::vector<int> subp((size_t)K * K);
-        for (int x = 0; x < K; x++)
-            for (int y = 0; y < K; y++) subp[x * K + y] = cs->sub[x * K + y] - cs->gap_v[x] - cs->gap_h[y];
-        const size_t ncodes = (size_t)seq_off[nseq];
-        HIPCHK(c->bt_codes.ensure(ncodes));
-        HIPCHK(c->bt_items.ensure(sizeof(ga_batch_item) * nitems));
+        BatchStage bs;
+        if (int r = stage_batch(c, codes, seq_off, nseq, npairs, cs, plan.kernel, plan.scratch_rows, bs)) return r;
+        // its own: the walk items, the pairs' tables, their level words and walk results, the waves' traceback words
         HIPCHK(c->bt_witems.ensure(sizeof(ga_batch_walk_item) * nitems));
-        HIPCHK(c->bt_sub.ensure(sizeof(int) * K * K));
-        HIPCHK(c->bt_gh.ensure(sizeof(int) * K));
-        HIPCHK(c->bt_gv.ensure(sizeof(int) * K));
-        HIPCHK(c->bt_ticket.ensure(sizeof(unsigned)));
-        HIPCHK(c->bt_out.ensure(sizeof(long long) * npairs));
         HIPCHK(c->bt_walk.ensure(sizeof(int4) * 2 * npairs));
         HIPCHK(c->bt_rng.ensure(sizeof(uint32_t) * plan.tab_entries));
         HIPCHK(c->bt_ops.ensure(sizeof(uint32_t) * plan.ops_words));
-        if (plan.scratch_rows > 0) HIPCHK(c->bt_scratch.ensure(sizeof(int2) * 2 * plan.scratch_rows * waves));
-        if (c->bt_tb.ensure(sizeof(uint32_t) * (size_t)plan.tb_words * waves) != hipSuccess)
+        if (c->bt_tb.ensure(sizeof(uint32_t) * (size_t)plan.tb_words * bs.waves) != hipSuccess) {
+            (void)hipStreamSynchronize(c->stream);  // the staged uploads read this call's buffers
             return fail(GA_E_NOMEM, "no device memory for the batch's traceback words");
-        HIPCHK(hipMemcpyAsync(c->bt_codes.p, codes, ncodes, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->bt_items.p, plan.kernel.data(), sizeof(ga_batch_item) * nitems, hipMemcpyHostToDevice,
-                              c->stream));
+        }
         HIPCHK(hipMemcpyAsync(c->bt_witems.p, plan.walk.data(), sizeof(ga_batch_walk_item) * nitems,
                               hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->bt_sub.p, subp.data(), sizeof(int) * K * K, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->bt_gh.p, cs->gap_h, sizeof(int) * K, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->bt_gv.p, cs->gap_v, sizeof(int) * K, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemsetAsync(c->bt_ticket.p, 0, sizeof(unsigned), c->stream));
         // every pair's tie-break table from its own seed, on a few host threads
         const double t_tab = now_ms();
         std::vector<uint32_t> tab((size_t)plan.tab_entries);
@@ -2479,12 +2404,9 @@ int ga_batch_align(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int6
         c->batch_align_ms[1] = (float)(now_ms() - t_tab);
         HIPCHK(hipMemcpyAsync(c->bt_rng.p, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipEventRecord(c->ev[0], c->stream));
-        ga::launch_batch_align(c->stream, c->bt_codes.as<uint8_t>(), c->bt_items.as<ga_batch_item>(), nitems,
-                               c->bt_sub.as<int>(), c->bt_gh.as<int>(), c->bt_gv.as<int>(), K, cs->gap_open, plan.qbytes,
-                               c->bt_ticket.as<unsigned>(), c->bt_out.as<long long>(),
-                               plan.scratch_rows > 0 ? c->bt_scratch.as<int2>() : nullptr, plan.scratch_rows, waves,
-                               plan.CB, c->bt_witems.as<ga_batch_walk_item>(), c->bt_rng.as<uint32_t>(),
-                               c->bt_ops.as<uint32_t>(), c->bt_walk.as<int4>(), c->bt_tb.as<uint32_t>(), plan.tb_words);
+        const ga::AlignArgs q{bs.args, c->bt_witems.as<ga_batch_walk_item>(), c->bt_rng.as<uint32_t>(),
+                              c->bt_ops.as<uint32_t>(), c->bt_walk.as<int4>(), c->bt_tb.as<uint32_t>(), plan.tb_words};
+        ga::launch_batch_align(c->stream, q, plan.qbytes, plan.CB, bs.waves);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(c->ev[1], c->stream));
         std::vector<long long> got((size_t)npairs);
@@ -2538,18 +2460,13 @@ int ga_batch_align(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int6
         c->rc_used = false;
         uint32_t state[MTN + 1];
         for (const int64_t k : plan.single) {
-            const int64_t sa = pair_a[k], sb = pair_b[k];
-            const int64_t m = len_of(sa), n = len_of(sb);
-            ga_costs own = *cs;  // this pair's sentinel comes from its own max_cost
-            if (pair_max_cost) own.max_cost = pair_max_cost[k];
-            seed_state(seeds[k], state);
-            int r = load_problem(c, codes + seq_off[sa], m, codes + seq_off[sb], n, &own, nullptr, nullptr, 0, n);
-            if (!r)
-                r = ga_problem_align(c, state, chars + seq_off[sa], chars + seq_off[sb], out_a + out_off[k],
-                                     out_mid + out_off[k], out_b + out_off[k], out_off[k + 1] - out_off[k], &out_len[k],
-                                     &tb_status[k], &cost_out[k]);
-            c->loaded = false;
-            if (r) return fail(r, "pair " + std::to_string(k) + ": " + g_err);
+            auto align = [&](int64_t sa, int64_t sb) {
+                seed_state(seeds[k], state);
+                return ga_problem_align(c, state, chars + seq_off[sa], chars + seq_off[sb], out_a + out_off[k],
+                                        out_mid + out_off[k], out_b + out_off[k], out_off[k + 1] - out_off[k],
+                                        &out_len[k], &tb_status[k], &cost_out[k]);
+            };
+            if (int r = batch_single_pair(c, codes, seq_off, pair_a, pair_b, pair_max_cost, cs, k, align)) return r;
         }
     }
     c->batch_align_ms[3] = (float)(now_ms() - t_call);
@@ -2682,15 +2599,8 @@ int ga_problem_set_slab(ga_ctx* c, const uint8_t* a, int64_t m, const uint8_t* b
     c->walk_rng_ready = false;
     if (int r = load_problem(c, a, m, b, n, cs, nullptr, nullptr, col_begin, col_end)) return r;
     HIPCHK(c->halo_in.ensure(sizeof(int2) * (m + 1)));
-    if (!c->prog_host) {
-        void* hp = nullptr;
-        HIPCHK(hipHostMalloc(&hp, 256, hipHostMallocMapped | hipHostMallocCoherent));
-        c->prog_host = static_cast<uint32_t*>(hp);
-        void* dp = nullptr;
-        HIPCHK(hipHostGetDevicePointer(&dp, hp, 0));
-        c->prog_dev = static_cast<uint32_t*>(dp);
-    }
-    std::memset(c->prog_host, 0, 256);
+    HIPCHK(c->prog.ensure(256));
+    std::memset(c->prog.p, 0, 256);
     return GA_OK;
 }
 
@@ -2787,19 +2697,19 @@ int ga_slab_buffers(ga_ctx* c, void** halo_in, uint32_t** halo_in_prog, void** h
     if (int r = check_ctx(c)) return r;
     if (!c->slab) return fail(GA_E_STATE, "not a slab context");
     if (halo_in) *halo_in = c->halo_in_ext ? (void*)c->halo_in_ext : c->halo_in.p;
-    if (halo_in_prog) *halo_in_prog = c->prog_host;
+    if (halo_in_prog) *halo_in_prog = c->prog.host<uint32_t>();
     if (halo_out)
         *halo_out = c->halo_out_ext ? (void*)c->halo_out_ext
                                     : (void*)(c->hand.as<int2>() + (size_t)(c->nslabs - 1) * (c->m + 1));
-    if (halo_out_prog) *halo_out_prog = c->prog_host + 1;
+    if (halo_out_prog) *halo_out_prog = c->prog.host<uint32_t>() + 1;
     return GA_OK;
 }
 
 int ga_slab_fill_launch(ga_ctx* c, int32_t flags) {
     if (int r = check_ctx(c)) return r;
     if (!c->slab) return fail(GA_E_STATE, "not a slab context");
-    __atomic_store_n(&c->prog_host[0], 0u, __ATOMIC_SEQ_CST);
-    __atomic_store_n(&c->prog_host[1], 0u, __ATOMIC_SEQ_CST);
+    __atomic_store_n(c->prog.host<uint32_t>(), 0u, __ATOMIC_SEQ_CST);
+    __atomic_store_n(c->prog.host<uint32_t>() + 1, 0u, __ATOMIC_SEQ_CST);
     c->rc_used = false;
     if ((flags & GA_FILL_TRACEBACK) && rc_slab_eligible(c)) {
         // the slab's traceback by recompute: checkpoints instead of m * n words

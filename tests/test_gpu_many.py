@@ -109,18 +109,27 @@ def test_align_repeated_pipe_modes(monkeypatch, mode, fills, m, n, seed, count, 
     assert random.getstate()[1] == tuple(int(x) for x in ref[-1][2])
 
 
-@pytest.mark.parametrize("chain", ["1", "0"])
-@pytest.mark.parametrize("m,n,seed,count,kw", [
+_CHAIN_SHAPES = [
     (700, 650, 13, 11, dict(match_score=2, mismatch_score=-3, gap_open_score=-5, gap_extension_score=-1)),
     (600, 640, 14, 9, dict(scoring_mat_name="BLOSUM62", gap_open_score=-10)),
     (40000, 300, 15, 7, dict(match_score=2, mismatch_score=-3, gap_open_score=-5, gap_extension_score=-1)),
-])
-def test_align_repeated_walk_chain(monkeypatch, chain, m, n, seed, count, kw):
+]
+# every shape with and without the chain, and the smallest once more with the per-launch walks' result words and
+# levels in device memory (GA_PIPE_PINNED_IO=0: read back with plain copies)
+_CHAIN_CASES = [pytest.param(*s, chain, None, id=f"{s[0]}-{s[1]}-{s[2]}-{s[3]}-kw{q}-{chain}")
+                for chain in ("1", "0") for q, s in enumerate(_CHAIN_SHAPES)]
+_CHAIN_CASES.append(pytest.param(*_CHAIN_SHAPES[1], "0", "0", id="600-640-14-9-kw1-0-devio"))
+
+
+@pytest.mark.parametrize("m,n,seed,count,kw,chain,pinned_io", _CHAIN_CASES)
+def test_align_repeated_walk_chain(monkeypatch, chain, pinned_io, m, n, seed, count, kw):
     """Walks chained in one launch (walk_chain_kernel, opt-in GA_PIPE_CHAIN=1) and one launch per walk (the default):
     more alignments than slots (every slot reused), short walks that outrun the tie-break producer, a tall
     pair; each alignment's strings and cost and the final random state equal the chained oracle's."""
     import globalign_amd
     set_knob(monkeypatch, "GA_PIPE_CHAIN", chain)
+    if pinned_io is not None:
+        set_knob(monkeypatch, "GA_PIPE_PINNED_IO", pinned_io)
     alpha = "protein" if "scoring_mat_name" in kw else "dna"
     s1, s2 = splitmix_seq(m, seed, alpha), splitmix_seq(n, seed + 1, alpha)
     ref = _chain_oracle(s1, s2, kw, seed, count)
