@@ -74,7 +74,7 @@ struct FillArgs {
     // wave; nullptr: the profile wave computes it from a and sub'
     const uint32_t* qprof;
     // lane fill, score only: the lean sub-chunk from the first step (ga_lane.hip), allowed when row 0 is uniform in the
-    // shifted domain (H'(0, j) = o and h2'(0, j) = 2o for every column: the reference's boundary with 2o + GH(n) <=
+    // shifted domain (H'(0, j) = o and h2'(0, j) = 2o for every column: the reference's boundary with 2o + max GH(j) <=
     // big): lanes still above row 1 then step on zero profile bytes and keep exactly those values
     int lean0;
 };

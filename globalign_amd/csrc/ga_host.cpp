@@ -168,6 +168,7 @@ struct ga_ctx {
     int64_t n_global = 0, col0 = 0;
     int K = 0, o = 0, big = 0, CB = 1, qbytes = 1;
     int64_t gh_total = 0;      // GH(n_global): the sum of the horizontal gap costs of seq_2
+    int64_t gh_max = 0;        // max over j = 1 .. n_global of GH(j): with gap costs of mixed sign GH is not monotone
     int64_t gv_total = 0;      // GV(m): the sum of the vertical gap costs of seq_1
     // a streamed single call's small results in pinned, coherent host memory (no copy after the walk): [0, 16) the
     // walk's result words (it writes them there), [16, 20) the fill's H'(m, n) words, [20] its abort word (copied on
@@ -413,8 +414,12 @@ int load_problem(ga_ctx* c, const uint8_t* a, int64_t m, const uint8_t* b_all, i
     c->o = o;
     c->big = (int)big;
     c->custom = row0 != nullptr || col0 != nullptr;
-    c->gh_total = 0;  // GH(n) of the whole problem: the lean ramp's uniform-row-0 test (enqueue_fill), the cost
-    for (int64_t j = 0; j < n_all; j++) c->gh_total += cs->gap_h[b_all[j]];
+    c->gh_total = 0;  // GH(n) of the whole problem (the cost's un-shift), and the largest GH(j) of any column: the
+    c->gh_max = INT64_MIN;  // lean ramp's uniform-row-0 test (enqueue_fill)
+    for (int64_t j = 0; j < n_all; j++) {
+        c->gh_total += cs->gap_h[b_all[j]];
+        c->gh_max = std::max(c->gh_max, c->gh_total);
+    }
     c->gv_total = 0;  // GV(m): the cost's un-shift (cost = H'(m, n) + GV(m) + GH(n))
     for (int64_t i = 0; i < m; i++) c->gv_total += cs->gap_v[a[i]];
     // one stripe (64 columns) per compute wave; a workgroup (one per CU) chains 4 waves (one per
@@ -785,11 +790,12 @@ int enqueue_fill(ga_ctx* c, int32_t flags, const Band& bd = Band()) {
     // the lane fill's query profile, built on the fill's stream just before it (K x (m + 4) dwords: C5 1.9 MB, a few us).
     // Fills of one problem in flight on other streams (align_many) rewrite it with the same values.
     // the lean ramp (ga_lane.hip lean0): row 0 is the reference's boundary and uniform in the shifted domain (H' = o,
-    // h2' = 2o in every column: 2o + GH(n) <= big); GA_LANE_LEAN0=0 keeps the masked ramp (A/B)
+    // h2' = 2o in every column: 2o + GH(j) <= big for every j, so for the largest prefix sum, which is GH(n) only
+    // when no gap cost is negative); GA_LANE_LEAN0=0 keeps the masked ramp (A/B)
     {
         const char* e = c->knob("GA_LANE_LEAN0");
         p.lean0 = (e ? atoi(e) : 1) && c->lane && !c->custom && bd.top == nullptr && !bd.band &&
-                  2 * (int64_t)c->o + c->gh_total <= (int64_t)c->big;
+                  2 * (int64_t)c->o + c->gh_max <= (int64_t)c->big;
     }
     p.qprof = nullptr;
     if (c->lane && !c->xknob("GA_LANE_QPROF_WAVE")) {  // (experiments build: the profile wave builds it, for A/B)

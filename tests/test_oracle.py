@@ -10,6 +10,8 @@ reference (tests/golden/make_golden.py):
                          degenerate lengths that raise IndexError (A.5)
   * random_fill.json  -- dp_array_forward on arbitrary boundaries
   * splitmix.json     -- SURVEY 8d synthetic configs (1k, 2k, 10k)
+  * general_costs.json -- make_dp_array + dp_array_forward + dp_array_backward under letter-dependent,
+                         asymmetric cost tables (tests/golden/make_general_golden.py, tests/general_costs.py)
 """
 import json
 import os
@@ -125,6 +127,68 @@ def test_oracle_splitmix(mode, okw):
         assert aln_digest(a, mid, b) == rec["aln_sha16"]
         assert res["ndispatch"] * 18 == rec["choices"]
         assert state_digest(core.mt_state_tuple(res["mt_out"])) == rec["state_after"]
+
+
+@pytest.mark.parametrize("mode", ["full", "sets", "ckpt"])
+def test_oracle_general_costs(mode):
+    """The reference under general tables (asymmetric sub with a non-zero diagonal, a gap cost per letter that
+    differs between the two directions, signed and wide values, a matrix file with a gap score per letter): every
+    record's status, cost, strings and final random state through each walk of the oracle.  Family S also pins the
+    oracle's restated .mtx transform against the reference's costing dict."""
+    from tests import general_costs as gc
+    cases = json.load(open(os.path.join(GOLDEN, "general_costs.json")))
+    assert {rec["family"] for rec in cases} == {"G", "W", "S"} and len(cases) >= 50
+    assert sum(rec["status"] == "IndexError" for rec in cases) >= 3  # the degenerate-length quirk is in the fixture
+    kw = dict(threads=3, tile=(3, 5)) if mode == "ckpt" else {}
+    for rec in cases:
+        cmat, o = rec["costing_mat"], rec["gap_open_cost"]
+        if rec["family"] == "S":
+            mtx = transform.read_mtx_rows(rec["mtx"]["letters"], rec["mtx"]["scores"])
+            _, _, _, cmat_s, _, goc = transform.settings(
+                dict(seq_1=rec["seq_1"], seq_2=rec["seq_2"], scoring_mat_path="<mtx>", gap_open_score=-o), mtx=mtx)
+            assert cmat_s == cmat and list(cmat_s.keys()) == list(cmat.keys()) and goc == o
+        else:
+            assert cmat == gc.table(rec["family"], rec["table_seed"])
+        random.seed(rec["seed"])
+        res = core.align(rec["seq_1"], rec["seq_2"], cmat, o, core.mt_state_array(), mode=mode, **kw)
+        assert res["status"] == rec["status"]
+        assert res["cost"] == rec["cost"]
+        if rec["status"] == "ok":
+            assert list(res["strings"]) == rec["strings"]
+        assert state_digest(core.mt_state_tuple(res["mt_out"])) == rec["state_after"]
+
+
+def test_general_cost_cases_can_fail():
+    """Every GPU case of tests/general_costs.py with unequal sides of at least 17 letters must be able to fail: the
+    oracle's cost (core.boundary + core.fill_score) changes when gap_h and gap_v are swapped, when sub is transposed
+    and when the gap costs are rotated by one letter -- what a kernel reading the wrong table entry would compute.
+    Family S is symmetric by the API's own requirement (a scoring matrix file must be), so transposing its sub is
+    the identity and is not asked of it; its swap and rotation are."""
+    from tests import general_costs as gc
+    met = {"G": 0, "W": 0, "S": 0}
+    for case in gc.all_gpu_cases():
+        if not gc.eligible(case):
+            continue
+        family, tseed, m, n, o = case
+        cmat = gc.table(family, tseed)
+        s1, s2 = gc.sequences(case)
+        base = gc.oracle_cost(cmat, s1, s2, o)
+        for kind in gc.CORRUPTIONS:
+            bad = gc.corrupt(cmat, kind)
+            if family == "S" and kind == "transpose":
+                assert bad == cmat
+                continue
+            assert gc.oracle_cost(bad, s1, s2, o) != base, (case, kind)
+        met[family] += 1
+    print("cases that can fail under every corruption:", met)
+    assert met == {"G": 49, "W": 34, "S": 12}  # every eligible case of the lists, none dropped unnoticed
+
+
+def test_general_cost_lean_ramp_case():
+    """The lean-ramp case's arithmetic (tests/general_costs.lean_ramp_case asserts it while building)."""
+    from tests import general_costs as gc
+    cmat, s1, s2, o = gc.lean_ramp_case()
+    assert (len(s1), len(s2), o) == (5, 70, 4600) and s2[35:] == "T" * 35 and "T" not in s2[:35]
 
 
 def test_mt_emulation_matches_cpython():
