@@ -31,6 +31,7 @@
 #include "ga_check.h"
 #include "ga_batch.h"
 #include "ga_batch_align.h"
+#include "ga_plan.h"
 #include "ga_rng.h"
 #include "ga_strings.h"
 
@@ -52,7 +53,7 @@ int fail(int code, const std::string& msg) {
 
 // ------------------------------------------------------------------ buffers
 // Device memory that grows on demand and is released with its owner (a context or a pipeline slot): nothing copies
-// one, Band and the launches' argument structs hold pointers into it.
+// one, FillBufs, Band and the launches' argument structs hold pointers into it.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
@@ -113,7 +114,31 @@ struct PinBuf {
     T* dev() const { return static_cast<T*>(dp); }
 };
 
+// The buffers one fill writes, and its two timing events (created and destroyed by their owner): the context has
+// one set, every pipeline slot one of its own, so that fills can run side by side.
+struct FillBufs {
+    DevBuf tb;                 // traceback words
+    DevBuf hand;               // workgroup hand-off edges
+    DevBuf flags;              // [0] ticket, [1] abort
+    DevBuf out_last;           // H'(m, n)
+    DevBuf GVp, GHp, top, left, bnd_row, bnd_col, meta, bscr;  // the boundary pass's output (make_dp_array) and scratch
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    // the boundary arrays of an m x n_all problem, and the fill's four result words
+    hipError_t ensure_boundary(int64_t m, int64_t n_all) {
+        const std::pair<DevBuf*, size_t> want[] = {
+            {&bnd_row, sizeof(int) * 3 * (n_all + 1)}, {&bnd_col, sizeof(int) * 3 * (m + 1)},
+            {&GVp, sizeof(int) * (m + 1)},             {&bscr, sizeof(int) * ga::boundary_scratch_ints((int)m, (int)n_all)},
+            {&GHp, sizeof(int) * (n_all + 1)},         {&top, sizeof(int2) * (n_all + 1)},
+            {&left, sizeof(int2) * (m + 1)},           {&meta, sizeof(int) * 8},
+            {&out_last, sizeof(int) * 4}};
+        for (const auto& [buf, bytes] : want)
+            if (hipError_t e = buf->ensure(bytes); e != hipSuccess) return e;
+        return hipSuccess;
+    }
+};
+
 using namespace garng;
+static_assert(gaplan::kFillRows == ga::FROWS, "the planner's chunk rows (ga_plan.h)");
 static_assert(ga::COLCK_PAD == 64, "rc_rows_fit (ga_check.h) assumes a 64-row pad");
 
 }  // namespace
@@ -161,7 +186,7 @@ struct ga_ctx {
     int priority = 0;  // of `stream` (the greatest the device offers, see ga_ctx_create)
     hipStream_t stream = nullptr;
     hipEvent_t ev_dep = nullptr;  // ga_ctx_wait_stream
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t wev[2] = {nullptr, nullptr};  // the walk's timing events (the fill's: fb.ev)
     // problem
     bool loaded = false, custom = false, filled_tb = false;
     int64_t m = 0, n = 0;      // local problem (slab: n = local columns)
@@ -176,19 +201,16 @@ struct ga_ctx {
     PinBuf res_pin{true};
     hipEvent_t ev_fill = nullptr, ev_res = nullptr;
     bool rc_pos_zeroed = false;  // rc_pos was cleared on the fill's stream before the fill (rc_align)
-    int nstripes = 0, nslabs = 0, TC = 0, nwc = 4, qrows = 1024, num_cu = 256;
-    int T = 1, T_req = 0, nwc_req = 0;
-    int diag_req = 0;          // score-only fill kernel: 0 automatic, 1 row scan, 2 anti-diagonal, 3 lane-skewed (GA_FILL_MODE)
-    int lane_T_req = 0;        // columns per lane of the lane-skewed kernel (GA_LANE_COLS_PER_LANE; 0: automatic)
-    bool lane = false;         // the last enqueued fill used the lane-skewed kernel
-    int diag_T_req = 0;        // columns per lane of the anti-diagonal kernel (GA_DIAG_COLS_PER_LANE; 0: automatic)
-    bool diag = false;         // the last enqueued fill used the anti-diagonal kernel      // columns per lane of the fill (T_req 0: automatic; GA_COLS_PER_LANE)
+    int qrows = 1024, num_cu = 256;  // the row scan's query-profile ring (load_problem)
+    gaplan::Knobs pk;          // the planner's knobs, parsed once (plan_knobs)
+    // the last enqueued fill's plan (ga_plan.h): kernel, geometry, checkpoint spacing; before the first fill the
+    // loaded problem's row-scan geometry
+    gaplan::FillPlan plan;
     int64_t GV_m = 0, GH_n = 0;
     std::vector<uint8_t> h_a, h_b;
     // device buffers
-    DevBuf a, b, sub, gh, gv, qp, GVp, GHp, top, left, bnd_row, bnd_col, meta, hand, flags, tb, out_last, full, rng, bscr,
-        ckpt,
-        ops, result;
+    DevBuf a, b, sub, gh, gv, qp, full, rng, ckpt, ops, result;
+    FillBufs fb;  // what a fill writes
     DevBuf halo_in{true};  // uncached
     bool slab = false;
     // slab progress words in pinned, coherent host memory: [0] halo_in rows (written by the host
@@ -204,10 +226,9 @@ struct ga_ctx {
     // pipelined repeated alignments (ga_problem_align_many): two slots of traceback words, walk
     // buffers and events; the walk runs on its own stream beside the next fill
     struct PipeSlot {
-        DevBuf tb, hand, flags, out_last, rng, ops, result;
-        // each pipelined alignment computes its own boundary (make_dp_array) into its slot
-        DevBuf GVp, GHp, top, left, bnd_row, bnd_col, meta, bscr;
-        hipEvent_t f0 = nullptr, f1 = nullptr, fdone = nullptr, w0 = nullptr, w1 = nullptr;
+        FillBufs fb;  // each pipelined alignment computes its own boundary (make_dp_array) into its slot
+        DevBuf rng, ops, result;
+        hipEvent_t fdone = nullptr, w0 = nullptr, w1 = nullptr;
         PinBuf tab_pin;  // pinned staging of the walk's table slice
     } pipe[6];
     hipStream_t wstream = nullptr, fstream[4] = {nullptr, nullptr, nullptr, nullptr};  // [0] unused: ctx->stream
@@ -265,9 +286,8 @@ struct ga_ctx {
     PinBuf up_pin;
     hipStream_t ustream = nullptr;
     hipEvent_t ev_up = nullptr;
-    int rc_T = 0;          // its fill stripe width (64-column tiles per block)
+    gaplan::FillPlan rc_plan;  // the plan of the fill the recompute walk reads (rc_fill): stripes, spacing
     bool rc_jump = false;  // the last recompute walk was the tie-to-tie walk (jump entries)
-    int rc_every_used = 64;
 };
 
 namespace {
@@ -279,112 +299,24 @@ int check_ctx(ga_ctx* c) {
     return GA_OK;
 }
 
-// Stripe geometry: T columns per lane (a stripe = one compute wave = 64*T columns).
-// Blocked stripes pay the wave scan, the edge traffic and the control once per 64*T cells, but
-// leave fewer stripes (waves) to fill the chip and lengthen each row's dependent chain.  A
-// workgroup chains 4 waves (one per SIMD) when every stripe gets a wave that way, else 8.
-void set_stripes(ga_ctx* c, int T_req, bool tb, bool full, int64_t ncols = -1) {
-    const int64_t ncol = ncols < 0 ? c->n : ncols;  // a traceback band may cover a prefix of the columns
-    const int64_t simds = 4 * (int64_t)c->num_cu;
-    // register budget (no spills, see the code objects' vgpr_spill_count): the FULL debug output is
-    // T == 1 only; traceback words T <= 2; score only T <= 8 with an int8 profile, 4 with int16
-    const int cap = full ? 1 : tb ? 2 : (c->qbytes == 2 ? 4 : 8);
-    int T = 1;
-    if (T_req == 1 || T_req == 2 || T_req == 4 || T_req == 8) {
-        T = std::min(T_req, cap);
-    } else {
-        // the widest stripes that still leave >= 1.5 waves per SIMD (measured: 1M columns score
-        // only T = 8 > 4 > 2 > 1; 100k columns with traceback T = 1 > 2 > 4)
-        for (int t = cap; t > 1; t /= 2)
-            if ((ncol + 64 * t - 1) / (64 * t) * 2 >= 3 * simds) {
-                T = t;
-                break;
-            }
-    }
-    // a slab with a right neighbour hands column n on: its last stripe must be whole (T == 1
-    // takes the edge from any lane)
-    while (T > 1 && c->col0 + c->n < c->n_global && c->n % (64 * T) != 0) T /= 2;
-    c->T = T;
-    c->nstripes = (int)((ncol + 64 * T - 1) / (64 * T));
-    c->nwc = c->nwc_req == 4 || c->nwc_req == 8 ? c->nwc_req : c->nstripes <= 4 * c->num_cu ? 4 : 8;
-    c->nslabs = (c->nstripes + c->nwc - 1) / c->nwc;
-}
-
-// Lane-skewed fill geometry: TD columns per lane, NWC compute waves per workgroup,
-// every stripe resident at once (a stripe waits on its left neighbour only, so the whole chain must
-// run concurrently).  The cost model is the measured step of tools/micro/lane_bench.hip (cycles per
-// step per wave at one / two waves per SIMD, with the kernel's per-step LDS traffic and the DPP
-// shift-register output) times the chain's length, m steps plus ~74 steps of skew per stripe.
-// Returns false (row scan) when the profile table does not fit beside the rings.
-bool lane_geometry(ga_ctx* c, int64_t ncol, int* qrows_out, bool tb, int force_T = 0, int force_N = 0,
-                   int qrows_cap = 0) {
-    if (c->qbytes != 1 || c->K > 32) return false;
-    // Cycles per step per wave measured in the kernel (score only, 16-step sub-chunks; tools/lane_stamps.py,
-    // tools/exp/lane_sub.sh, tools/exp/c4_pack.sh): one wave per SIMD (4-wave workgroups) 84 / 115 / 154 /
-    // 239 at TD = 1 / 2 / 4 / 8; two waves per SIMD (8-wave workgroups) about 2.1x that per wave, the
-    // partner's issue plus the chain coupling (C4: 243 ms against 207 for 1-wave rounds).
-    static const double cyc1[4] = {84, 115, 154, 239};
-    // workgroups per CU the residency check may count on (GA_LANE_WG_PER_CU, tuning: 2 needs an LDS floor
-    // below 80 KB, GA_FILL_LDS_FLOOR)
-    const int wpc = [c] {
-        const char* e = c->knob("GA_LANE_WG_PER_CU");
-        return e ? std::max(1, std::min(2, atoi(e))) : 1;
-    }();
-    int64_t cus = c->num_cu * wpc;
-    // A slab whose edge another kernel (an RCCL receive or send) must move WHILE the fill runs: keep one CU
-    // of every shader engine (8 CUs) free and every workgroup resident.  A kernel launched beside the fill
-    // places each of its workgroups on a CU of one shader engine, round robin, and waits there: measured
-    // (tools/exp/r3_cores.py), an RCCL-shaped kernel starts beside 224 fill workgroups on 256 CUs, not
-    // beside 228.  Linked edges (ga_slab_link / _import: the fill stores them itself) need no room.
-    const bool coresident = c->slab && ((c->col0 > 0 && !c->in_prog_ext) ||
-                                        (c->col0 + c->n < c->n_global && !c->out_prog_ext));
-    if (coresident) cus = c->num_cu - c->num_cu / 8;
-    // Rounds: with 4-wave workgroups, one per CU, more stripes than 4 per CU run in rounds of workgroups.
-    // A later round starts as the first finish, on left edges long written, so it runs uncoupled; the
-    // chain then takes R*m + skew steps at the 1-wave step cost.  Not for a slab with a right neighbour
-    // (its last stripe, in the last round, would hold the next GPU back by the earlier rounds).
-    const bool right_nb = c->col0 + c->n < c->n_global;
-    int bestT = 0, bestN = 0;
-    double best = 0;
-    for (int ti = 0; ti < 4; ti++) {
-        const int T = 1 << ti;
-        if (force_T ? force_T != T : c->lane_T_req && c->lane_T_req != T) continue;
-        // traceback windows (register budget, ga_lane.hip lane_variant_ok): TD <= 4 with one-byte
-        // words, <= 2 with two- and four-byte words (four-byte: 4 waves per workgroup)
-        if (tb && T > (c->CB == 1 ? 4 : 2)) continue;
-        // a slab with a right neighbour hands column n on: its last stripe must be whole
-        if (right_nb && ncol % (64 * T) != 0) continue;
-        const int64_t ns = (ncol + 64 * T - 1) / (64 * T);
-        for (int nwc : {4, 8}) {
-            if (force_N ? force_N != nwc : (c->nwc_req == 4 || c->nwc_req == 8) && nwc != c->nwc_req) continue;
-            if (tb && c->CB == 4 && nwc == 8) continue;
-            const int64_t rounds = (ns + nwc * cus - 1) / (nwc * cus);
-            if (rounds > 1 && (nwc == 8 || right_nb || tb || coresident)) continue;  // 8-wave workgroups: all resident
-            const double step = nwc == 4 ? cyc1[ti] : 2.1 * cyc1[ti];
-            const double t = ((double)rounds * (double)c->m + 74.0 * (double)ns) * step;
-            if (!bestT || t < best) {
-                best = t;
-                bestT = T;
-                bestN = nwc;
-            }
-        }
-    }
-    if (!bestT) return false;
-    // GA_LANE_QROWS caps the profile table (tuning: a smaller table lets two workgroups share a CU)
-    const int qcap = [c] {
-        const char* e = c->knob("GA_LANE_QROWS");
-        return e ? atoi(e) : 4096;
-    }();
-    const size_t budget = 150 * 1024;
-    int qr = std::max(256, std::min(4096, qrows_cap > 0 ? qrows_cap : qcap));
-    while (qr > 256 && ga::fill_lane_lds_bytes(bestN, c->K, qr) > budget) qr >>= 1;
-    if (ga::fill_lane_lds_bytes(bestN, c->K, qr) > budget || qr < bestN * 64 + 192) return false;
-    c->T = bestT;
-    c->nwc = bestN;
-    c->nstripes = (int)((ncol + 64 * bestT - 1) / (64 * bestT));
-    c->nslabs = (c->nstripes + c->nwc - 1) / c->nwc;
-    *qrows_out = qr;
-    return true;
+// The loaded problem or slab as the fill planner sees it (ga_plan.h).
+gaplan::Problem plan_problem(const ga_ctx* c) {
+    gaplan::Problem pb;
+    pb.m = c->m;
+    pb.n = c->n;
+    pb.n_global = c->n_global;
+    pb.col0 = c->col0;
+    pb.K = c->K;
+    pb.CB = c->CB;
+    pb.qbytes = c->qbytes;
+    pb.o = c->o;
+    pb.num_cu = c->num_cu;
+    pb.qrows = c->qrows;
+    pb.slab = c->slab;
+    pb.in_linked = c->in_prog_ext != nullptr;
+    pb.out_linked = c->out_prog_ext != nullptr;
+    pb.custom = c->custom;
+    return pb;
 }
 
 // sub' = sub - gV - gH, K x K: what every fill adds per cell in the shifted domain
@@ -422,9 +354,6 @@ int load_problem(ga_ctx* c, const uint8_t* a, int64_t m, const uint8_t* b_all, i
     }
     c->gv_total = 0;  // GV(m): the cost's un-shift (cost = H'(m, n) + GV(m) + GH(n))
     for (int64_t i = 0; i < m; i++) c->gv_total += cs->gap_v[a[i]];
-    // one stripe (64 columns) per compute wave; a workgroup (one per CU) chains 4 waves (one per
-    // SIMD: the fastest rows) when every stripe gets a wave that way, else 8 (two per SIMD)
-    set_stripes(c, c->T_req, false, false);
     c->h_a.assign(a, a + m);
     c->h_b.assign(b_all, b_all + n_all);
     HIPCHK(c->a.ensure(m));
@@ -437,11 +366,10 @@ int load_problem(ga_ctx* c, const uint8_t* a, int64_t m, const uint8_t* b_all, i
     HIPCHK(hipMemcpyAsync(c->sub.p, cs->sub, sizeof(int) * K * K, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->gh.p, cs->gap_h, sizeof(int) * K, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->gv.p, cs->gap_v, sizeof(int) * K, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c->bnd_row.ensure(sizeof(int) * 3 * (n_all + 1)));
-    HIPCHK(c->bnd_col.ensure(sizeof(int) * 3 * (m + 1)));
+    HIPCHK(c->fb.ensure_boundary(m, n_all));
     if (c->custom) {
-        HIPCHK(hipMemcpyAsync(c->bnd_row.p, row0, sizeof(int) * 3 * (n_all + 1), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->bnd_col.p, col0, sizeof(int) * 3 * (m + 1), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->fb.bnd_row.p, row0, sizeof(int) * 3 * (n_all + 1), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->fb.bnd_col.p, col0, sizeof(int) * 3 * (m + 1), hipMemcpyHostToDevice, c->stream));
     }
     {
         // sub', read by the fill's IO wave into its LDS query profile
@@ -455,13 +383,10 @@ int load_problem(ga_ctx* c, const uint8_t* a, int64_t m, const uint8_t* b_all, i
             160 * 1024)
             return fail(GA_E_RANGE, "alphabet too large for the LDS query profile");
     }
-    HIPCHK(c->GVp.ensure(sizeof(int) * (m + 1)));
-    HIPCHK(c->bscr.ensure(sizeof(int) * ga::boundary_scratch_ints((int)m, (int)n_all)));
-    HIPCHK(c->GHp.ensure(sizeof(int) * (n_all + 1)));
-    HIPCHK(c->top.ensure(sizeof(int2) * (n_all + 1)));
-    HIPCHK(c->left.ensure(sizeof(int2) * (m + 1)));
-    HIPCHK(c->meta.ensure(sizeof(int) * 8));
-    HIPCHK(c->out_last.ensure(sizeof(int) * 4));
+    // the loaded problem's row-scan geometry, until a fill plans its own: one stripe (64 columns) per compute wave;
+    // a workgroup (one per CU) chains 4 waves (one per SIMD: the fastest rows) when every stripe gets a wave that
+    // way, else 8 (two per SIMD)
+    c->plan = gaplan::row_plan(plan_problem(c), c->pk);
     HIPCHK(c->result.ensure(sizeof(int) * 16));
     HIPCHK(c->ops.ensure(m + n_all + 1024));  // 2-bit levels; the walk flushes whole 128-byte blocks
     HIPCHK(c->rng.ensure(sizeof(uint32_t) * (m + n_all + 2 + 64)));  // + the walk's entry look-ahead (SLD)
@@ -482,260 +407,105 @@ int64_t dev_avail_bytes(ga_ctx* c, int64_t held) {
 }
 
 // A band of rows of the whole problem (banded traceback): rows r0+1 .. r0+mb, its
-// top row from a checkpoint (nullptr: row 0), no boundary pass; or the checkpointing pass itself.
-struct Band {
-    int64_t r0 = 0, mb = 0;
-    int64_t nc = 0;             // columns 1..nc only (0: all): the walk enters the band at column nc
+// top row from a checkpoint (nullptr: row 0), no boundary pass; or the checkpointing pass itself; or the recompute
+// walk's score fill; or a pipeline slot's fill (align_many): the planner's request (ga_plan.h; tb, full and
+// has_ckpt are enqueue_fill's to set) and where the fill reads and writes.
+struct Band : gaplan::Request {
+    int64_t r0 = 0;
     const int2* top = nullptr;  // (H', h2') of row r0, [n+1] (column 0 = the left edge's corner)
-    bool band = false;          // fill rows r0+1 .. r0+mb only (the boundary is already computed)
-    // the recompute walk's score fill: the lane kernel with its checkpoints (every stripe's
-    // right edge, the staircase lane states every rc_every steps) into ctx->colck / ctx->stck
-    bool rc = false;
-    int rc_every = 0;           // 0: chosen with the stripes' geometry (enqueue_fill)
     int2* ckpt = nullptr;       // checkpointing pass: where rows ckpt_rows, 2*ckpt_rows, ... go
     int ckpt_rows = 0;
-    // pipelined alignments (align_many): a fill with buffers and a stream of its own, so that two
-    // fills can run at once; the boundary is computed by the first fill only
-    DevBuf* tbuf = nullptr;     // traceback words instead of ctx->tb
-    DevBuf* hbuf = nullptr;     // workgroup hand-off edges instead of ctx->hand
-    DevBuf* fbuf = nullptr;     // ticket / abort words instead of ctx->flags
-    DevBuf* obuf = nullptr;     // H'(m, n) instead of ctx->out_last
+    // pipelined alignments (align_many): a fill with buffers and a stream of its own, so that several fills can
+    // run at once (nullptr: the context's)
+    FillBufs* bufs = nullptr;
     hipStream_t stream = nullptr;
-    bool skip_boundary = false;
-    // a traceback fill through the lane-skewed kernel at this geometry (TD columns per lane, NWC
-    // compute waves; 0: the usual choice): the pipeline's narrow fills (align_many)
-    int lane_td = 0, lane_nwc = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // fill timing events instead of ctx->ev[0 / 1]
-    // boundary arrays instead of the context's (a pipeline slot's own make_dp_array output)
-    DevBuf *GVp = nullptr, *GHp = nullptr, *top_b = nullptr, *left = nullptr, *bnd_row = nullptr, *bnd_col = nullptr,
-           *meta = nullptr, *bscr = nullptr;
 };
 
-// Enqueue boundary + query profile + fill.  Does not synchronise.
 #ifdef GA_EXPERIMENTS
 constexpr bool kRcJumpDefault = false;  // the tie-to-tie walk unless GA_RC_JUMP says otherwise
 #endif
 // the recompute walk's block cache: the word walk's, and (experiments build) the tie-to-tie walk's entries
-inline size_t rc_cache_bytes(bool jump, int TD, int CB) {
+size_t rc_cache_bytes(bool jump, int TD, int CB) {
     // (+ one 64-column stripe of slack: a loader reads whole 1 KiB runs)
     return jump ? (size_t)ga::RC_CACHE_I * ga::RC_CACHE_S * 4 * TD * 6144 + 65536
                 : (size_t)ga::RC_CACHE_I * ga::RC_CACHE_S * TD * 64 * 64 * CB + (size_t)64 * 64 * 4 * 4;
 }
-// whether the tie-to-tie walk may run (experiments build, GA_RC_JUMP): the checkpoint sizing then budgets its cache
-inline bool rc_jump_requested(const ga_ctx* c) {
+
+// ---------------------------------------------------------------- the planner's inputs (ga_plan.h)
+const gaplan::LdsSizes kLdsSizes{ga::fill_lane_lds_bytes, ga::rc_worker_bytes, rc_cache_bytes};
+
+// The knobs the fill's plan depends on, as numbers: parsed here, once per context, and nowhere else.
+gaplan::Knobs plan_knobs(const ga_ctx* c) {
+    gaplan::Knobs kn;
+    if (const char* e = c->knob("GA_COLS_PER_LANE")) kn.T_req = atoi(e);  // tuning overrides
+    if (const char* e = c->knob("GA_FILL_NWC")) kn.nwc_req = atoi(e);
+    if (const char* e = c->knob("GA_FILL_MODE"))
+        kn.diag_req = !strcmp(e, "diag") ? 2 : !strcmp(e, "row") ? 1 : !strcmp(e, "lane") ? 3 : 0;
+    if (const char* e = c->knob("GA_LANE_COLS_PER_LANE")) kn.lane_T_req = atoi(e);
+    if (const char* e = c->knob("GA_DIAG_COLS_PER_LANE")) kn.diag_T_req = atoi(e);
+    if (const char* e = c->knob("GA_LANE_WG_PER_CU")) kn.lane_wg_per_cu = std::max(1, std::min(2, atoi(e)));
+    if (const char* e = c->knob("GA_LANE_QROWS")) kn.lane_qrows = atoi(e);
+    if (const char* e = c->knob("GA_RC_NARROW")) kn.rc_narrow = atoi(e) != 0;
+    if (const char* e = c->knob("GA_RC_BUDGET_MB")) kn.rc_budget = atoll(e) << 20;
 #ifdef GA_EXPERIMENTS
+    // whether the tie-to-tie walk may run (GA_RC_JUMP): the checkpoint sizing then budgets its cache
     const char* e = c->xknob("GA_RC_JUMP");
-    return e ? atoi(e) != 0 : kRcJumpDefault;
-#else
-    (void)c;
-    return false;
+    kn.rc_jump = e ? atoi(e) != 0 : kRcJumpDefault;
 #endif
+    return kn;
 }
 
-int enqueue_fill(ga_ctx* c, int32_t flags, const Band& bd = Band()) {
-    int every = bd.rc_every > 0 ? bd.rc_every : 64;  // the recompute fill's checkpoint spacing (chosen below)
-    if (!c->loaded) return fail(GA_E_STATE, "no problem loaded");
-    const bool tb = (flags & (GA_FILL_TRACEBACK | GA_FILL_FULL)) != 0;
-    const bool full = (flags & GA_FILL_FULL) != 0;
-    const int64_t m = bd.band ? bd.mb : c->m, n = bd.band && bd.nc > 0 ? bd.nc : c->n;
-    // 16-row chunks; CB 16-byte words per lane per chunk (ga_device.h)
-    c->TC = (int)((m + ga::FROWS - 1) / ga::FROWS) * c->CB;
-    // score only: the anti-diagonal kernel (64-column stripes) when asked for and its profile
-    // ring is deep enough for a workgroup's skew (8 waves x 64 steps)
-    // (its query-profile ring deeper than a workgroup's skew: NWC stripes x 64*TD steps)
-    int qrows = c->qrows;
-    c->diag = false;
-    c->lane = false;
-    // score only: the lane-skewed kernel when its chain's skew (~74 steps per stripe)
-    // is short against the m rows every stripe walks (measured: 1M x 125k 60 ms against 107 for the row
-    // scan, C4 244 against 312; 100k x 100k, whose 782 stripes add 58k steps of skew, 13.5 against 12.6)
-    if (bd.rc) {
-        if (tb || full || !lane_geometry(c, n, &qrows, false)) return fail(GA_E_STATE, "recompute fill needs the lane kernel");
-        // the checkpointing variant runs 16-step sub-chunks (8 waves at TD = 8 would take 8-step ones)
-        if (c->nwc == 8 && c->T == 8 && !lane_geometry(c, n, &qrows, false, 8, 4)) return fail(GA_E_STATE, "recompute fill geometry");
-        // the recompute workers stage a block's codes in LDS (64*TD columns x the checkpoint spacing): at
-        // wide stripes and wide spacings (C4: TD 8, every 256 steps, 219 KB) that exceeds the CU's LDS, so
-        // the stripes narrow until a worker fits beside the walk's 128 KB torus budget
-        constexpr int kRcLds = 256 * 256 * 2;  // the walk's torus (ga_walk.h TP x TP u16): the launch's dynamic LDS
-        // Stripes of at most 4 columns per lane (unless GA_LANE_COLS_PER_LANE asks): a block is 64 rows of one stripe, and the walk reads ~1-2 of
-        // its TD tiles, so wider blocks starve the walk (C4 on one GPU at TD 8: fill 226 ms, walk 160 ms;
-        // at TD 4: 284 + 90 ms, tools/exp/r3b_c4tb3.sh, r3b_c4rc.py)
-        // and 4 where the geometry model chose fewer (round 4, the lean sub-chunk): fewer, wider stripes shorten
-        // the ramp as much as their slower step lengthens the rows, and the walk's blocks come cheaper (C3: fill
-        // 9.69 -> 9.81 ms, walk 5.72 -> 5.42; C5 3.92 against 6.3 ms at TD = 1; tools/r4_td.sh).
-        // Round 6: with the lean ramp (the first 64 steps no longer masked) and the cone-shaped recompute window
-        // below, 2 columns per lane win for small alphabets whose stripes all run at once (one workgroup of four per
-        // CU): C3 fill 7.61 -> 6.83 ms, walk 5.18 -> 5.03 (cone 2; 5.65 with the round-5 window), call 12.98 ->
-        // 12.09; C2 1.42 -> 1.30.  The protein fill does not (C5 at TD 2: fill 1.73 -> 1.91 ms), so K > 8 keeps 4
-        // (tools/exp/r6/check5.sh, check6.sh, rc_diag.py).  The default under those conditions:
-        // GA_RC_NARROW=0 restores 4 columns per lane for an A/B run, =1 and unset both mean 2; slabs, K > 8 and
-        // problems with more 128-column stripes than SIMDs (C4) keep 4; GA_LANE_COLS_PER_LANE overrides both.
-        if (!c->lane_T_req) {
-            const char* nw = c->knob("GA_RC_NARROW");
-            const bool td2 = (!nw || atoi(nw)) && !c->slab && c->K <= 8 && (n + 127) / 128 <= 4 * (int64_t)c->num_cu;
-            if (td2 && lane_geometry(c, n, &qrows, false, 2, 4)) {
-            } else if (c->T > 4) {
-                if (!lane_geometry(c, n, &qrows, false, 4, 4)) return fail(GA_E_STATE, "recompute fill geometry");
-            } else if (c->T < 4) {
-                (void)lane_geometry(c, n, &qrows, false, 4, 4);
-            }
-        }
-        // The checkpoint spacing, with the stripes' geometry known: the smallest (<= 4096 steps) whose states
-        // fit the memory budget (default 96 GB of the 288: C4 on one GPU, TD 4, takes 128 steps, 78 GB; 64
-        // would take 156 GB and walks no faster) and whose worker fits LDS; GA_RC_EVERY fixes it (the stripes
-        // narrow if it must)
-        // The budget is also capped by the device memory free for it: what hipMemGetInfo reports plus
-        // what this context's checkpoint buffers already hold, less the right-edge columns (8 B per row per
-        // stripe), the walk's tile cache and a 2 GB margin.  A problem whose checkpoints still do not fit returns
-        // GA_E_NOMEM, and ga_problem_align takes the banded traceback instead.
-        int64_t budget = (int64_t)96 << 30;
-        if (const char* e = c->knob("GA_RC_BUDGET_MB")) budget = atoll(e) << 20;
-        const int64_t dev_avail = dev_avail_bytes(c, (int64_t)c->stck.cap + (int64_t)c->colck.cap + (int64_t)c->rc_tb.cap);
-        auto ck_bytes = [&](int e) {
-            const int64_t nck = std::max<int64_t>((m - 1) / e, 1);
-            return nck * c->nstripes * (c->T + 1) * 512;
-        };
-        // (the walk's block cache as the walk that will run sizes it: ADVICE r5, the jump cache is ~6x the word one)
-        auto other_bytes = [&]() {
-            return (int64_t)c->nstripes * (m + 1) * 8 +
-                   (int64_t)rc_cache_bytes(rc_jump_requested(c) && c->T <= 4, c->T, c->CB) +
-                   ((int64_t)64 << 20);
-        };
-        auto fits = [&](int e) {
-            return ck_bytes(e) <= std::min(budget, dev_avail - other_bytes()) &&
-                   1024 + ga::rc_worker_bytes(c->T, c->CB, e) <= kRcLds;
-        };
-        for (;;) {
-            if (bd.rc_every > 0) every = bd.rc_every;
-            else
-                for (every = 64; every < 4096 && !fits(every); every *= 2) {}
-            if (1024 + ga::rc_worker_bytes(c->T, c->CB, every) <= kRcLds) break;
-            if (c->T == 1) {
-                // no spacing fits both: memory if the densest one fits LDS, else LDS
-                if (1024 + ga::rc_worker_bytes(1, c->CB, 64) <= kRcLds)
-                    return fail(GA_E_NOMEM, "recompute walk: the checkpoints do not fit the budget / free device memory");
-                return fail(GA_E_RANGE, "recompute walk: a block's codes do not fit LDS");
-            }
-            if (!lane_geometry(c, n, &qrows, false, c->T / 2, 4)) return fail(GA_E_STATE, "recompute fill geometry");
-        }
-        if (ck_bytes(every) > std::min(budget, dev_avail - other_bytes()))
-            return fail(GA_E_NOMEM, "recompute walk: the checkpoints do not fit the budget / free device memory");
-        c->rc_every_used = every;
-        c->lane = true;
-    } else if (bd.lane_td > 0 && tb && !full && bd.ckpt == nullptr)
-        c->lane = lane_geometry(c, n, &qrows, tb, bd.lane_td, bd.lane_nwc, 2048);
-    else if (!full && (bd.ckpt == nullptr || !tb) && (c->diag_req == 3 || (c->diag_req == 0 && !tb)) &&
-             lane_geometry(c, n, &qrows, tb) && (c->diag_req == 3 || 4 * 74 * (int64_t)c->nstripes <= m))
-        c->lane = true;
-    // automatic: score-only fills of tall problems on one GPU (m >= 4 n, <= 8 stripes per CU).
-    // Measured (profiles/r01/diag_sweep.txt): 1M x 125k 80 ms (TD = 1) against 107 ms for the row
-    // scan, 1M x 250k 126 ms (TD = 2) against 141 ms; the row scan wins on square shapes (C4 313 ms
-    // against 400 ms), where the anti-diagonal skew of 64 steps per stripe costs more.  Not for a
-    // slab of a multi-GPU fill: there the next rank starts when this one's last stripe does, and
-    // that start (the ramp) is ~15 ms for the anti-diagonal fill against ~3 ms for the row scan.
-    const int auto_td = (n + 63) / 64 <= 8 * (int64_t)c->num_cu ? 1 : 2;
-    const bool auto_diag = c->diag_req == 0 && !tb && !bd.band && !c->slab && m >= 4 * n &&
-                           (n + 64 * auto_td - 1) / (64 * auto_td) <= 8 * (int64_t)c->num_cu;
-    if (!c->lane && (!tb || (full && c->qbytes == 1)) && (c->diag_req == 2 || auto_diag) && bd.ckpt == nullptr) {
-        int td = full ? std::min(std::max(c->diag_T_req, 1), 2)
-                      : c->diag_T_req == 1 || c->diag_T_req == 2 || c->diag_T_req == 4 ? c->diag_T_req
-                      : auto_diag ? auto_td : 1;
-        if (c->qbytes == 2) td = std::min(td, 2);  // int16 profiles at TD = 4 spill
-        set_stripes(c, td, false, false, n);
-        if (full) {  // the debug FULL variant is built for 4 compute waves
-            c->nwc = 4;
-            c->nslabs = (c->nstripes + 3) / 4;
-        }
-        qrows = 8192;
-        while (qrows > 128 && (size_t)c->K * (qrows + 16) * c->qbytes > 64 * 1024) qrows >>= 1;
-        c->diag = qrows >= c->nwc * (64 * c->T + 16) + 64 * c->T + 64;
-    }
-    if (!c->diag && !c->lane) {
-        qrows = c->qrows;
-        set_stripes(c, c->T_req, tb, full, n);
-    }
+// ---------------------------------------------------------------- one fill: plan, buffers, arguments, launch
+// What the four stages of enqueue_fill share: the request, its plan, and where this fill reads and writes.
+struct FillJob {
+    const Band& bd;
+    gaplan::FillPlan pl;
+    FillBufs& fb;
+    hipStream_t st;
+    bool tb, full;
+    int64_t m, n;  // the rows and columns this fill covers (a band's, else the problem's)
+    bool lane() const { return pl.kind == gaplan::kLane; }
+};
+
+// 1. The plan (ga_plan.h).  An error returns before anything is enqueued.
+int fill_plan(ga_ctx* c, const Band& bd, bool tb, bool full, gaplan::FillPlan& pl) {
+    gaplan::Request rq = bd;
+    rq.tb = tb;
+    rq.full = full;
+    rq.has_ckpt = bd.ckpt != nullptr;
+    gaplan::Knobs kn = c->pk;
+    // what the checkpoints may take: the free device memory plus what this context's checkpoint buffers already hold
+    if (bd.rc) kn.dev_avail = dev_avail_bytes(c, (int64_t)c->stck.cap + (int64_t)c->colck.cap + (int64_t)c->rc_tb.cap);
+    pl = gaplan::plan_fill(plan_problem(c), rq, kn, kLdsSizes);
+    return pl.err ? fail(pl.err, pl.msg) : GA_OK;
+}
+
+// 2. The buffers at the plan's sizes, and their presets on the fill's stream.
+int fill_buffers(ga_ctx* c, const FillJob& j) {
+    const gaplan::FillPlan& pl = j.pl;
+    const int64_t m = j.m, n = j.n;
+    HIPCHK(j.fb.out_last.ensure(sizeof(int) * 4));
     // traceback words cover T 64-column stripes per fill stripe
-    DevBuf& tbb = bd.tbuf ? *bd.tbuf : c->tb;
-    DevBuf& hb = bd.hbuf ? *bd.hbuf : c->hand;
-    DevBuf& fb = bd.fbuf ? *bd.fbuf : c->flags;
-    DevBuf& ob = bd.obuf ? *bd.obuf : c->out_last;
-    hipStream_t st = bd.stream ? bd.stream : c->stream;
-    HIPCHK(ob.ensure(sizeof(int) * 4));
-    if (tb) HIPCHK(tbb.ensure((size_t)c->nstripes * c->T * c->TC * 1024));
-    HIPCHK(hb.ensure(sizeof(int2) * (size_t)c->nslabs * (m + 1)));
+    if (j.tb) HIPCHK(j.fb.tb.ensure((size_t)pl.nstripes * pl.T * pl.TC * 1024));
+    HIPCHK(j.fb.hand.ensure(sizeof(int2) * (size_t)pl.nslabs * (m + 1)));
     // workgroup hand-off rows read by a successor start as ga::HAND_SENT (bytes 0x80)
-    if (c->nslabs > 1)
-        HIPCHK(hipMemsetAsync(hb.p, 0x80, sizeof(int2) * (size_t)(c->nslabs - 1) * (m + 1), st));
-    HIPCHK(fb.ensure(sizeof(unsigned) * 16));
-    if (full) {
-        if ((m + 1) * (n + 1) > (int64_t)64 << 20) return fail(GA_E_RANGE, "GA_FILL_FULL is for small problems");
-        HIPCHK(c->full.ensure(sizeof(int) * 3 * (m + 1) * (n + 1)));
-    }
-    unsigned* fl = fb.as<unsigned>();
+    if (pl.nslabs > 1)
+        HIPCHK(hipMemsetAsync(j.fb.hand.p, 0x80, sizeof(int2) * (size_t)(pl.nslabs - 1) * (m + 1), j.st));
+    HIPCHK(j.fb.flags.ensure(sizeof(unsigned) * 16));
+    if (j.full) HIPCHK(c->full.ensure(sizeof(int) * 3 * (m + 1) * (n + 1)));
     // flags layout: [0] ticket, [1] abort
-    HIPCHK(hipMemsetAsync(fl, 0, sizeof(unsigned) * 16, st));
-    DevBuf& bGVp = bd.GVp ? *bd.GVp : c->GVp;
-    DevBuf& bGHp = bd.GHp ? *bd.GHp : c->GHp;
-    DevBuf& btop = bd.top_b ? *bd.top_b : c->top;
-    DevBuf& bleft = bd.left ? *bd.left : c->left;
-    DevBuf& brow = bd.bnd_row ? *bd.bnd_row : c->bnd_row;
-    DevBuf& bcol = bd.bnd_col ? *bd.bnd_col : c->bnd_col;
-    DevBuf& bmeta = bd.meta ? *bd.meta : c->meta;
-    DevBuf& bscr = bd.bscr ? *bd.bscr : c->bscr;
-    if (!bd.band && !bd.skip_boundary)
-        ga::launch_boundary(st, c->a.as<uint8_t>(), (int)m, c->b.as<uint8_t>(), (int)c->n_global,
-                            c->gh.as<int>(), c->gv.as<int>(), c->o, c->big, bGVp.as<int>(), bGHp.as<int>(),
-                            btop.as<int2>(), bleft.as<int2>(), brow.as<int>(), bcol.as<int>(),
-                            bmeta.as<int>(), c->custom, bscr.as<int>());
-    ga::FillArgs p{};
-    p.a = c->a.as<uint8_t>() + bd.r0;
-    p.ckpt = bd.ckpt;
-    p.ckpt_rows = bd.ckpt_rows;
-    p.colck = nullptr;
-    p.stck = nullptr;
-    // one round of lane workgroups (every stripe resident): the chain's lag counts, read edges late
-    p.late = c->lane && c->nslabs <= c->num_cu ? 1 : 0;
-    if (const char* e = c->knob("GA_LANE_LATE")) p.late = atoi(e);
-    // chain neighbours on one XCD (ga_lane.hip lane_slab; experiments build only): measured no faster, since ticket
-    // order already keeps 165 of C3's 195 cross-workgroup links on one XCD (r5: 188 with the map; C3 fill 9.43 ->
-    // 9.46 ms, tools/exp/r5/xcd.sh).  Only for one round of workgroups that runs alone (a pipeline's fills share
-    // the device; a fill that finds its workgroups not all resident falls back to ticket order after ~40 us)
-    p.xcd_map = 0;
-    if (const char* e = c->xknob("GA_LANE_XCD")) p.xcd_map = c->lane && c->nslabs <= c->num_cu && bd.stream == nullptr ? atoi(e) : 0;
-    p.hand_direct = 0;  // measured: C4 210 ms against 221 with the direct hand-off, 1M x 125k 52.5 against 56 (r3_c4.log)
-    if (const char* e = c->knob("GA_LANE_DIRECT")) p.hand_direct = atoi(e);
-    p.stck_every = every;
-    p.stck_shift = 0;
-    while ((1 << p.stck_shift) < every) p.stck_shift++;
-    {
-        const char* e = c->knob("GA_FILL_LDS_FLOOR");
-        p.lds_floor = e ? atoi(e) : -1;
-        e = c->knob("GA_LANE_SUB");
-        p.lane_sub = e ? atoi(e) : -1;
-        e = c->knob("GA_LANE_TB_SUB");
-        p.lane_tb_sub = e ? atoi(e) : -1;
-        e = c->knob("GA_LANE_ASM");
-        p.asm_step = e ? atoi(e) : 1;
-        e = c->xknob("GA_LANE_IOPRIO");
-        p.io_prio = e ? atoi(e) : 0;
-        e = c->xknob("GA_LANE_HANDSCOPE");
-        p.hand_scope = e ? atoi(e) : 0;
-        e = c->knob("GA_LANE_POLLWIN");
-        p.poll_win = e ? std::min(std::max(atoi(e), 0), 192) : 0;
-        e = c->knob("GA_LANE_OUTWAVE");
-        p.out_wave = e ? atoi(e) : 1;
-    }
-    if (bd.rc) {
-        const int64_t nck = std::max<int64_t>((m - 1) / every, 1);
-        // An allocation that fails (the size check above passed, but the device's free memory moved) releases every
+    HIPCHK(hipMemsetAsync(j.fb.flags.p, 0, sizeof(unsigned) * 16, j.st));
+    if (j.bd.rc) {
+        const int64_t nck = std::max<int64_t>((m - 1) / pl.rc_every, 1);
+        // An allocation that fails (the plan's size check passed, but the device's free memory moved) releases every
         // recompute buffer before GA_E_NOMEM, so the fallback (ga_problem_align: banded / stored words) sizes
-        // itself with that memory free.  The boundary pass and the memsets enqueued above are harmless: the
-        // fallback's own fill enqueues them again behind them on the same stream.  GA_RC_FAIL_ALLOC=1 (tests)
-        // fails the second allocation after the first succeeded.
+        // itself with that memory free.  The memsets enqueued above are harmless: the fallback's own fill
+        // enqueues them again behind them on the same stream.  GA_RC_FAIL_ALLOC=1 (tests) fails the second
+        // allocation after the first succeeded.
         const bool fail_test = c->knob("GA_RC_FAIL_ALLOC") && atoi(c->knob("GA_RC_FAIL_ALLOC")) == 1;
         int nb = 0;
-        for (auto [buf, bytes] : {std::pair<DevBuf*, size_t>{&c->colck, sizeof(int2) * (size_t)c->nstripes * (m + 1 + ga::COLCK_PAD)},
-                                  {&c->stck, sizeof(int2) * (size_t)nck * c->nstripes * (c->T + 1) * 64}}) {
+        for (auto [buf, bytes] : {std::pair<DevBuf*, size_t>{&c->colck, sizeof(int2) * (size_t)pl.nstripes * (m + 1 + ga::COLCK_PAD)},
+                                  {&c->stck, sizeof(int2) * (size_t)nck * pl.nstripes * (pl.T + 1) * 64}}) {
             hipError_t e = buf->ensure(bytes);
             if (e == hipSuccess && fail_test && nb == 1) e = hipErrorOutOfMemory;
             nb++;
@@ -748,67 +518,131 @@ int enqueue_fill(ga_ctx* c, int32_t flags, const Band& bd = Band()) {
                             std::string("recompute checkpoints: ") + hipGetErrorString(e));
             }
         }
-        p.colck = c->colck.as<int2>();
-        p.stck = c->stck.as<int2>();
     }
-    p.subp = c->qp.as<int>();
-    p.K = c->K;
-    p.b = c->b.as<uint8_t>() + c->col0;
-    p.top = (bd.top ? bd.top : btop.as<int2>()) + c->col0;
-    if (c->slab && c->col0 > 0) {
-        p.left = c->halo_in_ext ? c->halo_in_ext : c->halo_in.as<int2>();
-        p.left_prog = c->in_prog_ext ? c->in_prog_ext : c->prog.dev<uint32_t>();  // [0]: halo_in rows
-    } else {
-        p.left = bleft.as<int2>() + bd.r0;
-        p.left_prog = nullptr;
+    if (c->dbg_on) {
+        HIPCHK(c->dbg.ensure(sizeof(unsigned long long) * ga::LK_DBG_WORDS * pl.nstripes));
+        HIPCHK(hipMemsetAsync(c->dbg.p, 0, sizeof(unsigned long long) * ga::LK_DBG_WORDS * pl.nstripes, j.st));
     }
-    p.hand = hb.as<int2>();
-    p.ticket = fl;
-    p.abort_word = fl + 1;
-    p.tb = tb ? tbb.as<uint8_t>() : nullptr;
-    p.out_last = ob.as<int>();
-    p.edge_prog = c->slab ? (c->out_prog_ext ? c->out_prog_ext : c->prog.dev<uint32_t>() + 1) : nullptr;  // [1]: halo_out rows
-    p.edge_out = c->slab ? c->halo_out_ext : nullptr;
-    p.full = full ? c->full.as<int>() : nullptr;
-    p.m = (int)m;
-    p.n = (int)n;
-    p.o = c->o;
-    p.nstripes = c->nstripes;
-    p.nslabs = c->nslabs;
-    p.TC = c->TC;
-    p.nwc = c->nwc;
-    p.qrows = qrows;
-    p.cols_per_lane = c->T;
+    // the lane fill's query profile (K x (m + 4) dwords: C5 1.9 MB)
+    if (j.lane() && !c->xknob("GA_LANE_QPROF_WAVE"))  // (experiments build: the profile wave builds it, for A/B)
+        HIPCHK(c->qprof.ensure(sizeof(uint32_t) * (size_t)c->K * (size_t)(m + 4)));
+    return GA_OK;
+}
+
+// The launch-time knobs of the lane kernel (tuning, A/B runs and tests: none changes the plan).
+void fill_launch_knobs(const ga_ctx* c, const FillJob& j, ga::FillArgs& p) {
+    const bool one_round = j.lane() && j.pl.nslabs <= c->num_cu;
+    auto num = [](const char* e, int unset) { return e ? atoi(e) : unset; };
+    // one round of lane workgroups (every stripe resident): the chain's lag counts, read edges late
+    p.late = num(c->knob("GA_LANE_LATE"), one_round ? 1 : 0);
+    // chain neighbours on one XCD (ga_lane.hip lane_slab; experiments build only): measured no faster, since ticket
+    // order already keeps 165 of C3's 195 cross-workgroup links on one XCD (r5: 188 with the map; C3 fill 9.43 ->
+    // 9.46 ms, tools/exp/r5/xcd.sh).  Only for one round of workgroups that runs alone (a pipeline's fills share
+    // the device; a fill that finds its workgroups not all resident falls back to ticket order after ~40 us)
+    p.xcd_map = one_round && j.bd.stream == nullptr ? num(c->xknob("GA_LANE_XCD"), 0) : 0;
+    // measured: C4 210 ms against 221 with the direct hand-off, 1M x 125k 52.5 against 56 (r3_c4.log)
+    p.hand_direct = num(c->knob("GA_LANE_DIRECT"), 0);
+    p.lds_floor = num(c->knob("GA_FILL_LDS_FLOOR"), -1);
+    p.lane_sub = num(c->knob("GA_LANE_SUB"), -1);
+    p.lane_tb_sub = num(c->knob("GA_LANE_TB_SUB"), -1);
+    p.asm_step = num(c->knob("GA_LANE_ASM"), 1);
+    p.io_prio = num(c->xknob("GA_LANE_IOPRIO"), 0);
+    p.hand_scope = num(c->xknob("GA_LANE_HANDSCOPE"), 0);
+    p.poll_win = std::min(std::max(num(c->knob("GA_LANE_POLLWIN"), 0), 0), 192);
+    p.out_wave = num(c->knob("GA_LANE_OUTWAVE"), 1);
     p.spin_limit = 1u << 26;        // ~seconds: only a broken hand-off can reach it
     p.halo_spin_limit = 1u << 30;  // waiting on another GPU may take long (~30 s)
     if (const char* e = c->knob("GA_HALO_SPIN_LIMIT")) p.halo_spin_limit = (unsigned)std::max(1L, atol(e));  // (tests)
     // a slab with a left neighbour: every wait of its fill is, in the end, a wait for that halo
     if (c->slab && c->col0 > 0) p.spin_limit = std::max(p.spin_limit, p.halo_spin_limit);
-    if (c->dbg_on) HIPCHK(c->dbg.ensure(sizeof(unsigned long long) * ga::LK_DBG_WORDS * c->nstripes));
-    if (c->dbg_on) HIPCHK(hipMemsetAsync(c->dbg.p, 0, sizeof(unsigned long long) * ga::LK_DBG_WORDS * c->nstripes, st));
-    p.dbg = c->dbg_on ? c->dbg.as<unsigned long long>() : nullptr;
-    // the lane fill's query profile, built on the fill's stream just before it (K x (m + 4) dwords: C5 1.9 MB, a few us).
-    // Fills of one problem in flight on other streams (align_many) rewrite it with the same values.
     // the lean ramp (ga_lane.hip lean0): row 0 is the reference's boundary and uniform in the shifted domain (H' = o,
     // h2' = 2o in every column: 2o + GH(j) <= big for every j, so for the largest prefix sum, which is GH(n) only
     // when no gap cost is negative); GA_LANE_LEAN0=0 keeps the masked ramp (A/B)
-    {
-        const char* e = c->knob("GA_LANE_LEAN0");
-        p.lean0 = (e ? atoi(e) : 1) && c->lane && !c->custom && bd.top == nullptr && !bd.band &&
-                  2 * (int64_t)c->o + c->gh_max <= (int64_t)c->big;
+    p.lean0 = num(c->knob("GA_LANE_LEAN0"), 1) && j.lane() && !c->custom && j.bd.top == nullptr && !j.bd.band &&
+              2 * (int64_t)c->o + c->gh_max <= (int64_t)c->big;
+}
+
+// 3. The kernels' arguments.
+ga::FillArgs fill_args(const ga_ctx* c, const FillJob& j) {
+    const gaplan::FillPlan& pl = j.pl;
+    const Band& bd = j.bd;
+    ga::FillArgs p{};
+    p.a = c->a.as<uint8_t>() + bd.r0;
+    p.ckpt = bd.ckpt;
+    p.ckpt_rows = bd.ckpt_rows;
+    p.colck = bd.rc ? c->colck.as<int2>() : nullptr;
+    p.stck = bd.rc ? c->stck.as<int2>() : nullptr;
+    p.stck_every = pl.rc_every;
+    p.stck_shift = 0;
+    while ((1 << p.stck_shift) < pl.rc_every) p.stck_shift++;
+    fill_launch_knobs(c, j, p);
+    p.subp = c->qp.as<int>();
+    p.K = c->K;
+    p.b = c->b.as<uint8_t>() + c->col0;
+    p.top = (bd.top ? bd.top : j.fb.top.as<int2>()) + c->col0;
+    if (c->slab && c->col0 > 0) {
+        p.left = c->halo_in_ext ? c->halo_in_ext : c->halo_in.as<int2>();
+        p.left_prog = c->in_prog_ext ? c->in_prog_ext : c->prog.dev<uint32_t>();  // [0]: halo_in rows
+    } else {
+        p.left = j.fb.left.as<int2>() + bd.r0;
+        p.left_prog = nullptr;
     }
-    p.qprof = nullptr;
-    if (c->lane && !c->xknob("GA_LANE_QPROF_WAVE")) {  // (experiments build: the profile wave builds it, for A/B)
-        HIPCHK(c->qprof.ensure(sizeof(uint32_t) * (size_t)c->K * (size_t)(m + 4)));
-        ga::launch_lane_qprof(st, p.a, (int)m, p.subp, c->K, c->qprof.as<uint32_t>());
-        p.qprof = c->qprof.as<uint32_t>();
-    }
-    HIPCHK(hipEventRecord(bd.ev0 ? bd.ev0 : c->ev[0], st));
-    if (c->lane) ga::launch_fill_lane(st, p, c->CB);
-    else if (c->diag) ga::launch_fill_diag(st, p, c->qbytes, full);
-    else ga::launch_fill(st, p, c->CB, c->qbytes, tb, full);
+    p.hand = j.fb.hand.as<int2>();
+    p.ticket = j.fb.flags.as<unsigned>();
+    p.abort_word = p.ticket + 1;
+    p.tb = j.tb ? j.fb.tb.as<uint8_t>() : nullptr;
+    p.out_last = j.fb.out_last.as<int>();
+    p.edge_prog = c->slab ? (c->out_prog_ext ? c->out_prog_ext : c->prog.dev<uint32_t>() + 1) : nullptr;  // [1]: halo_out rows
+    p.edge_out = c->slab ? c->halo_out_ext : nullptr;
+    p.full = j.full ? c->full.as<int>() : nullptr;
+    p.m = (int)j.m;
+    p.n = (int)j.n;
+    p.o = c->o;
+    p.nstripes = pl.nstripes;
+    p.nslabs = pl.nslabs;
+    p.TC = pl.TC;
+    p.nwc = pl.nwc;
+    p.qrows = pl.qrows;
+    p.cols_per_lane = pl.T;
+    p.dbg = c->dbg_on ? c->dbg.as<unsigned long long>() : nullptr;
+    p.qprof = j.lane() && !c->xknob("GA_LANE_QPROF_WAVE") ? c->qprof.as<uint32_t>() : nullptr;
+    return p;
+}
+
+// 4. The launches: the boundary pass, the lane fill's query profile, the fill between its two timing events.
+int fill_launch(ga_ctx* c, const FillJob& j, const ga::FillArgs& p) {
+    FillBufs& fb = j.fb;
+    if (!j.bd.band)
+        ga::launch_boundary(j.st, c->a.as<uint8_t>(), (int)j.m, c->b.as<uint8_t>(), (int)c->n_global,
+                            c->gh.as<int>(), c->gv.as<int>(), c->o, c->big, fb.GVp.as<int>(), fb.GHp.as<int>(),
+                            fb.top.as<int2>(), fb.left.as<int2>(), fb.bnd_row.as<int>(), fb.bnd_col.as<int>(),
+                            fb.meta.as<int>(), c->custom, fb.bscr.as<int>());
+    // the query profile is built on the fill's stream just before it (a few us).  Fills of one problem in flight on
+    // other streams (align_many) rewrite it with the same values.
+    if (p.qprof) ga::launch_lane_qprof(j.st, p.a, (int)j.m, p.subp, c->K, c->qprof.as<uint32_t>());
+    HIPCHK(hipEventRecord(fb.ev[0], j.st));
+    if (j.lane()) ga::launch_fill_lane(j.st, p, c->CB);
+    else if (j.pl.kind == gaplan::kDiag) ga::launch_fill_diag(j.st, p, c->qbytes, j.full);
+    else ga::launch_fill(j.st, p, c->CB, c->qbytes, j.tb, j.full);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(bd.ev1 ? bd.ev1 : c->ev[1], st));
+    HIPCHK(hipEventRecord(fb.ev[1], j.st));
+    return GA_OK;
+}
+
+// Enqueue boundary + query profile + fill.  Does not synchronise.  The plan it used becomes the context's
+// (ga_ctx::plan) and goes to plan_out.
+int enqueue_fill(ga_ctx* c, int32_t flags, const Band& bd = Band(), gaplan::FillPlan* plan_out = nullptr) {
+    if (!c->loaded) return fail(GA_E_STATE, "no problem loaded");
+    const bool tb = (flags & (GA_FILL_TRACEBACK | GA_FILL_FULL)) != 0;
+    const bool full = (flags & GA_FILL_FULL) != 0;
+    gaplan::FillPlan pl;
+    if (int r = fill_plan(c, bd, tb, full, pl)) return r;
+    c->plan = pl;
+    if (plan_out) *plan_out = pl;
+    const FillJob j{bd, pl, bd.bufs ? *bd.bufs : c->fb, bd.stream ? bd.stream : c->stream, tb, full,
+                    bd.band ? bd.mb : c->m, bd.band && bd.nc > 0 ? bd.nc : c->n};
+    if (int r = fill_buffers(c, j)) return r;
+    if (int r = fill_launch(c, j, fill_args(c, j))) return r;
     c->filled_tb = tb;
     return GA_OK;
 }
@@ -816,30 +650,30 @@ int enqueue_fill(ga_ctx* c, int32_t flags, const Band& bd = Band()) {
 int finish_fill(ga_ctx* c, int64_t* cost_out, int32_t* full_out) {
     int last[4] = {0, 0, 0, 0}, meta[2] = {0, 0};
     unsigned abort_word = 0;
-    HIPCHK(hipMemcpyAsync(last, c->out_last.p, sizeof(int) * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(meta, c->meta.p, sizeof(int) * 2, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&abort_word, c->flags.as<unsigned>() + 1, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(last, c->fb.out_last.p, sizeof(int) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(meta, c->fb.meta.p, sizeof(int) * 2, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&abort_word, c->fb.flags.as<unsigned>() + 1, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipEventElapsedTime(&c->fill_ms, c->ev[0], c->ev[1]));
+    HIPCHK(hipEventElapsedTime(&c->fill_ms, c->fb.ev[0], c->fb.ev[1]));
     if (abort_word) return fail(GA_E_TIMEOUT, "fill kernel hand-off wait timed out");
     c->GV_m = meta[0];
     // un-shift: cost = H'(m, n) + GV(m) + GH(column)
     int64_t gh_end = 0;
     {
         int v = 0;
-        HIPCHK(hipMemcpy(&v, c->GHp.as<int>() + c->col0 + c->n, sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&v, c->fb.GHp.as<int>() + c->col0 + c->n, sizeof(int), hipMemcpyDeviceToHost));
         gh_end = v;
     }
     if (cost_out) *cost_out = (int64_t)last[0] + c->GV_m + gh_end;
     if (full_out) {
         const int64_t m = c->m, n = c->n, W = n + 1;
         std::vector<int> GV(m + 1), GH(n + 1);
-        HIPCHK(hipMemcpy(GV.data(), c->GVp.p, sizeof(int) * (m + 1), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(GH.data(), c->GHp.p, sizeof(int) * (n + 1), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(GV.data(), c->fb.GVp.p, sizeof(int) * (m + 1), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(GH.data(), c->fb.GHp.p, sizeof(int) * (n + 1), hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(full_out, c->full.p, sizeof(int) * 3 * (m + 1) * W, hipMemcpyDeviceToHost));
         std::vector<int> br(3 * (n + 1)), bc(3 * (m + 1));
-        HIPCHK(hipMemcpy(br.data(), c->bnd_row.p, sizeof(int) * br.size(), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(bc.data(), c->bnd_col.p, sizeof(int) * bc.size(), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(br.data(), c->fb.bnd_row.p, sizeof(int) * br.size(), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(bc.data(), c->fb.bnd_col.p, sizeof(int) * bc.size(), hipMemcpyDeviceToHost));
         for (int64_t i = 0; i <= m; i++)
             for (int64_t j = 0; j <= n; j++) {
                 int* f = full_out + 3 * (i * W + j);
@@ -877,8 +711,8 @@ struct WalkBufs {
     unsigned* ops_prog = nullptr;  // WalkArgs::ops_prog (ops then in pinned host memory)
 };
 WalkBufs ctx_walk_bufs(ga_ctx* c) {
-    return WalkBufs{c->tb.as<uint8_t>(), c->rng.as<uint32_t>(), c->ops.as<uint32_t>(), c->result.as<int>(), c->stream,
-                    c->ev[2], c->ev[3]};
+    return WalkBufs{c->fb.tb.as<uint8_t>(), c->rng.as<uint32_t>(), c->ops.as<uint32_t>(), c->result.as<int>(), c->stream,
+                    c->wev[0], c->wev[1]};
 }
 
 ga::WalkArgs walk_args(ga_ctx* c, int64_t ntab, const WalkStart& st, int64_t r0, int64_t mb, bool vhandoff,
@@ -886,11 +720,11 @@ ga::WalkArgs walk_args(ga_ctx* c, int64_t ntab, const WalkStart& st, int64_t r0,
     ga::WalkArgs w{};
     w.tb = wb.tb;
     w.CB = c->CB;
-    w.TC = c->TC;
+    w.TC = c->plan.TC;
     w.a = c->a.as<uint8_t>() + r0;
     w.b = c->b.as<uint8_t>() + c->col0;
-    w.bnd_row = (wb.bnd_row ? wb.bnd_row : c->bnd_row.as<int>()) + 3 * c->col0;
-    w.bnd_col = (wb.bnd_col ? wb.bnd_col : c->bnd_col.as<int>()) + 3 * r0;
+    w.bnd_row = (wb.bnd_row ? wb.bnd_row : c->fb.bnd_row.as<int>()) + 3 * c->col0;
+    w.bnd_col = (wb.bnd_col ? wb.bnd_col : c->fb.bnd_col.as<int>()) + 3 * r0;
     w.rng = wb.rng;
     w.nrng = (long long)ntab;
     w.m = (int)(mb >= 0 ? mb : c->m);
@@ -1059,7 +893,7 @@ int64_t band_rows(ga_ctx* c) {
     if (const char* e = c->knob("GA_TB_BUDGET_MB")) budget = atoll(e) << 20;
     // ... and no more than the device has free for them (what this context's word buffer already holds counts as
     // free), less a 2 GB margin: a stored-words fill past it failed with GA_E_HIP instead of banding
-    budget = std::min(budget, dev_avail_bytes(c, (int64_t)c->tb.cap));
+    budget = std::min(budget, dev_avail_bytes(c, (int64_t)c->fb.tb.cap));
     const int64_t words = ((c->n + 63) / 64) * 64 * c->CB;  // traceback bytes per row
     if (c->m * words <= budget) return 0;
     const int64_t Bh = std::max<int64_t>(64, (budget / words / ga::FROWS) * ga::FROWS);
@@ -1068,7 +902,7 @@ int64_t band_rows(ga_ctx* c) {
 
 int check_fill_abort(ga_ctx* c) {
     unsigned abort_word = 0;
-    HIPCHK(hipMemcpy(&abort_word, c->flags.as<unsigned>() + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&abort_word, c->fb.flags.as<unsigned>() + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
     if (abort_word) return fail(GA_E_TIMEOUT, "fill kernel hand-off wait timed out");
     return GA_OK;
 }
@@ -1108,7 +942,7 @@ int banded_align(ga_ctx* c, int64_t Bh, uint32_t* mt_state, const char* a_chr, c
         if (b > 0) {
             int2* row = ck + (size_t)(b - 1) * (n + 1);
             // column 0 of the checkpoint row: the left edge's corner H'(r0, 0)
-            HIPCHK(hipMemcpyAsync(row, c->left.as<int2>() + bd.r0, sizeof(int2), hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(row, c->fb.left.as<int2>() + bd.r0, sizeof(int2), hipMemcpyDeviceToDevice, c->stream));
             bd.top = row;
         }
         if (int r = enqueue_fill(c, GA_FILL_TRACEBACK, bd)) return r;
@@ -1119,7 +953,7 @@ int banded_align(ga_ctx* c, int64_t Bh, uint32_t* mt_state, const char* a_chr, c
         len += seg;
         walk_ms += c->walk_ms;
         float f = 0.f;
-        if (hipEventElapsedTime(&f, c->ev[0], c->ev[1]) == hipSuccess) fill_ms += f;
+        if (hipEventElapsedTime(&f, c->fb.ev[0], c->fb.ev[1]) == hipSuccess) fill_ms += f;
     }
     c->walk_ms = walk_ms;
     c->fill_ms = fill_ms;
@@ -1161,9 +995,8 @@ int rc_fill(ga_ctx* c) {
     Band bd;
     bd.rc = true;
     bd.rc_every = rc_every_req(c);
-    if (int r = enqueue_fill(c, 0, bd)) return r;
+    if (int r = enqueue_fill(c, 0, bd, &c->rc_plan)) return r;
     c->rc_used = true;
-    c->rc_T = c->T;
     return GA_OK;
 }
 
@@ -1175,8 +1008,8 @@ int rc_fill(ga_ctx* c) {
 // its block's 3 x 64 x 64*TD entries in LDS) and o <= 14 (X'-H', Y'-H' saturated at o+1 index a 1024-entry LUT).
 bool rc_jump_wanted(ga_ctx* c, int TD) {
 #ifdef GA_EXPERIMENTS
-    return rc_jump_requested(c) && TD <= 4 && c->o <= 14 &&
-           ga::rc_jump_lds_bytes(TD, c->rc_every_used) + 12 * 1024 <= 160 * 1024;
+    return c->pk.rc_jump && TD <= 4 && c->o <= 14 &&
+           ga::rc_jump_lds_bytes(TD, c->rc_plan.rc_every) + 12 * 1024 <= 160 * 1024;
 #else
     (void)c;
     (void)TD;
@@ -1186,8 +1019,8 @@ bool rc_jump_wanted(ga_ctx* c, int TD) {
 
 int rc_walk_launch(ga_ctx* c, int64_t ntab, const WalkStart& st, WalkBufs& wb) {
     const int64_t m = c->m, n = c->n;
-    const int TD = c->rc_T, CB = c->CB;
-    const int nbi = (int)((m + 63) / 64), nbs = c->nstripes;
+    const int TD = c->rc_plan.T, CB = c->CB;
+    const int nbi = (int)((m + 63) / 64), nbs = c->rc_plan.nstripes;
     c->rc_jump = rc_jump_wanted(c, TD);
     HIPCHK(c->rc_tb.ensure(rc_cache_bytes(c->rc_jump, TD, CB)));
     const size_t nflags = (size_t)nbi * nbs;
@@ -1222,19 +1055,19 @@ int rc_walk_launch(ga_ctx* c, int64_t ntab, const WalkStart& st, WalkBufs& wb) {
     r.b = c->b.as<uint8_t>() + c->col0;
     r.subp = c->qp.as<int>();
     r.K = c->K;
-    r.top = c->top.as<int2>() + c->col0;
+    r.top = c->fb.top.as<int2>() + c->col0;
     // the slab's left edge (another GPU's right edge, landed in full by now) or column 0
-    r.left = c->slab && c->col0 > 0 ? (c->halo_in_ext ? c->halo_in_ext : c->halo_in.as<int2>()) : c->left.as<int2>();
+    r.left = c->slab && c->col0 > 0 ? (c->halo_in_ext ? c->halo_in_ext : c->halo_in.as<int2>()) : c->fb.left.as<int2>();
     r.colck = c->colck.as<int2>();
     r.stck = c->stck.as<int2>();
-    r.stck_every = c->rc_every_used;
+    r.stck_every = c->rc_plan.rc_every;
     r.tb = c->rc_tb.as<uint8_t>();
     r.TC = w.TC;
     r.m = (int)m;
     r.n = (int)n;
     r.o = c->o;
     r.TD = TD;
-    r.nstripes = c->nstripes;
+    r.nstripes = nbs;
     r.nbi = nbi;
     r.nbs = nbs;
     r.flags = c->rc_flags.as<unsigned>();
@@ -1359,15 +1192,15 @@ int fill_results_async(ga_ctx* c) {
     HIPCHK(hipEventRecord(c->ev_fill, c->stream));
     HIPCHK(hipStreamWaitEvent(c->ustream, c->ev_fill, 0));
     int* res = c->res_pin.host<int>();
-    HIPCHK(hipMemcpyAsync(res + 16, c->out_last.p, sizeof(int) * 4, hipMemcpyDeviceToHost, c->ustream));
-    HIPCHK(hipMemcpyAsync(res + 20, c->flags.as<unsigned>() + 1, sizeof(unsigned), hipMemcpyDeviceToHost, c->ustream));
+    HIPCHK(hipMemcpyAsync(res + 16, c->fb.out_last.p, sizeof(int) * 4, hipMemcpyDeviceToHost, c->ustream));
+    HIPCHK(hipMemcpyAsync(res + 20, c->fb.flags.as<unsigned>() + 1, sizeof(unsigned), hipMemcpyDeviceToHost, c->ustream));
     HIPCHK(hipEventRecord(c->ev_res, c->ustream));
     return GA_OK;
 }
 
 int fill_results_finish(ga_ctx* c, int64_t* cost_out) {
     HIPCHK(hipEventSynchronize(c->ev_res));
-    HIPCHK(hipEventElapsedTime(&c->fill_ms, c->ev[0], c->ev[1]));
+    HIPCHK(hipEventElapsedTime(&c->fill_ms, c->fb.ev[0], c->fb.ev[1]));
     const int* res = c->res_pin.host<int>();
     if (res[20]) return fail(GA_E_TIMEOUT, "fill kernel hand-off wait timed out");
     c->GV_m = (int)c->gv_total;
@@ -1526,7 +1359,7 @@ int pipe_setup(ga_ctx* c) {
     const int64_t per = c->m + c->n + 1;
     for (int s = 0; s < c->pipe_slots; s++) {
         auto& sl = c->pipe[s];
-        for (hipEvent_t* e : {&sl.f0, &sl.f1, &sl.w0, &sl.w1})
+        for (hipEvent_t* e : {&sl.fb.ev[0], &sl.fb.ev[1], &sl.w0, &sl.w1})
             if (!*e) HIPCHK(hipEventCreate(e));
         if (!sl.fdone) HIPCHK(hipEventCreateWithFlags(&sl.fdone, hipEventDisableTiming));
         HIPCHK(sl.tab_pin.ensure(sizeof(uint32_t) * per));
@@ -1534,18 +1367,11 @@ int pipe_setup(ga_ctx* c) {
         HIPCHK(sl.ops.ensure(c->m + c->n + 1024));
         HIPCHK(sl.result.ensure(sizeof(int) * 16));
         const int64_t m = c->m, na = c->n_global;
-        HIPCHK(sl.GVp.ensure(sizeof(int) * (m + 1)));
-        HIPCHK(sl.GHp.ensure(sizeof(int) * (na + 1)));
-        HIPCHK(sl.top.ensure(sizeof(int2) * (na + 1)));
-        HIPCHK(sl.left.ensure(sizeof(int2) * (m + 1)));
-        HIPCHK(sl.bnd_row.ensure(sizeof(int) * 3 * (na + 1)));
-        HIPCHK(sl.bnd_col.ensure(sizeof(int) * 3 * (m + 1)));
-        HIPCHK(sl.meta.ensure(sizeof(int) * 8));
-        HIPCHK(sl.bscr.ensure(sizeof(int) * ga::boundary_scratch_ints((int)m, (int)na)));
+        HIPCHK(sl.fb.ensure_boundary(m, na));
         if (c->custom) {  // host-supplied boundary triples: the boundary pass reads them from the slot
-            HIPCHK(hipMemcpyAsync(sl.bnd_row.p, c->bnd_row.p, sizeof(int) * 3 * (na + 1), hipMemcpyDeviceToDevice,
+            HIPCHK(hipMemcpyAsync(sl.fb.bnd_row.p, c->fb.bnd_row.p, sizeof(int) * 3 * (na + 1), hipMemcpyDeviceToDevice,
                                   c->stream));
-            HIPCHK(hipMemcpyAsync(sl.bnd_col.p, c->bnd_col.p, sizeof(int) * 3 * (m + 1), hipMemcpyDeviceToDevice,
+            HIPCHK(hipMemcpyAsync(sl.fb.bnd_col.p, c->fb.bnd_col.p, sizeof(int) * 3 * (m + 1), hipMemcpyDeviceToDevice,
                                   c->stream));
         }
     }
@@ -1554,32 +1380,19 @@ int pipe_setup(ga_ctx* c) {
 }
 
 // fill of an alignment into slot `slot` on stream `st`, then its cost inputs into pinned memory, then `fdone`
-int pipe_fill(ga_ctx* c, int slot, hipStream_t st, bool row = false) {
+int pipe_fill(ga_ctx* c, int slot, hipStream_t st, bool row = false, gaplan::FillPlan* plan_out = nullptr) {
     auto& sl = c->pipe[slot];
-    Band bd;
-    bd.tbuf = &sl.tb;
-    bd.hbuf = &sl.hand;
-    bd.fbuf = &sl.flags;
-    bd.obuf = &sl.out_last;
+    Band bd;  // this slot's buffers, this stream, this lane geometry
+    bd.bufs = &sl.fb;
     bd.stream = st;
-    bd.ev0 = sl.f0;
-    bd.ev1 = sl.f1;
-    bd.GVp = &sl.GVp;
-    bd.GHp = &sl.GHp;
-    bd.top_b = &sl.top;
-    bd.left = &sl.left;
-    bd.bnd_row = &sl.bnd_row;
-    bd.bnd_col = &sl.bnd_col;
-    bd.meta = &sl.meta;
-    bd.bscr = &sl.bscr;
     bd.lane_td = row ? 0 : c->pipe_lane_td;
     bd.lane_nwc = row ? 0 : c->pipe_lane_nwc;
-    if (int r = enqueue_fill(c, GA_FILL_TRACEBACK, bd)) return r;
+    if (int r = enqueue_fill(c, GA_FILL_TRACEBACK, bd, plan_out)) return r;
     int* pin = c->pipe_pin.host<int>() + 8 * slot;
-    HIPCHK(hipMemcpyAsync(pin, sl.out_last.p, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(pin + 4, sl.meta.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(pin + 5, sl.GHp.as<int>() + c->col0 + c->n, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(pin + 6, sl.flags.as<unsigned>() + 1, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(pin, sl.fb.out_last.p, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(pin + 4, sl.fb.meta.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(pin + 5, sl.fb.GHp.as<int>() + c->col0 + c->n, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(pin + 6, sl.fb.flags.as<unsigned>() + 1, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(sl.fdone, st));
     return GA_OK;
 }
@@ -1695,24 +1508,25 @@ int align_chain(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, con
         // fill 0 first (it fixes the fill geometry and so the size of every slot's traceback words), then
         // the walks' launch, so that its workgroup has a CU before the other fills take them all, then
         // fills 1 .. S-1; fill j goes into slot j % S on fill stream j % F (each computes its own boundary)
-        if (int r = pipe_fill(c, 0, fs[0])) return r;
+        gaplan::FillPlan pl;
+        if (int r = pipe_fill(c, 0, fs[0], false, &pl)) return r;
         enqueued++;
         // every slot's fill buffers at their final size now: a reallocation's hipFree while the chain runs
         // would wait for the chain, which waits for the host
-        const size_t tb_bytes = (size_t)c->nstripes * c->T * c->TC * 1024;
-        const size_t hand_bytes = sizeof(int2) * (size_t)c->nslabs * (m + 1);
+        const size_t tb_bytes = (size_t)pl.nstripes * pl.T * pl.TC * 1024;
+        const size_t hand_bytes = sizeof(int2) * (size_t)pl.nslabs * (m + 1);
         for (int s = 1; s < S; s++) {
             auto& sl = c->pipe[s];
-            HIPCHK(sl.tb.ensure(tb_bytes));
-            HIPCHK(sl.hand.ensure(hand_bytes));
-            HIPCHK(sl.flags.ensure(sizeof(unsigned) * 16));
-            HIPCHK(sl.out_last.ensure(sizeof(int) * 4));
+            HIPCHK(sl.fb.tb.ensure(tb_bytes));
+            HIPCHK(sl.fb.hand.ensure(hand_bytes));
+            HIPCHK(sl.fb.flags.ensure(sizeof(unsigned) * 16));
+            HIPCHK(sl.fb.out_last.ensure(sizeof(int) * 4));
         }
         ga::WalkChainArgs A{};
         for (int s = 0; s < S; s++) {
             auto& sl = c->pipe[s];
-            const WalkBufs wb{sl.tb.as<uint8_t>(), nullptr, sl.ops.as<uint32_t>(), sl.result.as<int>(),
-                              ws, nullptr, nullptr, sl.bnd_row.as<int>(), sl.bnd_col.as<int>()};
+            const WalkBufs wb{sl.fb.tb.as<uint8_t>(), nullptr, sl.ops.as<uint32_t>(), sl.result.as<int>(),
+                              ws, nullptr, nullptr, sl.fb.bnd_row.as<int>(), sl.fb.bnd_col.as<int>()};
             A.w[s] = walk_args(c, per, WalkStart{m, n, 0, 0, 0, 1}, 0, -1, false, wb);
             A.w[s].result = reinterpret_cast<int*>(static_cast<uint8_t*>(io_dev) + io_stride * s);
             A.w[s].ops = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(io_dev) + io_stride * s + 256);
@@ -1771,7 +1585,7 @@ int align_chain(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, con
         }
         cost_out[k] = (int64_t)pin[0] + pin[4] + pin[5];
         float f = 0.f;
-        if (hipEventElapsedTime(&f, sl.f0, sl.f1) == hipSuccess) fill_sum += f;
+        if (hipEventElapsedTime(&f, sl.fb.ev[0], sl.fb.ev[1]) == hipSuccess) fill_sum += f;
         walk_sum += res[8] / 1.0e5f;  // the walker's own time (s_memrealtime ticks, 100 MHz)
         if (trace)
             fprintf(trace, "{\"k\": %d, \"chain\": 1, \"fill_ms\": %.3f, \"walk_ms\": %.3f, \"walk_done_host\": %.3f, "
@@ -1787,8 +1601,8 @@ int align_chain(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, con
             enqueued++;
         }
         // alignment k's strings, while walk k+1 and the fills run
-        const WalkBufs wb{sl.tb.as<uint8_t>(), nullptr, sl.ops.as<uint32_t>(), sl.result.as<int>(),
-                          ws, nullptr, nullptr, sl.bnd_row.as<int>(), sl.bnd_col.as<int>()};
+        const WalkBufs wb{sl.fb.tb.as<uint8_t>(), nullptr, sl.ops.as<uint32_t>(), sl.result.as<int>(),
+                          ws, nullptr, nullptr, sl.fb.bnd_row.as<int>(), sl.fb.bnd_col.as<int>()};
         WalkStart st{m, n, 0, 0, 0, 1};
         int reason = 0;
         int64_t len = 0;
@@ -1832,7 +1646,7 @@ int align_many(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, cons
         // and GA_PIPE_FILLS (2..4) override.
         const char* pm = c->knob("GA_PIPE_MODE");
         bool lane = c->CB == 1 && c->qbytes == 1 && c->K <= 32 && c->m >= 32768 && c->n >= 4 * 4 * 64 * 64 &&
-                    c->diag_req != 1 && c->diag_req != 2;
+                    c->pk.diag_req != 1 && c->pk.diag_req != 2;
         if (pm && !strcmp(pm, "row")) lane = false;
         if (pm && !strcmp(pm, "lane")) lane = c->qbytes == 1 && c->K <= 32;
         c->pipe_lane_td = lane ? (c->CB == 1 ? 4 : 2) : 0;
@@ -1921,10 +1735,10 @@ int align_many(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, cons
     }();
     auto walk_bufs = [&](int s) {
         auto& sl = c->pipe[s];
-        return WalkBufs{sl.tb.as<uint8_t>(), sl.rng.as<uint32_t>(),
+        return WalkBufs{sl.fb.tb.as<uint8_t>(), sl.rng.as<uint32_t>(),
                         pinned_io ? reinterpret_cast<uint32_t*>(io_dev + io_stride * s + 256) : sl.ops.as<uint32_t>(),
                         pinned_io ? reinterpret_cast<int*>(io_dev + io_stride * s) : sl.result.as<int>(), ws, sl.w0,
-                        sl.w1, sl.bnd_row.as<int>(), sl.bnd_col.as<int>()};
+                        sl.w1, sl.fb.bnd_row.as<int>(), sl.fb.bnd_col.as<int>()};
     };
     std::vector<int> pending;  // slots holding an enqueued fill no walk has taken, in enqueue order
     std::vector<int> walk_slot((size_t)count, -1);
@@ -2019,7 +1833,7 @@ int align_many(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, cons
             Dmax = std::max(Dmax, Dk);
             if (trace) {
                 float t[4] = {0.f, 0.f, 0.f, 0.f};
-                hipEvent_t evs[4] = {sl.f0, sl.f1, sl.w0, sl.w1};
+                hipEvent_t evs[4] = {sl.fb.ev[0], sl.fb.ev[1], sl.w0, sl.w1};
                 for (int q = 0; q < 4; q++) (void)hipEventElapsedTime(&t[q], origin, evs[q]);
                 // the walker's own accounting (walk_kernel result[4..11]; s_memrealtime ticks at 100 MHz)
                 fprintf(trace, "{\"k\": %d, \"fill0\": %.3f, \"fill1\": %.3f, \"walk0\": %.3f, \"walk1\": %.3f, "
@@ -2044,7 +1858,7 @@ int align_many(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, cons
             if (pin[6]) return fail(GA_E_TIMEOUT, "fill kernel hand-off wait timed out");
             cost_out[k] = (int64_t)pin[0] + pin[4] + pin[5];
             float f = 0.f;
-            if (hipEventElapsedTime(&f, sl.f0, sl.f1) == hipSuccess) fill_sum += f;
+            if (hipEventElapsedTime(&f, sl.fb.ev[0], sl.fb.ev[1]) == hipSuccess) fill_sum += f;
             float wms = 0.f;
             if (hipEventElapsedTime(&wms, sl.w0, sl.w1) == hipSuccess) walk_sum += wms;
             // the next fill into walk k's slot (walk k has read it), on its stream after the fill F before
@@ -2203,6 +2017,12 @@ int ga_ctx_create_opts(int device, const char* options, ga_ctx** out) {
                 return fail(GA_E_ARG, "GA_RC_EVERY must be a power of two in [64, 2^20], not '" + it->second + "'");
         }
     }
+    // the planner's self-test plans with the kernels' LDS formulas as ga_plan.h restates them: they must be the kernels'
+    for (int every : {64, 128, 4096})
+        for (int w : {1, 2, 4, 8})
+            if (gaplan::restated_fill_lane_lds_bytes(w, 4 * w, 4 * every) != ga::fill_lane_lds_bytes(w, 4 * w, 4 * every) ||
+                gaplan::restated_rc_worker_bytes(w, w == 8 ? 1 : w, every) != ga::rc_worker_bytes(w, w == 8 ? 1 : w, every))
+                return fail(GA_E_STATE, "ga_plan.h restates the kernels' LDS formulas wrongly");
     int n = 0;
     HIPCHK(hipGetDeviceCount(&n));
     if (device < 0 || device >= n) return fail(GA_E_ARG, "no such HIP device");
@@ -2224,12 +2044,7 @@ int ga_ctx_create_opts(int device, const char* options, ga_ctx** out) {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
             c->num_cu = cus;
-        if (const char* e = c->knob("GA_COLS_PER_LANE")) c->T_req = atoi(e);  // tuning overrides
-        if (const char* e = c->knob("GA_FILL_NWC")) c->nwc_req = atoi(e);
-        if (const char* e = c->knob("GA_FILL_MODE"))
-            c->diag_req = !strcmp(e, "diag") ? 2 : !strcmp(e, "row") ? 1 : !strcmp(e, "lane") ? 3 : 0;
-        if (const char* e = c->knob("GA_LANE_COLS_PER_LANE")) c->lane_T_req = atoi(e);
-        if (const char* e = c->knob("GA_DIAG_COLS_PER_LANE")) c->diag_T_req = atoi(e);
+        c->pk = plan_knobs(c);
     }
     // The fill runs on a stream of the greatest priority.  HIP keeps a separate pool of hardware
     // queues per priority (GPU_MAX_HW_QUEUES = 4 per pool and process), so no normal-priority
@@ -2251,8 +2066,8 @@ int ga_ctx_create_opts(int device, const char* options, ga_ctx** out) {
         delete c;
         return fail(GA_E_HIP, "hipEventCreate failed");
     }
-    for (auto& e : c->ev) {
-        if (hipEventCreate(&e) != hipSuccess) {
+    for (hipEvent_t* e : {&c->fb.ev[0], &c->fb.ev[1], &c->wev[0], &c->wev[1]}) {
+        if (hipEventCreate(e) != hipSuccess) {
             delete c;
             return fail(GA_E_HIP, "hipEventCreate failed");
         }
@@ -2271,7 +2086,7 @@ void ga_ctx_destroy(ga_ctx* c) {
     if (c->ev_res) (void)hipEventDestroy(c->ev_res);
     if (c->ustream) (void)hipStreamDestroy(c->ustream);
     for (auto& sl : c->pipe)
-        for (hipEvent_t e : {sl.f0, sl.f1, sl.fdone, sl.w0, sl.w1})
+        for (hipEvent_t e : {sl.fb.ev[0], sl.fb.ev[1], sl.fdone, sl.w0, sl.w1})
             if (e) (void)hipEventDestroy(e);
     if (c->wstream) (void)hipStreamDestroy(c->wstream);
     if (c->cwstream) (void)hipStreamDestroy(c->cwstream);
@@ -2282,7 +2097,7 @@ void ga_ctx_destroy(ga_ctx* c) {
         if (ns) (void)hipStreamDestroy(ns);
     for (int f = 1; f < 4; f++)
         if (c->fstream[f]) (void)hipStreamDestroy(c->fstream[f]);
-    for (auto& e : c->ev)
+    for (hipEvent_t e : {c->fb.ev[0], c->fb.ev[1], c->wev[0], c->wev[1]})
         if (e) (void)hipEventDestroy(e);
     if (c->ev_dep) (void)hipEventDestroy(c->ev_dep);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -2327,14 +2142,14 @@ int ga_batch_costs_ex(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, i
     if (!plan.kernel.empty()) {
         BatchStage bs;
         if (int r = stage_batch(c, codes, seq_off, nseq, npairs, cs, plan.kernel, plan.scratch_rows, bs)) return r;
-        HIPCHK(hipEventRecord(c->ev[0], c->stream));
+        HIPCHK(hipEventRecord(c->fb.ev[0], c->stream));
         ga::launch_batch_fill(c->stream, bs.args, plan.qbytes, bs.waves);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(c->ev[1], c->stream));
+        HIPCHK(hipEventRecord(c->fb.ev[1], c->stream));
         std::vector<long long> got((size_t)npairs);
         HIPCHK(hipMemcpyAsync(got.data(), c->bt_out.p, sizeof(long long) * npairs, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipEventElapsedTime(&c->fill_ms, c->ev[0], c->ev[1]));
+        HIPCHK(hipEventElapsedTime(&c->fill_ms, c->fb.ev[0], c->fb.ev[1]));
         for (const ga_batch_item& it : plan.kernel) {
             if (got[(size_t)it.out] == INT64_MIN)
                 return fail(GA_E_STATE, "pair " + std::to_string(it.out) + ": work item does not fit the batch launch");
@@ -2409,12 +2224,12 @@ int ga_batch_align(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int6
         gabatch::build_pair_tables(plan.kernel.data(), plan.walk.data(), nitems, seeds, nthreads, tab.data());
         c->batch_align_ms[1] = (float)(now_ms() - t_tab);
         HIPCHK(hipMemcpyAsync(c->bt_rng.p, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipEventRecord(c->ev[0], c->stream));
+        HIPCHK(hipEventRecord(c->fb.ev[0], c->stream));
         const ga::AlignArgs q{bs.args, c->bt_witems.as<ga_batch_walk_item>(), c->bt_rng.as<uint32_t>(),
                               c->bt_ops.as<uint32_t>(), c->bt_walk.as<int4>(), c->bt_tb.as<uint32_t>(), plan.tb_words};
         ga::launch_batch_align(c->stream, q, plan.qbytes, plan.CB, bs.waves);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(c->ev[1], c->stream));
+        HIPCHK(hipEventRecord(c->fb.ev[1], c->stream));
         std::vector<long long> got((size_t)npairs);
         std::vector<int4> walked((size_t)npairs * 2);
         std::vector<uint32_t> ops((size_t)plan.ops_words);
@@ -2423,7 +2238,7 @@ int ga_batch_align(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int6
                               c->stream));
         HIPCHK(hipMemcpyAsync(ops.data(), c->bt_ops.p, sizeof(uint32_t) * ops.size(), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipEventElapsedTime(&c->fill_ms, c->ev[0], c->ev[1]));
+        HIPCHK(hipEventElapsedTime(&c->fill_ms, c->fb.ev[0], c->fb.ev[1]));
         c->batch_align_ms[0] = c->fill_ms;
         // the strings, on the table build's threads (every pair writes its own outputs); out_len < 0: see below
         const double t_dec = now_ms();
@@ -2498,11 +2313,15 @@ int ga_problem_set_cells(ga_ctx* c, const int32_t* cells, int64_t* cost_out) {
     if (!cells || !cost_out) return fail(GA_E_ARG, "null argument");
     const int64_t m = c->m, n = c->n;
     if ((m + 1) * (n + 1) > (int64_t)64 << 20) return fail(GA_E_RANGE, "ga_problem_set_cells is for small problems");
-    c->TC = (int)((m + ga::FROWS - 1) / ga::FROWS) * c->CB;
-    HIPCHK(c->tb.ensure((size_t)((n + 63) / 64) * c->TC * 1024));
+    // words in a fill's layout, 16-row chunks of CB 16-byte words per lane: the walk reads them at the plan's TC
+    const int TC = (int)((m + ga::FROWS - 1) / ga::FROWS) * c->CB;
+    gaplan::FillPlan pl = c->plan;
+    pl.TC = TC;
+    c->plan = pl;
+    HIPCHK(c->fb.tb.ensure((size_t)((n + 63) / 64) * TC * 1024));
     HIPCHK(c->full.ensure(sizeof(int) * 3 * (m + 1) * (n + 1)));
     HIPCHK(hipMemcpyAsync(c->full.p, cells, sizeof(int) * 3 * (m + 1) * (n + 1), hipMemcpyHostToDevice, c->stream));
-    ga::launch_tb_from_cells(c->stream, c->full.as<int>(), (int)m, (int)n, c->o, c->CB, c->TC, c->tb.as<uint8_t>());
+    ga::launch_tb_from_cells(c->stream, c->full.as<int>(), (int)m, (int)n, c->o, c->CB, TC, c->fb.tb.as<uint8_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
     const int32_t* last = cells + 3 * (m * (n + 1) + n);
@@ -2706,7 +2525,7 @@ int ga_slab_buffers(ga_ctx* c, void** halo_in, uint32_t** halo_in_prog, void** h
     if (halo_in_prog) *halo_in_prog = c->prog.host<uint32_t>();
     if (halo_out)
         *halo_out = c->halo_out_ext ? (void*)c->halo_out_ext
-                                    : (void*)(c->hand.as<int2>() + (size_t)(c->nslabs - 1) * (c->m + 1));
+                                    : (void*)(c->fb.hand.as<int2>() + (size_t)(c->plan.nslabs - 1) * (c->m + 1));
     if (halo_out_prog) *halo_out_prog = c->prog.host<uint32_t>() + 1;
     return GA_OK;
 }
@@ -2829,7 +2648,7 @@ int ga_debug_stamps(ga_ctx* c, int enable, unsigned long long* out, int64_t cap)
     if (!c) return fail(GA_E_ARG, "null context");
     c->dbg_on = enable != 0;
     if (out && c->dbg.p) {
-        const int64_t nb = std::min<int64_t>(cap, ga::LK_DBG_WORDS * (int64_t)c->nstripes);
+        const int64_t nb = std::min<int64_t>(cap, ga::LK_DBG_WORDS * (int64_t)c->plan.nstripes);
         HIPCHK(hipMemcpy(out, c->dbg.p, sizeof(unsigned long long) * nb, hipMemcpyDeviceToHost));
     }
     return GA_OK;
@@ -2838,10 +2657,10 @@ int ga_debug_stamps(ga_ctx* c, int enable, unsigned long long* out, int64_t cap)
 // Diagnostics: the fill geometry of the loaded problem {T, nstripes, nwc, nslabs}.
 int ga_debug_geometry(ga_ctx* c, int32_t* out4) {
     if (!c || !out4) return fail(GA_E_ARG, "null argument");
-    out4[0] = c->T;
-    out4[1] = c->nstripes;
-    out4[2] = c->nwc;
-    out4[3] = c->nslabs;
+    out4[0] = c->plan.T;
+    out4[1] = c->plan.nstripes;
+    out4[2] = c->plan.nwc;
+    out4[3] = c->plan.nslabs;
     return GA_OK;
 }
 
@@ -2849,11 +2668,11 @@ int ga_debug_geometry(ga_ctx* c, int32_t* out4) {
 // and its geometry {T, nstripes, nwc, nslabs}.
 int ga_debug_fill_kind(ga_ctx* c, int32_t* out5) {
     if (!c || !out5) return fail(GA_E_ARG, "null argument");
-    out5[0] = c->rc_used ? 3 : c->lane ? 2 : c->diag ? 1 : 0;  // 3: the recompute walk's lane fill
-    out5[1] = c->T;
-    out5[2] = c->nstripes;
-    out5[3] = c->nwc;
-    out5[4] = c->nslabs;
+    out5[0] = c->rc_used ? 3 : c->plan.kind == gaplan::kLane ? 2 : c->plan.kind == gaplan::kDiag ? 1 : 0;  // 3: the recompute walk's lane fill
+    out5[1] = c->plan.T;
+    out5[2] = c->plan.nstripes;
+    out5[3] = c->plan.nwc;
+    out5[4] = c->plan.nslabs;
     return GA_OK;
 }
 

@@ -2,7 +2,9 @@
 // UndefinedBehaviorSanitizer (make -C globalign_amd/csrc asan; run by tests/test_host_asan.py):
 //   * the tie-break table (ga_rng.h): RngTable's four-word scan, its resumable extend() and state_after(), against a draw-by-draw restatement of CPython's random.choice (_randbelow_with_getrandbits over
 //     genrand_uint32) and the dispatcher's level rule (globaligner.py:595-685);
-//   * the problem checks (ga_check.h): argument validation, the int32 range guard, the profile / word widths.
+//   * the problem checks (ga_check.h): argument validation, the int32 range guard, the profile / word widths;
+//   * the fill planner (ga_plan.h): the kernel, geometry and checkpoint spacing of the shapes the project's records
+//     pin (profiles/r06, DESIGN.md 5.2 / 5.6 / 5.8.1, tests/test_gpu_rc_default_width.py), and every error return.
 // No HIP: the engine's library is tested on the GPU; this binary covers the host logic under the sanitizers.
 //
 //   ga_host_selftest            all checks; exit status 0 when every one passes
@@ -16,6 +18,7 @@
 #include <vector>
 
 #include "ga_check.h"
+#include "ga_plan.h"
 #include "ga_rng.h"
 
 using namespace garng;
@@ -196,6 +199,151 @@ void test_checks() {
     CHECK(rc_rows_fit(100000) && !rc_rows_fit((int64_t)1 << 28), "rc_rows_fit");
 }
 
+// ---------------------------------------------------------------- the fill planner (ga_plan.h)
+// The recompute walk's word cache as ga_host.cpp rc_cache_bytes sizes it: RC_CACHE_I x RC_CACHE_S = 64 x 32 blocks
+// (ga_device.h) of TD 64 x 64 tiles of CB bytes, + one stripe of slack (the tie-to-tie walk's is not planned here)
+size_t word_cache_bytes(bool, int TD, int CB) { return (size_t)64 * 32 * TD * 64 * 64 * CB + (size_t)64 * 64 * 4 * 4; }
+const gaplan::LdsSizes kLds{gaplan::restated_fill_lane_lds_bytes, gaplan::restated_rc_worker_bytes, word_cache_bytes};
+
+// an m x n problem on 256 CUs: DNA (K = 4) unless K says otherwise, one-byte words and profile
+gaplan::Problem shape(int64_t m, int64_t n, int K = 4) {
+    gaplan::Problem pb;
+    pb.m = m;
+    pb.n = pb.n_global = n;
+    pb.K = K;
+    pb.o = 5;
+    return pb;  // CB 1, qbytes 1, 256 CUs, 1024 profile rows (load_problem's for K <= 64): the defaults
+}
+
+gaplan::Request rc_request() {
+    gaplan::Request rq;
+    rq.rc = true;
+    return rq;
+}
+
+void expect_plan(const char* what, const gaplan::FillPlan& pl, int kind, int T, int nstripes = -1, int nwc = -1,
+                 int nslabs = -1, int every = -1) {
+    CHECK(pl.err == GA_OK, "%s: error %d (%s)", what, pl.err, pl.msg ? pl.msg : "");
+    CHECK(pl.kind == kind && pl.T == T && (nstripes < 0 || pl.nstripes == nstripes) && (nwc < 0 || pl.nwc == nwc) &&
+              (nslabs < 0 || pl.nslabs == nslabs) && (every < 0 || pl.rc_every == every),
+          "%s: kind %d T %d stripes %d waves %d workgroups %d every %d, expected %d %d %d %d %d %d", what, pl.kind, pl.T,
+          pl.nstripes, pl.nwc, pl.nslabs, pl.rc_every, kind, T, nstripes, nwc, nslabs, every);
+}
+
+void expect_error(const char* what, const gaplan::FillPlan& pl, int code, const char* msg) {
+    CHECK(pl.err == code && pl.msg && std::strcmp(pl.msg, msg) == 0, "%s: error %d (%s), expected %d (%s)", what, pl.err,
+          pl.msg ? pl.msg : "", code, msg);
+}
+
+void test_plan() {
+    using namespace gaplan;
+    const Knobs unset;
+    Knobs wide = unset;  // GA_RC_NARROW=0
+    wide.rc_narrow = false;
+    const Request score, rc = rc_request();
+    Request tb;
+    tb.tb = true;
+    const int64_t c2 = 10000, c3 = 100000, c5 = 20000, c4 = 1000000;
+    const int kProtein = 25;  // BLOSUM62's letters and '-' (scoring.load_named_matrix: CostTables' K)
+    // the recompute fill of the benchmark's workloads (profiles/r06/check5_bench_*.json, fill_kind)
+    expect_plan("C3 rc", plan_fill(shape(c3, c3), rc, unset, kLds), kLane, 2, 782, 4, 196);
+    expect_plan("C3 rc, GA_RC_NARROW=0", plan_fill(shape(c3, c3), rc, wide, kLds), kLane, 4, 391, 4, 98);
+    expect_plan("C2 rc", plan_fill(shape(c2, c2), rc, unset, kLds), kLane, 2, 79, 4, 20);
+    expect_plan("C2 rc, GA_RC_NARROW=0", plan_fill(shape(c2, c2), rc, wide, kLds), kLane, 4, 40, 4, 10);
+    expect_plan("C5 rc", plan_fill(shape(c5, c5, kProtein), rc, unset, kLds), kLane, 4, 79, 4, 20);
+    // score only: C4 in two rounds of 4-wave workgroups; the tall fills' widths
+    expect_plan("C4 score", plan_fill(shape(c4, c4), score, unset, kLds), kLane, 8, 1954, 4, 489);
+    expect_plan("1M x 125k score", plan_fill(shape(c4, 125000), score, unset, kLds), kLane, 2);
+    expect_plan("1M x 250k score", plan_fill(shape(c4, 250000), score, unset, kLds), kLane, 4);
+    expect_plan("1M x 500k score", plan_fill(shape(c4, 500000), score, unset, kLds), kLane, 8);
+    // stored words: the row scan, 64-column stripes, two waves per SIMD
+    expect_plan("C3 stored words", plan_fill(shape(c3, c3), tb, unset, kLds), kRow, 1, 1563, 8, 196);
+    {
+        // C4 with traceback on one GPU: 4 columns per lane, and the spacing whose checkpoints fit 96 GB (128 steps,
+        // 78 GB; 64 would take 156 GB)
+        Knobs kn = unset;
+        kn.dev_avail = (int64_t)286 << 30;
+        expect_plan("C4 rc", plan_fill(shape(c4, c4), rc, kn, kLds), kLane, 4, -1, -1, -1, 128);
+    }
+    {
+        // the pipeline's narrow traceback fills at C3
+        Request pipe = tb;
+        pipe.lane_td = 4;
+        pipe.lane_nwc = 4;
+        const FillPlan pl = plan_fill(shape(c3, c3), pipe, unset, kLds);
+        expect_plan("C3 pipeline fill", pl, kLane, 4, 391, 4, 98);
+        CHECK(pl.qrows <= 2048, "C3 pipeline fill: %d profile rows", pl.qrows);
+    }
+    // the recompute fill's width rules at tests/test_gpu_rc_default_width.py's shapes
+    expect_plan("DNA default", plan_fill(shape(2500, 2600), rc, unset, kLds), kLane, 2);
+    expect_plan("DNA, GA_RC_NARROW=0", plan_fill(shape(2500, 2600), rc, wide, kLds), kLane, 4);
+    expect_plan("protein", plan_fill(shape(1200, 1400, kProtein), rc, unset, kLds), kLane, 4);
+    expect_plan("more stripes than SIMDs", plan_fill(shape(256, 131300), rc, unset, kLds), kLane, 4);
+    {
+        Knobs kn = unset;  // GA_LANE_COLS_PER_LANE=4, GA_RC_NARROW=1
+        kn.lane_T_req = 4;
+        expect_plan("GA_LANE_COLS_PER_LANE=4", plan_fill(shape(2500, 2600), rc, kn, kLds), kLane, 4);
+    }
+    {
+        // a slab with a right neighbour ends on a whole stripe: 1,000,192 columns are 3907 x 256, so
+        // the 8 columns per lane a fill this wide would take fall to 4; too many stripes for the lane kernel, which
+        // keeps every stripe of such a slab resident
+        Problem pb = shape(c4, 1000192);
+        pb.slab = true;
+        pb.n_global = 2 * pb.n;
+        expect_plan("slab with a right neighbour", plan_fill(pb, score, unset, kLds), kRow, 4, 3907);
+        // the last slab hands nothing on and keeps 8 (its 1954 stripes are still more than the 8 x 224 that stay
+        // resident beside the kernel that brings its left edge)
+        pb.col0 = pb.n;
+        expect_plan("last slab", plan_fill(pb, score, unset, kLds), kRow, 8, 1954);
+        // the context's plan before any fill: the row scan's (ga_slab_buffers' default halo_out address)
+        pb.col0 = 0;
+        expect_plan("slab, loaded", row_plan(pb, unset), kRow, 4, 3907, 8, 489);
+    }
+    // every error return
+    expect_error("K > 32", plan_fill(shape(c2, c2, 33), rc, unset, kLds), GA_E_STATE, "recompute fill needs the lane kernel");
+    {
+        Request both = rc;
+        both.tb = true;
+        expect_error("rc with words", plan_fill(shape(c2, c2), both, unset, kLds), GA_E_STATE,
+                     "recompute fill needs the lane kernel");
+    }
+    {
+        // a linked slab with a right neighbour, 1500 stripes of 512 columns: resident only as 8-wave workgroups, which
+        // the checkpointing variant does not run, and rounds of 4-wave ones are not for such a slab
+        Problem pb = shape(c4, 768000);
+        pb.slab = pb.in_linked = pb.out_linked = true;
+        pb.n_global = 2 * pb.n;
+        expect_plan("linked slab, score", plan_fill(pb, score, unset, kLds), kLane, 8, 1500, 8, 188);
+        expect_error("linked slab, rc", plan_fill(pb, rc, unset, kLds), GA_E_STATE, "recompute fill geometry");
+    }
+    {
+        Knobs kn = unset;
+        kn.dev_avail = 1 << 20;  // no spacing fits 1 MB: the stripes narrow to one column per lane, then give up
+        expect_error("1 MB available", plan_fill(shape(c3, c3), rc, kn, kLds), GA_E_NOMEM,
+                     "recompute walk: the checkpoints do not fit the budget / free device memory");
+        Request fixed = rc;  // GA_RC_EVERY=64: its worker fits LDS, its checkpoints do not fit
+        fixed.rc_every = 64;
+        expect_error("1 MB available, GA_RC_EVERY=64", plan_fill(shape(c3, c3), fixed, kn, kLds), GA_E_NOMEM,
+                     "recompute walk: the checkpoints do not fit the budget / free device memory");
+        // (no real word width makes the densest worker miss LDS: a formula that does)
+        LdsSizes big = kLds;
+        big.rc_worker_bytes = [](int, int, int) { return 1 << 20; };
+        expect_error("worker past LDS", plan_fill(shape(c3, c3), rc, unset, big), GA_E_RANGE,
+                     "recompute walk: a block's codes do not fit LDS");
+    }
+    {
+        Request full = tb;
+        full.full = true;
+        expect_error("FULL at C2", plan_fill(shape(c2, c2), full, unset, kLds), GA_E_RANGE, "GA_FILL_FULL is for small problems");
+        // the FULL debug variant of the anti-diagonal kernel is built for 4 compute waves
+        Knobs kn = unset;
+        kn.diag_req = 2;
+        kn.nwc_req = 8;
+        expect_plan("FULL anti-diagonal", plan_fill(shape(300, 1000), full, kn, kLds), kDiag, 1, 16, 4, 4);
+    }
+}
+
 double ms_since(std::chrono::steady_clock::time_point t) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
 }
@@ -228,6 +376,7 @@ int main(int argc, char** argv) {
     test_table(78, 1);
     test_table(79, 50000);
     test_checks();
+    test_plan();
     if (failures) {
         std::fprintf(stderr, "%d check(s) failed\n", failures);
         return 1;

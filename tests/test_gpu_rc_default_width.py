@@ -1,4 +1,4 @@
-"""The recompute fill's default stripe width (ga_host.cpp enqueue_fill): 2 columns per lane for
+"""The recompute fill's default stripe width (ga_plan.h plan_rc_fill): 2 columns per lane for
 alphabets of <= 8 codes whose 128-column stripes all run at once (<= 4 per CU), 4 otherwise; GA_RC_NARROW=0 restores
 4 for an A/B run and GA_LANE_COLS_PER_LANE overrides both.  The width is fill_kind()[1]; every case is also held
 to the oracle (cost, the three strings, the random state) by test_gpu_rc._align."""
