@@ -41,6 +41,7 @@ class EngineError(RuntimeError):
 # every symbol include/globalign_amd.h declares (tests check the exports)
 EXPORTS = [
     "ga_last_error", "ga_device_count", "ga_ctx_create", "ga_ctx_create_opts", "ga_ctx_destroy", "ga_build_flags", "ga_problem_set", "ga_problem_fill", "ga_batch_costs", "ga_batch_costs_ex", "ga_batch_align", "ga_batch_align_timings", "ga_debug_seed_state",
+    "ga_batch_align_ex", "ga_batch_align_info", "ga_debug_pair_tables",
     "ga_problem_set_cells",
     "ga_problem_traceback", "ga_problem_align", "ga_problem_align_many", "ga_problem_set_slab", "ga_slab_buffers", "ga_slab_bind_halos",
     "ga_slab_link", "ga_slab_link_export", "ga_slab_link_import", "ga_enable_peer_access",
@@ -109,6 +110,9 @@ def load_library():
         L.ga_batch_costs_ex.argtypes = [vp, vp, pi64, i64, p32, p32, p32, i64, C.POINTER(GaCosts), pi64]
         L.ga_batch_align.argtypes = [vp, vp, pi64, i64, p32, p32, p32, i64, C.POINTER(GaCosts), vp, vp, vp, vp, vp, pi64,
                                      pi64, p32, pi64]
+        L.ga_batch_align_ex.argtypes = L.ga_batch_align.argtypes + [C.c_uint32]
+        L.ga_batch_align_info.argtypes = [vp, p32]
+        L.ga_debug_pair_tables.argtypes = [vp, vp, p32, i64, i32, pu32, p32]
         L.ga_batch_align_timings.argtypes = [vp, C.POINTER(C.c_float)]
         L.ga_debug_seed_state.argtypes = [C.c_uint64, pu32]
         L.ga_problem_set_cells.argtypes = [vp, p32, pi64]
@@ -208,6 +212,10 @@ def options_string(options=None):
     return ";".join(f"{k}={v}" for k, v in sorted(merged.items()))
 
 
+# where a batch's tie-break tables are made (ga_batch_align_ex's flags)
+RNG_TABLES = {None: 0, "host": 1, "device": 2}
+
+
 class Engine:
     """One HIP device context (ga_ctx)."""
 
@@ -284,12 +292,16 @@ class Engine:
         self.m = self.n = 0
         return out
 
-    def batch_align(self, codes, seq_off, pair_a, pair_b, tables, seeds, chars, pair_max_cost=None):
-        """Alignments of many pairs in one call, every pair from its own random seed (ga_batch_align): batch_costs's
+    def batch_align(self, codes, seq_off, pair_a, pair_b, tables, seeds, chars, pair_max_cost=None, rng_tables=None):
+        """Alignments of many pairs in one call, every pair from its own random seed (ga_batch_align_ex): batch_costs's
         arguments, seeds (uint64, one per pair) and chars, the upper-cased sequences' bytes concatenated as codes is.
+        rng_tables: where the pairs' tie-break tables are made -- None (the context's default), "host" or "device"
+        (batch_rng_kernel); the results are the same.
         -> (costs int64, status int32, lengths int64, offsets int64, (seq_1_aligned, middle, seq_2_aligned) uint8
         buffers): pair k's strings are the lengths[k] bytes at offsets[k] of each buffer.  Afterwards no problem
         counts as loaded."""
+        if rng_tables not in RNG_TABLES:
+            raise ValueError(f"rng_tables must be None, 'host' or 'device', not {rng_tables!r}")
         codes = np.ascontiguousarray(codes, dtype=np.uint8)
         chars = np.ascontiguousarray(chars, dtype=np.uint8)
         seq_off = np.ascontiguousarray(seq_off, dtype=np.int64)
@@ -318,14 +330,40 @@ class Engine:
         costs = np.zeros(P, dtype=np.int64)
         lengths = np.zeros(P, dtype=np.int64)
         status = np.zeros(P, dtype=np.int32)
-        _check(self._L.ga_batch_align(self._h, codes.ctypes.data, seq_off.ctypes.data_as(p64), len(seq_off) - 1,
-                                      pair_a.ctypes.data_as(p32), pair_b.ctypes.data_as(p32), pmc, P,
-                                      C.byref(tables.struct), seeds.ctypes.data, chars.ctypes.data, bufs[0].ctypes.data,
-                                      bufs[1].ctypes.data, bufs[2].ctypes.data, offsets.ctypes.data_as(p64),
-                                      lengths.ctypes.data_as(p64), status.ctypes.data_as(p32),
-                                      costs.ctypes.data_as(p64)))
+        _check(self._L.ga_batch_align_ex(self._h, codes.ctypes.data, seq_off.ctypes.data_as(p64), len(seq_off) - 1,
+                                         pair_a.ctypes.data_as(p32), pair_b.ctypes.data_as(p32), pmc, P,
+                                         C.byref(tables.struct), seeds.ctypes.data, chars.ctypes.data,
+                                         bufs[0].ctypes.data, bufs[1].ctypes.data, bufs[2].ctypes.data,
+                                         offsets.ctypes.data_as(p64), lengths.ctypes.data_as(p64),
+                                         status.ctypes.data_as(p32), costs.ctypes.data_as(p64), RNG_TABLES[rng_tables]))
         self.m = self.n = 0
         return costs, status, lengths, offsets, bufs
+
+    def batch_align_info(self):
+        """{device_items, host_items, fell_back, generator_blocks} of the last batch_align or debug_pair_tables
+        (ga_batch_align_info): the kernel pairs whose tie-break table the device / the host made, whether the
+        generator reached a word cap and the pairs were redone with host tables, and the generator's workgroups."""
+        out = (C.c_int32 * 4)()
+        _check(self._L.ga_batch_align_info(self._h, out))
+        return dict(device_items=out[0], host_items=out[1], fell_back=bool(out[2]), generator_blocks=out[3])
+
+    def debug_pair_tables(self, seeds, steps, rng_tables="device"):
+        """The tie-break tables alone (ga_debug_pair_tables): item t's steps[t] entries under seeds[t], made on the
+        "host" or the "device".  -> (entries uint32, concatenated; offsets int64; status int32 per item: 0 complete,
+        1 word cap reached, 2 a write outside the item's range)."""
+        if rng_tables not in ("host", "device"):
+            raise ValueError(f"rng_tables must be 'host' or 'device', not {rng_tables!r}")
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        steps = np.ascontiguousarray(steps, dtype=np.int32)
+        if seeds.shape != steps.shape or seeds.ndim != 1:
+            raise ValueError("seeds and steps must be 1-d and of equal length")
+        offsets = np.concatenate([[0], np.cumsum(steps, dtype=np.int64)]).astype(np.int64)
+        tab = np.zeros(max(int(offsets[-1]), 1), dtype=np.uint32)
+        status = np.zeros(max(len(steps), 1), dtype=np.int32)
+        _check(self._L.ga_debug_pair_tables(self._h, seeds.ctypes.data, steps.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            len(steps), RNG_TABLES[rng_tables], tab.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                            status.ctypes.data_as(C.POINTER(C.c_int32))))
+        return tab[:int(offsets[-1])], offsets, status[:len(steps)]
 
     def batch_align_timings(self):
         """{kernel_ms, table_ms, decode_ms, call_ms, walk_ns_per_step, fill_ns_per_cell} of the last batch_align (the

@@ -4,7 +4,9 @@
 // Every pair of the batch walks with a tie-break stream of its own, the one `random.seed(seed)` starts, so the walks
 // do not depend on each other: build_pair_tables makes the kernel pairs' tables (ga_rng.h) on a few threads, and
 // decode_levels turns a finished walk's packed levels into the three alignment strings with the engine's one decoder
-// (ga_strings.h) in its strict mode, checking that the levels lead to the end cell the walk reported.
+// (ga_strings.h) in its strict mode, checking that the levels lead to the end cell the walk reported.  Under the
+// device route (ga_batch_align_ex, ga_batch_rng.h) build_pair_tables makes only the tables of the items that stay
+// on the host.
 #pragma once
 #include <stdint.h>
 

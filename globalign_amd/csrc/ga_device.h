@@ -6,6 +6,9 @@
 
 struct ga_batch_item;  // ga_batch.h
 struct ga_batch_walk_item;
+namespace gabrng {
+struct Item;  // ga_batch_rng.h
+}
 
 namespace ga {
 
@@ -238,5 +241,16 @@ struct AlignArgs {
 // a multiple of gabatch::kWavesPerGroup; CB: bytes of a traceback word (1, 2 or 4)
 void launch_batch_fill(hipStream_t s, const BatchArgs& p, int qbytes, int waves);
 void launch_batch_align(hipStream_t s, const AlignArgs& q, int qbytes, int CB, int waves);
+// the device-routed items' tie-break tables, one wave per item (batch_rng_kernel, ga_batch_rng.hip)
+struct RngArgs {
+    const gabrng::Item* items;   // seed, steps and tab_off of each item
+    long long nitems;
+    const uint32_t* base;        // init_genrand(19650218)'s 624 words (gabrng::base_array)
+    uint32_t* tab;               // item t's entries at tab[items[t].tab_off .. + items[t].steps)
+    int32_t* status;             // [nitems]: gabrng::kComplete or kCapReached
+    int cap_words_per_dispatch;  // the word cap is this * steps + 624
+};
+// returns the workgroups launched (gabrng::kWavesPerGroup items each)
+int launch_batch_rng(hipStream_t s, const RngArgs& a);
 
 }  // namespace ga

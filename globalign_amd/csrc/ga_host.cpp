@@ -31,6 +31,7 @@
 #include "ga_check.h"
 #include "ga_batch.h"
 #include "ga_batch_align.h"
+#include "ga_batch_rng.h"
 #include "ga_plan.h"
 #include "ga_rng.h"
 #include "ga_strings.h"
@@ -268,6 +269,12 @@ struct ga_ctx {
     // results, and the waves' traceback words; ga_batch_align_timings's figures of its last call
     DevBuf bt_witems, bt_rng, bt_ops, bt_walk, bt_tb;
     float batch_align_ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // [4], [5]: walk ns per dispatch, fill ns per cell
+    // the device route of the pairs' tables (batch_rng_kernel): its work items, status words and the seeding's base
+    // array (uploaded once), its own timing events, and ga_batch_align_info's figures of the last call
+    DevBuf bt_ritems, bt_rstatus, bt_rbase;
+    bool rbase_ready = false;
+    hipEvent_t rev[2] = {nullptr, nullptr};  // (created with the first generator launch)
+    int32_t batch_rng_info[4] = {0, 0, 0, 0};  // device-routed items, host-routed items, fell back, generator blocks
     int walk_jump_diag[3] = {0, 0, 0};  // the tie-to-tie walk's trips, region re-checks, ties (result[12..14])
     DevBuf jlut;           // the jump workers' LUT for gap open jlut_o (ga::jump_lut_build)
     int jlut_o = -1;
@@ -1963,6 +1970,60 @@ int batch_single_pair(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, c
     return GA_OK;
 }
 
+// How a call's tie-break tables are made: on the device for the items the route rule admits
+// (gabrng::route_device) when the call's flags or the context (GA_BATCH_RNG=device) ask for it, with the item limit
+// GA_BATCH_RNG_DEVICE_MAX_STEPS and the cap's words per dispatch GA_BATCH_RNG_WORD_CAP (both checked at creation).
+struct RngRoute {
+    bool want_device = false;
+    int64_t max_steps = gabrng::kDeviceMaxSteps;
+    int cap_words = gabrng::kCapWordsPerDispatch;
+};
+RngRoute rng_route(const ga_ctx* c, uint32_t flags) {
+    RngRoute r;
+    const uint32_t which = flags & GA_BATCH_TABLES_MASK;
+    const char* dflt = c->knob("GA_BATCH_RNG");
+    r.want_device = which == GA_BATCH_TABLES_DEVICE || (which == GA_BATCH_TABLES_DEFAULT && dflt && !strcmp(dflt, "device"));
+    if (const char* e = c->knob("GA_BATCH_RNG_DEVICE_MAX_STEPS")) r.max_steps = atoll(e);
+    if (const char* e = c->knob("GA_BATCH_RNG_WORD_CAP")) r.cap_words = atoi(e);
+    return r;
+}
+
+// batch_rng_kernel for `items` on the context's stream, between the events c->rev[0] and c->rev[1]: item t's entries
+// go to tab_dev[items[t].tab_off ..), its status word to c->bt_rstatus[t].  `items` is an upload's source: it lives
+// until the caller has synchronised the stream.  groups_out: the workgroups launched.
+int enqueue_batch_rng(ga_ctx* c, const std::vector<gabrng::Item>& items, uint32_t* tab_dev, int cap_words,
+                      int* groups_out) {
+    if (!c->rbase_ready) {
+        // init_genrand(19650218)'s array, the same for every seed: once per context
+        uint32_t base[gabrng::kN];
+        gabrng::base_array(base);
+        HIPCHK(c->bt_rbase.ensure(sizeof(base)));
+        HIPCHK(hipMemcpy(c->bt_rbase.p, base, sizeof(base), hipMemcpyHostToDevice));
+        c->rbase_ready = true;
+    }
+    for (hipEvent_t& e : c->rev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(c->bt_ritems.ensure(sizeof(gabrng::Item) * items.size()));
+    HIPCHK(c->bt_rstatus.ensure(sizeof(int32_t) * items.size()));
+    HIPCHK(hipMemcpyAsync(c->bt_ritems.p, items.data(), sizeof(gabrng::Item) * items.size(), hipMemcpyHostToDevice,
+                          c->stream));
+    HIPCHK(hipEventRecord(c->rev[0], c->stream));
+    const ga::RngArgs a{c->bt_ritems.as<gabrng::Item>(), (long long)items.size(), c->bt_rbase.as<uint32_t>(), tab_dev,
+                        c->bt_rstatus.as<int32_t>(), cap_words};
+    *groups_out = ga::launch_batch_rng(c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->rev[1], c->stream));
+    return GA_OK;
+}
+
+// tab[first, last) of a host-built table to its place in the device's, on the context's stream
+int upload_table_range(ga_ctx* c, const uint32_t* tab, uint32_t* tab_dev, int64_t first, int64_t last) {
+    if (last > first)
+        HIPCHK(hipMemcpyAsync(tab_dev + first, tab + first, sizeof(uint32_t) * (size_t)(last - first),
+                              hipMemcpyHostToDevice, c->stream));
+    return GA_OK;
+}
+
 }  // namespace
 
 // ====================================================================== C ABI
@@ -2016,6 +2077,18 @@ int ga_ctx_create_opts(int device, const char* options, ga_ctx** out) {
             if (v < 64 || (v & (v - 1)) != 0 || v > (1L << 20))
                 return fail(GA_E_ARG, "GA_RC_EVERY must be a power of two in [64, 2^20], not '" + it->second + "'");
         }
+    }
+    {
+        // the tables' route: a name, an item limit the generator's int32 counters hold, a word cap
+        auto it = knobs.find("GA_BATCH_RNG");
+        if (it != knobs.end() && it->second != "host" && it->second != "device")
+            return fail(GA_E_ARG, "GA_BATCH_RNG must be host or device, not '" + it->second + "'");
+        it = knobs.find("GA_BATCH_RNG_DEVICE_MAX_STEPS");
+        if (it != knobs.end() && (atoll(it->second.c_str()) < 0 || atoll(it->second.c_str()) > (1 << 20)))
+            return fail(GA_E_ARG, "GA_BATCH_RNG_DEVICE_MAX_STEPS must be in [0, 2^20], not '" + it->second + "'");
+        it = knobs.find("GA_BATCH_RNG_WORD_CAP");
+        if (it != knobs.end() && (atoll(it->second.c_str()) < 1 || atoll(it->second.c_str()) > 1024))
+            return fail(GA_E_ARG, "GA_BATCH_RNG_WORD_CAP must be in [1, 1024], not '" + it->second + "'");
     }
     // the planner's self-test plans with the kernels' LDS formulas as ga_plan.h restates them: they must be the kernels'
     for (int every : {64, 128, 4096})
@@ -2097,7 +2170,7 @@ void ga_ctx_destroy(ga_ctx* c) {
         if (ns) (void)hipStreamDestroy(ns);
     for (int f = 1; f < 4; f++)
         if (c->fstream[f]) (void)hipStreamDestroy(c->fstream[f]);
-    for (hipEvent_t e : {c->fb.ev[0], c->fb.ev[1], c->wev[0], c->wev[1]})
+    for (hipEvent_t e : {c->fb.ev[0], c->fb.ev[1], c->wev[0], c->wev[1], c->rev[0], c->rev[1]})
         if (e) (void)hipEventDestroy(e);
     if (c->ev_dep) (void)hipEventDestroy(c->ev_dep);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -2178,7 +2251,18 @@ int ga_batch_align(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int6
                    const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
                    const uint64_t* seeds, const char* chars, char* out_a, char* out_mid, char* out_b,
                    const int64_t* out_off, int64_t* out_len, int32_t* tb_status, int64_t* cost_out) {
+    return ga_batch_align_ex(c, codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, seeds, chars, out_a,
+                             out_mid, out_b, out_off, out_len, tb_status, cost_out, GA_BATCH_TABLES_DEFAULT);
+}
+
+int ga_batch_align_ex(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                      const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                      const uint64_t* seeds, const char* chars, char* out_a, char* out_mid, char* out_b,
+                      const int64_t* out_off, int64_t* out_len, int32_t* tb_status, int64_t* cost_out, uint32_t flags) {
     if (int r = check_ctx(c)) return r;
+    if ((flags & ~GA_BATCH_TABLES_MASK) || (flags & GA_BATCH_TABLES_MASK) > GA_BATCH_TABLES_DEVICE)
+        return fail(GA_E_ARG, "bad flags: bits 0-1 choose the tables (0 default, 1 host, 2 device)");
+    for (int32_t& x : c->batch_rng_info) x = 0;
     if (npairs == 0) return GA_OK;  // an empty batch: no launch
     if (!seeds || !chars || !out_a || !out_mid || !out_b || !out_off || !out_len || !tb_status || !cost_out)
         return fail(GA_E_ARG, "null argument");
@@ -2201,7 +2285,9 @@ int ga_batch_align(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int6
     if (!plan.single.empty() && c->slab)
         return fail(GA_E_STATE, "pair " + std::to_string(plan.single[0]) +
                                     ": needs the single-pair path, which a slab context cannot run");
-    if (!plan.kernel.empty()) {
+    // The kernel pairs with their tables by `route`; fell_back: the generator reached an item's word cap, nothing of
+    // the launch was decoded and the caller runs the pairs again with host tables.
+    auto kernel_pairs = [&](const RngRoute& route, bool& fell_back) -> int {
         const int nitems = (int)plan.kernel.size();
         BatchStage bs;
         if (int r = stage_batch(c, codes, seq_off, nseq, npairs, cs, plan.kernel, plan.scratch_rows, bs)) return r;
@@ -2216,14 +2302,50 @@ int ga_batch_align(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int6
         }
         HIPCHK(hipMemcpyAsync(c->bt_witems.p, plan.walk.data(), sizeof(ga_batch_walk_item) * nitems,
                               hipMemcpyHostToDevice, c->stream));
-        // every pair's tie-break table from its own seed, on a few host threads
+        // Every pair's tie-break table from its own seed.  The device-routed items' (gabrng::route_device) are made
+        // by batch_rng_kernel ahead of the walks, on the same stream; the others' on a few host threads meanwhile,
+        // their ranges of the table uploaded behind the generator.
+        std::vector<gabrng::Item> dev;
+        std::vector<ga_batch_item> host_items;
+        std::vector<ga_batch_walk_item> host_walk;
+        for (int t = 0; t < nitems; t++) {
+            const ga_batch_item& it = plan.kernel[(size_t)t];
+            const int64_t steps = (int64_t)it.m + it.n;
+            if (gabrng::route_device(route.want_device, steps, route.max_steps)) {
+                dev.push_back(gabrng::Item{seeds[it.out], plan.walk[(size_t)t].tab_off, (int32_t)steps, 0});
+            } else {
+                host_items.push_back(it);
+                host_walk.push_back(plan.walk[(size_t)t]);
+            }
+        }
+        int groups = 0;
+        if (!dev.empty())
+            if (int r = enqueue_batch_rng(c, dev, c->bt_rng.as<uint32_t>(), route.cap_words, &groups)) return r;
         const double t_tab = now_ms();
-        std::vector<uint32_t> tab((size_t)plan.tab_entries);
+        std::vector<uint32_t> tab(host_items.empty() ? 0 : (size_t)plan.tab_entries);
         const char* nt = c->knob("GA_BATCH_RNG_THREADS");
         const int nthreads = gabatch::rng_threads(nt ? atoi(nt) : 0, nitems);
-        gabatch::build_pair_tables(plan.kernel.data(), plan.walk.data(), nitems, seeds, nthreads, tab.data());
-        c->batch_align_ms[1] = (float)(now_ms() - t_tab);
-        HIPCHK(hipMemcpyAsync(c->bt_rng.p, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice, c->stream));
+        if (!host_items.empty()) {
+            const int64_t nhost = (int64_t)host_items.size();
+            gabatch::build_pair_tables(host_items.data(), host_walk.data(), nhost, seeds,
+                                       gabatch::rng_threads(nt ? atoi(nt) : 0, nhost), tab.data());
+            // (the work list's table ranges follow each other: neighbouring host items go up in one copy)
+            int64_t first = host_walk[0].tab_off, last = first;
+            for (int64_t t = 0; t < nhost; t++) {
+                const int64_t off = host_walk[(size_t)t].tab_off;
+                if (off != last) {
+                    if (int r = upload_table_range(c, tab.data(), c->bt_rng.as<uint32_t>(), first, last)) return r;
+                    first = off;
+                }
+                last = off + host_items[(size_t)t].m + host_items[(size_t)t].n;
+            }
+            if (int r = upload_table_range(c, tab.data(), c->bt_rng.as<uint32_t>(), first, last)) return r;
+        }
+        const float host_tab_ms = (float)(now_ms() - t_tab);
+        c->batch_align_ms[1] = host_tab_ms;
+        c->batch_rng_info[0] = (int32_t)dev.size();
+        c->batch_rng_info[1] = (int32_t)host_items.size();
+        c->batch_rng_info[3] = groups;
         HIPCHK(hipEventRecord(c->fb.ev[0], c->stream));
         const ga::AlignArgs q{bs.args, c->bt_witems.as<ga_batch_walk_item>(), c->bt_rng.as<uint32_t>(),
                               c->bt_ops.as<uint32_t>(), c->bt_walk.as<int4>(), c->bt_tb.as<uint32_t>(), plan.tb_words};
@@ -2237,9 +2359,27 @@ int ga_batch_align(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int6
         HIPCHK(hipMemcpyAsync(walked.data(), c->bt_walk.p, sizeof(int4) * 2 * npairs, hipMemcpyDeviceToHost,
                               c->stream));
         HIPCHK(hipMemcpyAsync(ops.data(), c->bt_ops.p, sizeof(uint32_t) * ops.size(), hipMemcpyDeviceToHost, c->stream));
+        // the generator's status words come back with the walks' results, in the same synchronisation
+        std::vector<int32_t> rstatus(dev.size());
+        if (!dev.empty())
+            HIPCHK(hipMemcpyAsync(rstatus.data(), c->bt_rstatus.p, sizeof(int32_t) * dev.size(), hipMemcpyDeviceToHost,
+                                  c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         HIPCHK(hipEventElapsedTime(&c->fill_ms, c->fb.ev[0], c->fb.ev[1]));
         c->batch_align_ms[0] = c->fill_ms;
+        if (!dev.empty()) {
+            // "tables": the generator's time and whatever of the host's share it did not hide
+            float gen_ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&gen_ms, c->rev[0], c->rev[1]));
+            c->batch_align_ms[1] = gen_ms + std::max(0.f, host_tab_ms - gen_ms);
+            for (const int32_t st : rstatus)
+                if (st != gabrng::kComplete) {
+                    // an item stopped at its word cap: the walks read unwritten entries (harmlessly: a walk makes at
+                    // most m + n - 1 steps whatever the table holds), so nothing of this launch is decoded
+                    fell_back = true;
+                    return GA_OK;
+                }
+        }
         // the strings, on the table build's threads (every pair writes its own outputs); out_len < 0: see below
         const double t_dec = now_ms();
         gabatch::run_shares(nitems, nthreads, [&](int64_t first, int64_t stride) {
@@ -2274,6 +2414,19 @@ int ga_batch_align(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int6
         }
         c->batch_align_ms[4] = (float)(10.0 * walk_ticks / std::max(steps, 1.0));  // (a tick is 10 ns)
         c->batch_align_ms[5] = (float)(10.0 * fill_ticks / std::max(cells, 1.0));
+        return GA_OK;
+    };
+    if (!plan.kernel.empty()) {
+        bool fell_back = false;
+        if (int r = kernel_pairs(rng_route(c, flags), fell_back)) return r;
+        if (fell_back) {
+            // through the host route; the figures of the device attempt stay in ga_batch_align_info
+            const float tables_ms = c->batch_align_ms[1];
+            const int32_t first_try[4] = {c->batch_rng_info[0], c->batch_rng_info[1], 1, c->batch_rng_info[3]};
+            if (int r = kernel_pairs(rng_route(c, GA_BATCH_TABLES_HOST), fell_back)) return r;
+            c->batch_align_ms[1] += tables_ms;
+            for (int q = 0; q < 4; q++) c->batch_rng_info[q] = first_try[q];
+        }
     }
     if (!plan.single.empty()) {
         // the single-pair path, one pair at a time, from that pair's seeded state (the state it leaves is dropped).
@@ -2297,6 +2450,84 @@ int ga_batch_align(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int6
 int ga_batch_align_timings(ga_ctx* c, float* out6) {
     if (!c || !out6) return fail(GA_E_ARG, "null argument");
     for (int q = 0; q < 6; q++) out6[q] = c->batch_align_ms[q];
+    return GA_OK;
+}
+
+int ga_batch_align_info(ga_ctx* c, int32_t* out4) {
+    if (!c || !out4) return fail(GA_E_ARG, "null argument");
+    for (int q = 0; q < 4; q++) out4[q] = c->batch_rng_info[q];
+    return GA_OK;
+}
+
+int ga_debug_pair_tables(ga_ctx* c, const uint64_t* seeds, const int32_t* steps, int64_t nitems, int32_t route,
+                         uint32_t* tab_out, int32_t* status_out) {
+    if (int r = check_ctx(c)) return r;
+    if (route != GA_BATCH_TABLES_HOST && route != GA_BATCH_TABLES_DEVICE)
+        return fail(GA_E_ARG, "route must be 1 (host) or 2 (device)");
+    if (nitems < 0 || (nitems > 0 && (!seeds || !steps || !tab_out || !status_out))) return fail(GA_E_ARG, "null argument");
+    for (int32_t& x : c->batch_rng_info) x = 0;
+    c->batch_align_ms[1] = 0.f;
+    // On the device the items lie kGuard words apart, between guard words no entry equals (bits 0 and 31 are never
+    // set in one): a write outside an item's range shows as status 2.
+    constexpr int64_t kGuard = 4;
+    constexpr uint32_t kGuardWord = 0xA5A5A5A5u;
+    const RngRoute rt = rng_route(c, (uint32_t)route);
+    std::vector<gabrng::Item> dev;
+    std::vector<int64_t> dev_of, out_off((size_t)nitems + 1, 0);
+    int64_t dev_words = kGuard;
+    for (int64_t t = 0; t < nitems; t++) {
+        if (steps[t] < 0) return fail(GA_E_ARG, "item " + std::to_string(t) + ": negative steps");
+        out_off[(size_t)t + 1] = out_off[(size_t)t] + steps[t];
+        status_out[t] = gabrng::kComplete;
+        if (gabrng::route_device(rt.want_device, steps[t], rt.max_steps)) {
+            dev.push_back(gabrng::Item{seeds[t], dev_words, steps[t], 0});
+            dev_of.push_back(t);
+            dev_words += steps[t] + kGuard;
+        }
+    }
+    int groups = 0;
+    std::vector<uint32_t> got;
+    std::vector<int32_t> rstatus(dev.size());
+    if (!dev.empty()) {
+        got.resize((size_t)dev_words);
+        HIPCHK(c->bt_rng.ensure(sizeof(uint32_t) * (size_t)dev_words));
+        HIPCHK(hipMemsetAsync(c->bt_rng.p, 0xA5, sizeof(uint32_t) * (size_t)dev_words, c->stream));
+        if (int r = enqueue_batch_rng(c, dev, c->bt_rng.as<uint32_t>(), rt.cap_words, &groups)) return r;
+        HIPCHK(hipMemcpyAsync(got.data(), c->bt_rng.p, sizeof(uint32_t) * got.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(rstatus.data(), c->bt_rstatus.p, sizeof(int32_t) * dev.size(), hipMemcpyDeviceToHost,
+                              c->stream));
+    }
+    // the host's items meanwhile, one after the other
+    {
+        garng::RngTable R;
+        uint32_t state[garng::MTN + 1];
+        size_t q = 0;
+        for (int64_t t = 0; t < nitems; t++) {
+            if (q < dev_of.size() && dev_of[q] == t) {
+                q++;
+                continue;
+            }
+            garng::seed_state(seeds[t], state);
+            R.start(state);
+            R.extend(steps[t]);
+            std::copy(R.tab.begin(), R.tab.begin() + steps[t], tab_out + out_off[(size_t)t]);
+        }
+    }
+    if (!dev.empty()) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipEventElapsedTime(&c->batch_align_ms[1], c->rev[0], c->rev[1]));
+        for (size_t q = 0; q < dev.size(); q++) {
+            const int64_t t = dev_of[q], off = dev[q].tab_off;
+            std::copy(got.begin() + off, got.begin() + off + steps[t], tab_out + out_off[(size_t)t]);
+            bool intact = true;
+            for (int64_t g = 1; g <= kGuard; g++)
+                intact &= got[(size_t)(off - g)] == kGuardWord && got[(size_t)(off + steps[t] + g - 1)] == kGuardWord;
+            status_out[t] = intact ? rstatus[q] : 2;
+        }
+    }
+    c->batch_rng_info[0] = (int32_t)dev.size();
+    c->batch_rng_info[1] = (int32_t)(nitems - (int64_t)dev.size());
+    c->batch_rng_info[3] = groups;
     return GA_OK;
 }
 

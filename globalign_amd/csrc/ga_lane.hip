@@ -736,8 +736,10 @@ __global__ void __launch_bounds__(lane_block_threads(NWC)) fill_lane_kernel(Fill
                         const int row = rlo + lane - 48;
                         const int2 v = (lane & 4) ? make_int2(R[0], R[1]) : make_int2(R[2], R[3]);
                         // one 8-byte store in asm: the compiler split `*p = v` into two dword stores and put the second
-                        // under an exec mask
-                        int2* const cdst = hi && row <= m ? colck_s + row : colck_x;
+                        // under an exec mask.  (row < 0: with a uniform row 0 the first 64 steps take this statement
+                        // too, where lanes 48..63 still hold rows above the matrix -- rlo = r0 - 62 -- and stripe 0's
+                        // would land before the buffer; the lean store's range check drops them, here the scratch slot)
+                        int2* const cdst = hi && row >= 0 && row <= m ? colck_s + row : colck_x;
                         const lk_v2u vv = {(unsigned)v.x, (unsigned)v.y};
                         asm volatile("global_store_dwordx2 %0, %1, off" ::"v"(cdst), "v"(vv) : "memory");
                     }

@@ -138,7 +138,7 @@ class GlobalAligner:
             seqs = seqs + seqs_2
         return self._score_batch(seqs, np.repeat(rows, len(cols)), np.tile(cols, len(rows)), (len(rows), len(cols)))
 
-    def align_pairs(self, seqs_1, seqs_2, seeds=0):
+    def align_pairs(self, seqs_1, seqs_2, seeds=0, tables="host"):
         """Alignments of seqs_1[k] with seqs_2[k] for every k, strings included, in one call.  Pair k is aligned under
         a random seed of its own: ``seeds`` is an int base (pair k uses base + k) or a sequence of one int per pair,
         each in [0, 2**64).  Pair k's strings, cost and score are those of ``random.seed(s_k)`` followed by
@@ -146,7 +146,12 @@ class GlobalAligner:
         process-global ``random`` state is left as it was.  Validation is score_pairs's.  A pair for which the single
         call raises the reference's IndexError (possible only with a one-letter sequence) makes the call raise
         IndexError("pair <k>: string index out of range") for the lowest such k.
+        ``tables`` says where the pairs' tie-break tables are made: "host" (a few CPU threads) or "device" (generated
+        on the GPU ahead of the walks, so the call's time does not depend on the host's cores); the results are the
+        same byte for byte.
         -> BatchAlignments."""
+        if tables not in ("host", "device"):
+            raise ValueError(f"tables must be 'host' or 'device', not {tables!r}")
         seqs_1, seqs_2 = list(seqs_1), list(seqs_2)
         if len(seqs_1) != len(seqs_2):
             raise ValueError(f"align_pairs needs as many first as second sequences, got {len(seqs_1)} and "
@@ -165,8 +170,11 @@ class GlobalAligner:
         if b.text is None:
             raise ValueError("align_pairs takes sequences of one-byte (latin-1) letters")
         eng = _native.default_engine(self.device)
+        # (the host route is the engine's call as it always was; only the device route names itself)
+        route = {} if tables == "host" else {"rng_tables": tables}
         costs, status, lengths, offsets, bufs = eng.batch_align(b.codes, b.seq_off, b.pair_a, b.pair_b, b.tables, seeds,
-                                                                np.frombuffer(b.text, dtype=np.uint8), b.pair_max_cost)
+                                                                np.frombuffer(b.text, dtype=np.uint8), b.pair_max_cost,
+                                                                **route)
         failed = np.flatnonzero(status == _native.GA_TB_INDEX_ERROR)
         if failed.size:
             raise IndexError(f"pair {int(failed[0])}: string index out of range")  # the reference's, SURVEY A.5

@@ -149,6 +149,36 @@ int ga_batch_align(ga_ctx* ctx, const uint8_t* codes, const int64_t* seq_off, in
  * dispatch, the fills' ns per cell} of the last ga_batch_align.  All but the call's cover the pairs that shared
  * the kernel launch; the last two are averages of what each wave timed for its own pairs. */
 int ga_batch_align_timings(ga_ctx* ctx, float* out6);
+/* ga_batch_align with a choice of where the kernel pairs' tie-break tables are made.  flags bits 0-1:
+ * GA_BATCH_TABLES_DEFAULT (the context's: host, or the device under option GA_BATCH_RNG=device),
+ * GA_BATCH_TABLES_HOST (ga_batch_align's threads) or GA_BATCH_TABLES_DEVICE: batch_rng_kernel generates each
+ * pair's MT19937 stream and its table on the GPU, ahead of the walks on the same stream, so neither the table
+ * build nor its upload remains.  The results are the same byte for byte.  Other bits must be zero.
+ * Under the device route a kernel pair of more than GA_BATCH_RNG_DEVICE_MAX_STEPS dispatches (m + n; option,
+ * default 1024, at most 2^20) still gets a host table, built while the generator runs.  A generator item may
+ * consume GA_BATCH_RNG_WORD_CAP * (m + n) + 624 words (option, default 48; a dispatch takes 32 on average); if
+ * one reaches that cap, nothing of the launch is decoded and the kernel pairs run again with host tables.
+ * ga_batch_align is this call with flags 0.  Slot 1 of ga_batch_align_timings is then the generator's time plus
+ * the host table time it did not hide. */
+#define GA_BATCH_TABLES_DEFAULT 0u
+#define GA_BATCH_TABLES_HOST 1u
+#define GA_BATCH_TABLES_DEVICE 2u
+#define GA_BATCH_TABLES_MASK 3u
+int ga_batch_align_ex(ga_ctx* ctx, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                      const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* costs,
+                      const uint64_t* seeds, const char* chars, char* out_a, char* out_mid, char* out_b,
+                      const int64_t* out_off, int64_t* out_len, int32_t* tb_status, int64_t* cost_out, uint32_t flags);
+/* out4 = {kernel pairs whose table the device made, kernel pairs whose table the host made, 1 when the generator
+ * reached a word cap and the pairs were redone with host tables (the first two then describe the device attempt),
+ * workgroups of the generator's launch} of the last ga_batch_align(_ex) or ga_debug_pair_tables. */
+int ga_batch_align_info(ga_ctx* ctx, int32_t* out4);
+/* The tie-break tables alone, with no alignment: item t's steps[t] entries under seeds[t], concatenated in
+ * tab_out, by route 1 (host) or 2 (device; an item over GA_BATCH_RNG_DEVICE_MAX_STEPS is built on the host, as
+ * in the real call).  status_out[t]: 0 complete, 1 the word cap was reached (entries past the stop are
+ * 0xA5A5A5A5, which no entry equals), 2 a word outside the item's range was written.  Afterwards slot 1 of
+ * ga_batch_align_timings holds the generator's time. */
+int ga_debug_pair_tables(ga_ctx* ctx, const uint64_t* seeds, const int32_t* steps, int64_t nitems, int32_t route,
+                         uint32_t* tab_out, int32_t* status_out);
 /* random.seed(seed) for an int seed (Modules/_randommodule.c random_seed): the 625 words of
  * random.getstate()[1] it leaves.  CPU only. */
 int ga_debug_seed_state(uint64_t seed, uint32_t* state_out);

@@ -7,8 +7,13 @@ JSON line per workload with pairs, cells, ms (median of 5 calls after 2 warm-ups
     python tools/batch_bench.py --crossover     one pair per call through the batch kernel and through the single-pair
                                                 fill, at growing sizes (the GA_BATCH_MAX_CELLS default)
     python tools/batch_bench.py --align         B1 and B2 through align_pairs (strings included), with the kernel, host
-                                                table and host decode ms of the last call and us per pair; B1 also
-                                                with the tables built on one thread
+                                                table and host decode ms of the last call and us per pair, and the
+                                                engine call's own ms (ga_batch_align: median, least and most of the
+                                                timed calls) with its table and kernel parts; each with the tables
+                                                built on 8 host threads, on one, and -- where the tree has the
+                                                route -- on the device; then the device generator alone on one item
+                                                of growing length (--align-host: without the device route, for older
+                                                trees)
     python tools/batch_bench.py --align-loop K  K of B1's pairs through random.seed(s) + GlobalAligner.align, one at a
                                                 time (runs on older trees too)
     python tools/batch_bench.py --align-crossover   one pair per align_pairs call through the batch kernel and through
@@ -99,24 +104,62 @@ def crossover():
         del _native.OPTIONS["GA_BATCH_MAX_CELLS"]
 
 
-def align_workloads():
-    def run(name, pairs, kw, **options):
+def align_workloads(device):
+    def run(name, pairs, kw, tables="host", **options):
         _native.OPTIONS.update({k: str(v) for k, v in options.items()})
         try:
             al = GlobalAligner(max_seq_len_prod=None, **kw)
             a, b = [p[0] for p in pairs], [p[1] for p in pairs]
-            ms = timed(lambda: al.align_pairs(a, b, seeds=1))
-            t = _native.default_engine(0).batch_align_timings()
+            route = {} if tables == "host" else {"tables": tables}  # (older trees have no such argument)
+            parts = []
+
+            def call():
+                al.align_pairs(a, b, seeds=1, **route)
+                parts.append(_native.default_engine(0).batch_align_timings())
+
+            ms = timed(call)
+            t, parts = parts[-1], parts[-REPEATS:]
+            engine = {f"engine_{k}": round(statistics.median(x[k] for x in parts), 4) for k in ("call_ms", "table_ms", "kernel_ms")}
+            calls = [x["call_ms"] for x in parts]
             report(name, len(pairs), sum(len(x) * len(y) for x, y in pairs), ms, us_per_pair=round(ms * 1e3 / len(pairs), 3),
-                   **{k: round(v, 4) for k, v in t.items()}, **options)
+                   **{k: round(v, 4) for k, v in t.items()}, **engine, engine_call_ms_min=round(min(calls), 4),
+                   engine_call_ms_max=round(max(calls), 4), tables=tables, **options)
         finally:
             for k in options:
                 del _native.OPTIONS[k]
 
-    b1 = pairs_of(4096, 200, 400, "dna", 1)
-    run("B1-align", b1, DNA)
-    run("B1-align", b1, DNA, GA_BATCH_RNG_THREADS=1)
-    run("B2-align", pairs_of(1024, 100, 600, "protein", 2), BLOSUM)
+    for name, pairs, kw in (("B1-align", pairs_of(4096, 200, 400, "dna", 1), DNA),
+                            ("B2-align", pairs_of(1024, 100, 600, "protein", 2), BLOSUM)):
+        run(name, pairs, kw, GA_BATCH_RNG_THREADS=8)
+        run(name, pairs, kw, GA_BATCH_RNG_THREADS=1)
+        if device:
+            run(name, pairs, kw, tables="device")
+    if device:
+        generator_sweep()
+
+
+def generator_sweep():
+    """batch_rng_kernel alone on ONE item of growing length, through the debug entry: its event time (a lone wave:
+    what the longest device-routed item of a launch costs) beside one host thread's time for the same table."""
+    _native.OPTIONS["GA_BATCH_RNG_DEVICE_MAX_STEPS"] = str(1 << 20)
+    try:
+        eng = _native.default_engine(0)
+        for steps in (256, 512, 1024, 2048, 4096, 8192, 16384, 32768, 65536):
+            gen, host = [], []
+            for k in range(WARMUP + REPEATS):
+                _, _, status = eng.debug_pair_tables([k + 1], [steps], rng_tables="device")
+                assert not status.any()
+                gen.append(eng.batch_align_timings()["table_ms"])
+                t0 = time.perf_counter()
+                eng.debug_pair_tables([k + 1], [steps], rng_tables="host")
+                host.append((time.perf_counter() - t0) * 1e3)
+            gen, host = gen[WARMUP:], host[WARMUP:]
+            print(json.dumps(dict(workload="generator-1-item", steps=steps, generator_ms=round(statistics.median(gen), 4),
+                                  generator_ms_min=round(min(gen), 4), generator_ms_max=round(max(gen), 4),
+                                  generator_ns_per_step=round(statistics.median(gen) * 1e6 / steps, 1),
+                                  host_thread_ms=round(statistics.median(host), 4))), flush=True)
+    finally:
+        del _native.OPTIONS["GA_BATCH_RNG_DEVICE_MAX_STEPS"]
 
 
 def align_loop(count):
@@ -151,13 +194,14 @@ def main():
     ap.add_argument("--loop", type=int, default=0, metavar="K")
     ap.add_argument("--crossover", action="store_true")
     ap.add_argument("--align", action="store_true")
+    ap.add_argument("--align-host", action="store_true")
     ap.add_argument("--align-loop", type=int, default=0, metavar="K")
     ap.add_argument("--align-crossover", action="store_true")
     args = ap.parse_args()
     if args.loop:
         loop(args.loop)
-    elif args.align:
-        align_workloads()
+    elif args.align or args.align_host:
+        align_workloads(device=args.align)
     elif args.align_loop:
         align_loop(args.align_loop)
     elif args.align_crossover:
