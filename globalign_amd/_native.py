@@ -5,6 +5,7 @@ GPU is visible, every entry point raises.  The shared library is built
 in-tree by ``__graft_entry__.build()`` (``make -C globalign_amd/csrc``).
 """
 import ctypes as C
+import json
 import os
 import threading
 
@@ -16,6 +17,7 @@ LIB_PATH = os.environ.get("GA_LIB_PATH") or os.path.join(_HERE, "_lib", "libglob
 GA_FILL_TRACEBACK = 1
 GA_FILL_FULL = 2
 GA_E_NOMEM = -6
+GA_E_GUARD = -7
 GA_TB_OK = 0
 GA_TB_INDEX_ERROR = 1
 
@@ -47,7 +49,7 @@ EXPORTS = [
     "ga_slab_link", "ga_slab_link_export", "ga_slab_link_import", "ga_enable_peer_access",
     "ga_slab_fill_launch", "ga_slab_fill_finish", "ga_slab_walk_prepare", "ga_slab_walk", "ga_slab_mt_state",
     "ga_stream_wait_ge", "ga_stream_write", "ga_ctx_stream", "ga_ctx_wait_stream", "ga_ctx_stream_priority",
-    "ga_last_kernel_ms", "ga_last_timings",
+    "ga_last_kernel_ms", "ga_last_timings", "ga_debug_guard_report", "ga_debug_guard_poke",
 ]
 
 
@@ -143,6 +145,8 @@ def load_library():
         L.ga_ctx_stream_priority.argtypes = [vp, C.POINTER(C.c_int)]
         L.ga_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.ga_last_timings.argtypes = [vp, C.POINTER(C.c_float)]
+        L.ga_debug_guard_report.argtypes = [vp, C.c_char_p, i64, pi64]
+        L.ga_debug_guard_poke.argtypes = [vp, C.c_char_p, i32, i64, i64]
         _lib = L
         return L
 
@@ -455,6 +459,23 @@ class Engine:
             lo, L = k * cap, int(ln[k])
             out.append((int(cost[k]), tuple(x[lo:lo + L].tobytes().decode() for x in (oa, om, ob)), int(st[k])))
         return out, mt
+
+    def guard_report(self):
+        """Guard mode's check without an error (ga_debug_guard_report; option GA_GUARD_BYTES): {guard_bytes, fill,
+        poison, violations: [{name, side 'front' / 'rear', offset of the first changed byte relative to the payload,
+        last, changed, payload}], buffers: [{name, payload bytes of the last request, guarded}]} -- the buffers the
+        context has allocated so far, its pipeline slots' as 'pipe<k>.<name>'."""
+        need = C.c_int64(0)
+        _check(self._L.ga_debug_guard_report(self._h, None, 0, C.byref(need)))
+        buf = C.create_string_buffer(need.value + 4096)
+        _check(self._L.ga_debug_guard_report(self._h, buf, len(buf), C.byref(need)))
+        return json.loads(buf.value.decode())
+
+    def guard_poke(self, name, side, offset, nbytes=1):
+        """Change nbytes bytes of a guard of buffer `name` from the host (ga_debug_guard_poke): side 'front' / 'rear',
+        offset from that guard's first byte.  For the tests that show the check reports a changed guard."""
+        _check(self._L.ga_debug_guard_poke(self._h, name.encode(), {"front": 0, "rear": 1}[side], int(offset),
+                                           int(nbytes)))
 
     def timings(self):
         """{fill_ms, walk_ms, rng_ms (host tie-break table), call_ms} of the last call."""

@@ -28,6 +28,11 @@ constexpr int FILL_LDS_MIN = 82 * 1024;  // > 80 KB: one fill workgroup per CU
 // the recompute fill's right-edge checkpoints: a stripe's rows 0..m, then this many scratch slots of its own (a store's
 // offset from the stripe's base then fits the 32-bit VGPR offset of a global store with an SGPR base)
 constexpr int COLCK_PAD = 64;
+// The first left-edge row a recompute block reads above its staircase checkpoint t0 (rc_windows, ga_rcwalk.hip): row
+// t0 + RC_EDGE_FIRST, and t0 >= 0, so never row 0 of a colck stripe.  The lean ramp's checkpoint store relies on it: at
+// r0 = 48 it leaves a ramp value, not the boundary's, in colck row 0 (lk_fill_lane, ga_lane.hip).  The host asserts
+// both halves (rc_walk_launch).
+constexpr int RC_EDGE_FIRST = 1;
 
 struct FillArgs {
     const uint8_t* a;         // m codes (seq_1)

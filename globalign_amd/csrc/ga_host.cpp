@@ -32,6 +32,7 @@
 #include "ga_batch.h"
 #include "ga_batch_align.h"
 #include "ga_batch_rng.h"
+#include "ga_guard.h"
 #include "ga_plan.h"
 #include "ga_rng.h"
 #include "ga_strings.h"
@@ -53,17 +54,41 @@ int fail(int code, const std::string& msg) {
     } while (0)
 
 // ------------------------------------------------------------------ buffers
+struct DevBuf;
+struct PinBuf;
+// Guard mode (ga_guard.h; options GA_GUARD_BYTES / GA_GUARD_FILL / GA_GUARD_POISON, never the
+// environment): one per context, shared by its buffers and its pipeline slots'.  Every buffer is allocated with G
+// bytes of a pattern in front of and behind what its kernels may write, and guard_check reads them back.
+struct GuardCfg {
+    size_t G = 0;
+    uint8_t fill = (uint8_t)gaguard::kDefaultFill;
+    bool poison = false;   // the payload starts as the pattern too
+    // the chained pipeline's persistent kernel runs (align_chain sets it around the launch): that kernel waits for
+    // this thread, so nothing may wait for the device or free memory; a buffer that asks for another size then is refused
+    bool in_chain = false;
+    std::vector<DevBuf*> dev;
+    std::vector<PinBuf*> pin;
+    // what a re-lay or a reallocation found in the guard it was about to overwrite, kept for the next check
+    std::vector<gaguard::Violation> pending;
+};
+
 // Device memory that grows on demand and is released with its owner (a context or a pipeline slot): nothing copies
 // one, FillBufs, Band and the launches' argument structs hold pointers into it.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
     bool uncached = false;
+    // guard mode (nullptr: off): p and cap are what they are without it -- the kernels' pointer and budget -- inside
+    // an allocation of goff + cap + goff bytes; size is the last request, where the rear guard begins
+    GuardCfg* g = nullptr;
+    size_t goff = 0, size = 0;
+    std::string name;
     explicit DevBuf(bool uncached_ = false) : uncached(uncached_) {}
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
     ~DevBuf() { release(); }
     hipError_t ensure(size_t bytes) {
+        if (g) return ensure_guarded(bytes);
         if (bytes <= cap && p) return hipSuccess;
         if (p) (void)hipFree(p);
         p = nullptr;
@@ -73,11 +98,14 @@ struct DevBuf {
         if (e == hipSuccess) cap = want;
         return e;
     }
+    hipError_t ensure_guarded(size_t bytes);
     void release() {
-        if (p) (void)hipFree(p);
+        if (p) (void)hipFree(static_cast<uint8_t*>(p) - goff);
         p = nullptr;
-        cap = 0;
+        cap = goff = size = 0;
     }
+    // release() outside the destructor: in guard mode what the guards caught is kept for the next check first
+    void release_checked();
     template <typename T>
     T* as() const { return reinterpret_cast<T*>(p); }
 };
@@ -90,13 +118,17 @@ struct PinBuf {
     void* dp = nullptr;  // the same memory as the device sees it (mapped buffers), looked up once per allocation
     size_t cap = 0;
     bool mapped = false;
+    GuardCfg* g = nullptr;  // guard mode, as DevBuf's
+    size_t goff = 0, size = 0;
+    std::string name;
     explicit PinBuf(bool mapped_ = false) : mapped(mapped_) {}
     PinBuf(const PinBuf&) = delete;
     PinBuf& operator=(const PinBuf&) = delete;
     ~PinBuf() {
-        if (p) (void)hipHostFree(p);
+        if (p) (void)hipHostFree(static_cast<uint8_t*>(p) - goff);
     }
     hipError_t ensure(size_t bytes) {
+        if (g) return ensure_guarded(bytes);
         if (bytes <= cap && p) return hipSuccess;
         void* old = p;
         p = dp = nullptr;
@@ -109,11 +141,139 @@ struct PinBuf {
         if (e == hipSuccess) cap = bytes;
         return e;
     }
+    hipError_t ensure_guarded(size_t bytes);
     template <typename T>
     T* host() const { return static_cast<T*>(p); }
     template <typename T>
     T* dev() const { return static_cast<T*>(dp); }
 };
+
+// One guard of a buffer against the pattern: `img` is the guard's G bytes as the host reads them.
+void guard_scan(GuardCfg* g, const std::string& name, int side, const uint8_t* img, size_t size,
+                std::vector<gaguard::Violation>& out) {
+    gaguard::Violation v;
+    if (gaguard::make_violation(name, side, gaguard::scan(img, g->G, g->fill), size, g->G, v)) out.push_back(v);
+}
+
+// A device buffer's two guards, copied back (the caller has made sure no kernel still writes near them).
+hipError_t guard_scan_dev(const DevBuf& b, bool front, bool rear, std::vector<gaguard::Violation>& out) {
+    if (!b.p || !b.g) return hipSuccess;
+    const size_t G = b.g->G;
+    std::vector<uint8_t> img(G);
+    const uint8_t* pay = static_cast<const uint8_t*>(b.p);
+    if (front) {
+        if (hipError_t e = hipMemcpy(img.data(), pay - G, G, hipMemcpyDeviceToHost); e != hipSuccess) return e;
+        guard_scan(b.g, b.name, gaguard::kFront, img.data(), b.size, out);
+    }
+    if (rear) {
+        if (hipError_t e = hipMemcpy(img.data(), pay + b.size, G, hipMemcpyDeviceToHost); e != hipSuccess) return e;
+        guard_scan(b.g, b.name, gaguard::kRear, img.data(), b.size, out);
+    }
+    return hipSuccess;
+}
+void guard_scan_pin(const PinBuf& b, bool front, bool rear, std::vector<gaguard::Violation>& out) {
+    if (!b.p || !b.g) return;
+    const uint8_t* pay = static_cast<const uint8_t*>(b.p);
+    if (front) guard_scan(b.g, b.name, gaguard::kFront, pay - b.g->G, b.size, out);
+    if (rear) guard_scan(b.g, b.name, gaguard::kRear, pay + b.size, b.size, out);
+}
+
+// A re-lay or a reallocation rewrites guard bytes that kernels of earlier launches may have hit, and it fills memory
+// that launches still in flight may be writing (a band's fill behind the previous band's): so the device
+// is idle first.  Under the chained pipeline that wait would never end (its persistent kernel waits for this thread,
+// up to its 60 s limit), and so would the null-stream memset after it: every buffer has its final size before the
+// chain starts, and a request for another size while it runs is an error, not a stall.
+hipError_t guard_quiesce(GuardCfg* g) {
+    if (g->in_chain) return hipErrorNotSupported;
+    return hipDeviceSynchronize();
+}
+
+hipError_t DevBuf::ensure_guarded(size_t bytes) {
+    const size_t G = g->G;
+    if (bytes <= cap && p) {
+        if (bytes == size) return hipSuccess;
+        // the same allocation for another size: what the old rear guard caught is kept, then the pattern goes from
+        // the smaller of the two ends to the new guard's end.  Bytes below both ends keep their contents.
+        if (hipError_t e = guard_quiesce(g); e != hipSuccess) return e;
+        if (hipError_t e = guard_scan_dev(*this, false, true, g->pending); e != hipSuccess) return e;
+        const gaguard::Range r = gaguard::relay_range(size, bytes, G);
+        if (hipError_t e = hipMemset(static_cast<uint8_t*>(p) + r.lo, g->fill, r.hi - r.lo); e != hipSuccess) return e;
+        size = bytes;
+        return hipStreamSynchronize(nullptr);  // the context's streams do not wait for the null stream
+    }
+    if (p) {
+        if (hipError_t e = guard_quiesce(g); e != hipSuccess) return e;
+        if (hipError_t e = guard_scan_dev(*this, true, true, g->pending); e != hipSuccess) return e;
+    }
+    release();
+    const size_t want = std::max<size_t>(bytes, 256), total = gaguard::alloc_bytes(want, G);
+    void* raw = nullptr;
+    hipError_t e = uncached ? hipExtMallocWithFlags(&raw, total, hipDeviceMallocUncached) : hipMalloc(&raw, total);
+    if (e != hipSuccess) return e;
+    uint8_t* r8 = static_cast<uint8_t*>(raw);
+    p = r8 + gaguard::payload_off(G);
+    goff = G;
+    cap = want;
+    size = bytes;
+    if (g->poison) {
+        e = hipMemset(r8, g->fill, total);
+    } else {
+        e = hipMemset(r8, g->fill, G);
+        if (e == hipSuccess) e = hipMemset(r8 + gaguard::rear_off(bytes, G), g->fill, total - gaguard::rear_off(bytes, G));
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    return e;
+}
+
+void DevBuf::release_checked() {
+    // best effort: the caller is on an error path of its own, and a scan that fails loses only this evidence
+    if (g && p && guard_quiesce(g) == hipSuccess) (void)guard_scan_dev(*this, true, true, g->pending);
+    release();
+}
+
+hipError_t PinBuf::ensure_guarded(size_t bytes) {
+    const size_t G = g->G;
+    if (bytes <= cap && p) {
+        if (bytes == size) return hipSuccess;
+        if (hipError_t e = guard_quiesce(g); e != hipSuccess) return e;
+        guard_scan_pin(*this, false, true, g->pending);
+        const gaguard::Range r = gaguard::relay_range(size, bytes, G);
+        std::memset(static_cast<uint8_t*>(p) + r.lo, g->fill, r.hi - r.lo);
+        size = bytes;
+        return hipSuccess;
+    }
+    if (p) {
+        if (hipError_t e = guard_quiesce(g); e != hipSuccess) return e;
+        guard_scan_pin(*this, true, true, g->pending);
+    }
+    void* old = p ? static_cast<uint8_t*>(p) - goff : nullptr;
+    p = dp = nullptr;
+    cap = goff = size = 0;
+    if (old)
+        if (hipError_t e = hipHostFree(old); e != hipSuccess) return e;
+    const unsigned flags = mapped ? hipHostMallocMapped | hipHostMallocCoherent : hipHostMallocDefault;
+    const size_t total = gaguard::alloc_bytes(bytes, G);
+    void* raw = nullptr;
+    void* rawd = nullptr;
+    hipError_t e = hipHostMalloc(&raw, total, flags);
+    if (e != hipSuccess) return e;
+    uint8_t* r8 = static_cast<uint8_t*>(raw);
+    p = r8 + gaguard::payload_off(G);
+    goff = G;
+    cap = size = bytes;
+    if (mapped) {
+        e = hipHostGetDevicePointer(&rawd, raw, 0);
+        if (e != hipSuccess) return e;
+        dp = static_cast<uint8_t*>(rawd) + gaguard::payload_off(G);
+    }
+    if (g->poison) {
+        std::memset(r8, g->fill, total);
+    } else {
+        std::memset(r8, g->fill, G);
+        std::memset(r8 + gaguard::rear_off(bytes, G), g->fill, G);
+    }
+    return hipSuccess;
+}
 
 // The buffers one fill writes, and its two timing events (created and destroyed by their owner): the context has
 // one set, every pipeline slot one of its own, so that fills can run side by side.
@@ -295,6 +455,7 @@ struct ga_ctx {
     hipEvent_t ev_up = nullptr;
     gaplan::FillPlan rc_plan;  // the plan of the fill the recompute walk reads (rc_fill): stripes, spacing
     bool rc_jump = false;  // the last recompute walk was the tie-to-tie walk (jump entries)
+    GuardCfg guard;        // guard mode (G = 0: off; guard_attach names and registers every buffer above)
 };
 
 namespace {
@@ -304,6 +465,96 @@ int check_ctx(ga_ctx* c) {
     hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return fail(GA_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
     return GA_OK;
+}
+
+// ---------------------------------------------------------------- guard mode
+// Every buffer of the context and of its pipeline slots under its member name ("colck", "fb.tb", "pipe2.fb.tb").
+// `link` stays outside: it is exported through an IPC handle, which names the allocation and not a pointer inside
+// it, so an importer would land on the front guard; ga_debug_guard_report lists it as unguarded.
+template <typename F, typename P>
+void guard_each(ga_ctx* c, F&& dev, P&& pin) {
+    auto fillbufs = [&](FillBufs& fb, const std::string& pre) {
+#define GA_FB(x) dev(fb.x, pre + "fb." #x)
+        GA_FB(tb), GA_FB(hand), GA_FB(flags), GA_FB(out_last), GA_FB(GVp), GA_FB(GHp), GA_FB(top), GA_FB(left);
+        GA_FB(bnd_row), GA_FB(bnd_col), GA_FB(meta), GA_FB(bscr);
+#undef GA_FB
+    };
+#define GA_D(x) dev(c->x, #x)
+#define GA_P(x) pin(c->x, #x)
+    GA_D(a), GA_D(b), GA_D(sub), GA_D(gh), GA_D(gv), GA_D(qp), GA_D(full), GA_D(rng), GA_D(ckpt), GA_D(ops), GA_D(result);
+    fillbufs(c->fb, "");
+    GA_D(halo_in), GA_D(dbg), GA_D(wdbg), GA_D(colck), GA_D(stck), GA_D(rc_tb), GA_D(rc_flags), GA_D(rc_pos), GA_D(rc_own);
+    GA_D(qprof), GA_D(bt_codes), GA_D(bt_items), GA_D(bt_sub), GA_D(bt_gh), GA_D(bt_gv), GA_D(bt_ticket), GA_D(bt_out);
+    GA_D(bt_scratch), GA_D(bt_witems), GA_D(bt_rng), GA_D(bt_ops), GA_D(bt_walk), GA_D(bt_tb), GA_D(bt_ritems);
+    GA_D(bt_rstatus), GA_D(bt_rbase), GA_D(jlut);
+    GA_P(res_pin), GA_P(prog), GA_P(pipe_pin), GA_P(chain_tab), GA_P(chain_ctl), GA_P(chain_io), GA_P(rc_ops_pin);
+    GA_P(rc_ops_prog), GA_P(up_pin);
+#undef GA_D
+#undef GA_P
+    for (int s = 0; s < 6; s++) {
+        auto& sl = c->pipe[s];
+        const std::string pre = "pipe" + std::to_string(s) + ".";
+        fillbufs(sl.fb, pre);
+        dev(sl.rng, pre + "rng"), dev(sl.ops, pre + "ops"), dev(sl.result, pre + "result");
+        pin(sl.tab_pin, pre + "tab_pin");
+    }
+}
+static_assert(sizeof(ga_ctx::pipe) / sizeof(ga_ctx::PipeSlot) == 6, "guard_each walks six pipeline slots");
+
+void guard_attach(ga_ctx* c) {
+    GuardCfg* g = &c->guard;
+    guard_each(
+        c,
+        [&](DevBuf& b, const std::string& name) {
+            b.g = g;
+            b.name = name;
+            g->dev.push_back(&b);
+        },
+        [&](PinBuf& b, const std::string& name) {
+            b.g = g;
+            b.name = name;
+            g->pin.push_back(&b);
+        });
+}
+
+// Every guard of the context against the pattern, with what earlier re-lays kept: the device is idle first (a
+// synchronous entry has waited for its own work; this also covers a pipeline's other streams).  `relay` restores the
+// pattern where it was found changed, so that one stray store is reported once and the context stays usable.
+int guard_collect(ga_ctx* c, bool relay, std::vector<gaguard::Violation>& out) {
+    GuardCfg* g = &c->guard;
+    out = g->pending;
+    if (relay) g->pending.clear();
+    HIPCHK(hipDeviceSynchronize());
+    for (DevBuf* b : g->dev) {
+        const size_t n0 = out.size();
+        HIPCHK(guard_scan_dev(*b, true, true, out));
+        if (relay)
+            for (size_t k = n0; k < out.size(); k++) {
+                uint8_t* at = b->as<uint8_t>() + (out[k].side == gaguard::kFront ? -(ptrdiff_t)g->G : (ptrdiff_t)b->size);
+                HIPCHK(hipMemset(at, g->fill, g->G));
+            }
+    }
+    for (PinBuf* b : g->pin) {
+        const size_t n0 = out.size();
+        guard_scan_pin(*b, true, true, out);
+        if (relay)
+            for (size_t k = n0; k < out.size(); k++)
+                std::memset(b->host<uint8_t>() + (out[k].side == gaguard::kFront ? -(ptrdiff_t)g->G : (ptrdiff_t)b->size),
+                            g->fill, g->G);
+    }
+    if (relay) HIPCHK(hipStreamSynchronize(nullptr));
+    return GA_OK;
+}
+
+// The end of a synchronous entry that may have run kernels: its own result, or GA_E_GUARD with the report.
+int guard_end(ga_ctx* c, int rc) {
+    if (!c || !c->guard.G) return rc;
+    const std::string msg = rc == GA_OK ? std::string() : g_err;
+    std::vector<gaguard::Violation> vs;
+    if (guard_collect(c, true, vs) != GA_OK) return rc != GA_OK ? fail(rc, msg) : GA_E_HIP;
+    if (vs.empty()) return rc != GA_OK ? fail(rc, msg) : GA_OK;
+    return fail(GA_E_GUARD, "guard violated: " + gaguard::describe(vs) +
+                                (rc == GA_OK ? std::string() : " (the call itself failed with " + std::to_string(rc) + ": " + msg + ")"));
 }
 
 // The loaded problem or slab as the fill planner sees it (ga_plan.h).
@@ -518,9 +769,9 @@ int fill_buffers(ga_ctx* c, const FillJob& j) {
             nb++;
             if (e != hipSuccess) {
                 (void)hipGetLastError();
-                c->colck.release();
-                c->stck.release();
-                c->rc_tb.release();
+                c->colck.release_checked();
+                c->stck.release_checked();
+                c->rc_tb.release_checked();
                 return fail(e == hipErrorOutOfMemory ? GA_E_NOMEM : GA_E_HIP,
                             std::string("recompute checkpoints: ") + hipGetErrorString(e));
             }
@@ -1034,7 +1285,9 @@ int rc_walk_launch(ga_ctx* c, int64_t ntab, const WalkStart& st, WalkBufs& wb) {
     // the cache slots' owner tags (ga::rc_slot_tag) carry the epoch's ready value: cleared with the flags
     const size_t nown = (size_t)ga::RC_CACHE_I * ga::RC_CACHE_S * sizeof(unsigned long long);
     if (c->rc_flags.cap < nflags * sizeof(unsigned) || c->rc_own.cap < nown || c->rc_epoch >= 0x7ffffff0u) {
-        HIPCHK(c->rc_flags.ensure(nflags * sizeof(unsigned)));
+        // the flags are cleared here and then reused, by any later problem that fits, at the buffer's whole capacity:
+        // the request names all of it
+        HIPCHK(c->rc_flags.ensure(std::max<size_t>({nflags * sizeof(unsigned), c->rc_flags.cap, 256})));
         HIPCHK(hipMemsetAsync(c->rc_flags.p, 0, c->rc_flags.cap, wb.stream));
         HIPCHK(c->rc_own.ensure(nown));
         HIPCHK(hipMemsetAsync(c->rc_own.p, 0, nown, wb.stream));
@@ -1068,6 +1321,13 @@ int rc_walk_launch(ga_ctx* c, int64_t ntab, const WalkStart& st, WalkBufs& wb) {
     r.colck = c->colck.as<int2>();
     r.stck = c->stck.as<int2>();
     r.stck_every = c->rc_plan.rc_every;
+    // rc_windows reads the edge rows t0 + RC_EDGE_FIRST and up with t0 = (R0 / stck_every) * stck_every >= 0: never
+    // row 0 of a colck stripe, which the fill's lean ramp leaves with a ramp value (ga_lane.hip).  A spacing that is
+    // not positive would make t0 meaningless.
+    static_assert(ga::RC_EDGE_FIRST >= 1, "the recompute blocks must not read colck row 0 (lean ramp, ga_lane.hip)");
+    if (r.stck_every < 64 || (r.stck_every & (r.stck_every - 1)))
+        return fail(GA_E_STATE, "recompute walk: checkpoint spacing " + std::to_string(r.stck_every) +
+                                    " is not a power of two >= 64 (the edge window's rows >= t0 + 1 rest on it)");
     r.tb = c->rc_tb.as<uint8_t>();
     r.TC = w.TC;
     r.m = (int)m;
@@ -1506,6 +1766,7 @@ int align_chain(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, con
         producer.join();
         if (rc != GA_OK) __atomic_store_n(ctl + 2, 1u, __ATOMIC_RELEASE);  // the chain exits at its next wait
         (void)hipStreamSynchronize(ws);
+        c->guard.in_chain = false;
         if (rc != GA_OK)
             for (int f = 0; f < F; f++) (void)hipStreamSynchronize(fs[f]);
         return rc;
@@ -1546,6 +1807,7 @@ int align_chain(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, con
         A.count = count;
         A.S = S;
         HIPCHK(hipEventRecord(c->pipe[0].w0, ws));
+        c->guard.in_chain = true;  // until stop(): guard mode must not wait for the device from here on
         ga::launch_walk_chain(ws, A);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(c->pipe[0].w1, ws));
@@ -2090,6 +2352,37 @@ int ga_ctx_create_opts(int device, const char* options, ga_ctx** out) {
         if (it != knobs.end() && (atoll(it->second.c_str()) < 1 || atoll(it->second.c_str()) > 1024))
             return fail(GA_E_ARG, "GA_BATCH_RNG_WORD_CAP must be in [1, 1024], not '" + it->second + "'");
     }
+    // guard mode: options only (none is in kEnvKnobs)
+    size_t guard_bytes = 0;
+    long guard_fill = (long)gaguard::kDefaultFill;
+    bool guard_poison = false;
+    {
+        auto whole = [](const std::string& v, long long& out) {
+            char* end = nullptr;
+            out = strtoll(v.c_str(), &end, 0);
+            return !v.empty() && end && *end == 0;
+        };
+        long long v = 0;
+        auto it = knobs.find("GA_GUARD_BYTES");
+        if (it != knobs.end()) {
+            if (!whole(it->second, v) || !gaguard::valid_guard_bytes(v))
+                return fail(GA_E_ARG, "GA_GUARD_BYTES must be 0 or a multiple of 256 up to 2^20, not '" + it->second + "'");
+            guard_bytes = (size_t)v;
+        }
+        it = knobs.find("GA_GUARD_FILL");
+        if (it != knobs.end()) {
+            if (!whole(it->second, v) || !gaguard::valid_fill(v))
+                return fail(GA_E_ARG, "GA_GUARD_FILL must be a byte value in [0, 255], not '" + it->second + "'");
+            guard_fill = (long)v;
+        }
+        it = knobs.find("GA_GUARD_POISON");
+        if (it != knobs.end()) {
+            if (it->second != "0" && it->second != "1")
+                return fail(GA_E_ARG, "GA_GUARD_POISON must be 0 or 1, not '" + it->second + "'");
+            guard_poison = it->second == "1";
+            if (guard_poison && !guard_bytes) return fail(GA_E_ARG, "GA_GUARD_POISON=1 needs GA_GUARD_BYTES");
+        }
+    }
     // the planner's self-test plans with the kernels' LDS formulas as ga_plan.h restates them: they must be the kernels'
     for (int every : {64, 128, 4096})
         for (int w : {1, 2, 4, 8})
@@ -2103,6 +2396,12 @@ int ga_ctx_create_opts(int device, const char* options, ga_ctx** out) {
     ga_ctx* c = new ga_ctx();
     c->device = device;
     c->knobs = std::move(knobs);
+    if (guard_bytes) {
+        c->guard.G = guard_bytes;
+        c->guard.fill = (uint8_t)guard_fill;
+        c->guard.poison = guard_poison;
+        guard_attach(c);
+    }
     {
         // hardware queues per priority pool: what the HIP runtime read when it started, i.e. the variable
         // as the process first saw it here (a later change, e.g. a module setting it after HIP started,
@@ -2153,6 +2452,12 @@ void ga_ctx_destroy(ga_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
+    if (c->guard.G) {
+        // the last look at the guards: nobody is left to take an error code
+        std::vector<gaguard::Violation> vs;
+        if (guard_collect(c, false, vs) == GA_OK && !vs.empty())
+            std::fprintf(stderr, "globalign_amd: guard violated at ga_ctx_destroy: %s\n", gaguard::describe(vs).c_str());
+    }
     if (c->peer_link) (void)hipIpcCloseMemHandle(c->peer_link);
     if (c->ev_up) (void)hipEventDestroy(c->ev_up);
     if (c->ev_fill) (void)hipEventDestroy(c->ev_fill);
@@ -2177,14 +2482,16 @@ void ga_ctx_destroy(ga_ctx* c) {
     delete c;  // the device and pinned buffers free themselves (DevBuf, PinBuf)
 }
 
-int ga_problem_set(ga_ctx* c, const uint8_t* a, int64_t m, const uint8_t* b, int64_t n, const ga_costs* cs,
-                   const int32_t* row0, const int32_t* col0) {
+// ga_problem_set and the other entries that run kernels and wait for them: the exported definitions, which end each
+// with guard mode's check, stand together at the end of the file (guard mode); the bodies are the *_impl.
+static int problem_set_impl(ga_ctx* c, const uint8_t* a, int64_t m, const uint8_t* b, int64_t n, const ga_costs* cs,
+                            const int32_t* row0, const int32_t* col0) {
     if (int r = check_ctx(c)) return r;
     c->slab = false;
     return load_problem(c, a, m, b, n, cs, row0, col0, 0, n);
 }
 
-int ga_problem_fill(ga_ctx* c, int32_t flags, int64_t* cost_out, int32_t* full_out) {
+static int problem_fill_impl(ga_ctx* c, int32_t flags, int64_t* cost_out, int32_t* full_out) {
     if (c) c->rc_used = false;
     if (int r = check_ctx(c)) return r;
     if (c->slab) return fail(GA_E_STATE, "slab contexts use ga_slab_fill_launch");
@@ -2198,9 +2505,9 @@ int ga_batch_costs(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int6
     return ga_batch_costs_ex(c, codes, seq_off, nseq, pair_a, pair_b, nullptr, npairs, cs, cost_out);
 }
 
-int ga_batch_costs_ex(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
-                      const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
-                      int64_t* cost_out) {
+static int batch_costs_ex_impl(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq,
+                               const int32_t* pair_a, const int32_t* pair_b, const int32_t* pair_max_cost,
+                               int64_t npairs, const ga_costs* cs, int64_t* cost_out) {
     if (int r = check_ctx(c)) return r;
     if (npairs == 0) return GA_OK;  // an empty batch: no launch
     if (!cost_out) return fail(GA_E_ARG, "null argument");
@@ -2255,10 +2562,11 @@ int ga_batch_align(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int6
                              out_mid, out_b, out_off, out_len, tb_status, cost_out, GA_BATCH_TABLES_DEFAULT);
 }
 
-int ga_batch_align_ex(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
-                      const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
-                      const uint64_t* seeds, const char* chars, char* out_a, char* out_mid, char* out_b,
-                      const int64_t* out_off, int64_t* out_len, int32_t* tb_status, int64_t* cost_out, uint32_t flags) {
+static int batch_align_ex_impl(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq,
+                               const int32_t* pair_a, const int32_t* pair_b, const int32_t* pair_max_cost,
+                               int64_t npairs, const ga_costs* cs, const uint64_t* seeds, const char* chars,
+                               char* out_a, char* out_mid, char* out_b, const int64_t* out_off, int64_t* out_len,
+                               int32_t* tb_status, int64_t* cost_out, uint32_t flags) {
     if (int r = check_ctx(c)) return r;
     if ((flags & ~GA_BATCH_TABLES_MASK) || (flags & GA_BATCH_TABLES_MASK) > GA_BATCH_TABLES_DEVICE)
         return fail(GA_E_ARG, "bad flags: bits 0-1 choose the tables (0 default, 1 host, 2 device)");
@@ -2459,8 +2767,8 @@ int ga_batch_align_info(ga_ctx* c, int32_t* out4) {
     return GA_OK;
 }
 
-int ga_debug_pair_tables(ga_ctx* c, const uint64_t* seeds, const int32_t* steps, int64_t nitems, int32_t route,
-                         uint32_t* tab_out, int32_t* status_out) {
+static int debug_pair_tables_impl(ga_ctx* c, const uint64_t* seeds, const int32_t* steps, int64_t nitems, int32_t route,
+                                  uint32_t* tab_out, int32_t* status_out) {
     if (int r = check_ctx(c)) return r;
     if (route != GA_BATCH_TABLES_HOST && route != GA_BATCH_TABLES_DEVICE)
         return fail(GA_E_ARG, "route must be 1 (host) or 2 (device)");
@@ -2537,7 +2845,7 @@ int ga_debug_seed_state(uint64_t seed, uint32_t* state_out) {
     return GA_OK;
 }
 
-int ga_problem_set_cells(ga_ctx* c, const int32_t* cells, int64_t* cost_out) {
+static int problem_set_cells_impl(ga_ctx* c, const int32_t* cells, int64_t* cost_out) {
     if (int r = check_ctx(c)) return r;
     if (!c->loaded) return fail(GA_E_STATE, "no problem loaded");
     if (c->slab) return fail(GA_E_STATE, "slab contexts fill their own cells");
@@ -2561,8 +2869,8 @@ int ga_problem_set_cells(ga_ctx* c, const int32_t* cells, int64_t* cost_out) {
     return GA_OK;
 }
 
-int ga_problem_traceback(ga_ctx* c, uint32_t* mt_state, const char* a_chr, const char* b_chr, char* oa, char* om,
-                         char* ob, int64_t cap, int64_t* out_len, int32_t* tb_status) {
+static int problem_traceback_impl(ga_ctx* c, uint32_t* mt_state, const char* a_chr, const char* b_chr, char* oa,
+                                  char* om, char* ob, int64_t cap, int64_t* out_len, int32_t* tb_status) {
     if (int r = check_ctx(c)) return r;
     if (!c->filled_tb) return fail(GA_E_STATE, "traceback needs a GA_FILL_TRACEBACK fill first");
     if (!mt_state || !a_chr || !b_chr || !oa || !om || !ob || !out_len || !tb_status) return fail(GA_E_ARG, "null argument");
@@ -2572,8 +2880,8 @@ int ga_problem_traceback(ga_ctx* c, uint32_t* mt_state, const char* a_chr, const
     return finish_walk(c, R, mt_state, a_chr, b_chr, oa, om, ob, cap, out_len, tb_status);
 }
 
-int ga_problem_align(ga_ctx* c, uint32_t* mt_state, const char* a_chr, const char* b_chr, char* oa, char* om,
-                     char* ob, int64_t cap, int64_t* out_len, int32_t* tb_status, int64_t* cost_out) {
+static int problem_align_impl(ga_ctx* c, uint32_t* mt_state, const char* a_chr, const char* b_chr, char* oa, char* om,
+                              char* ob, int64_t cap, int64_t* out_len, int32_t* tb_status, int64_t* cost_out) {
     if (int r = check_ctx(c)) return r;
     if (c->slab) return fail(GA_E_STATE, "slab contexts use ga_slab_fill_launch");
     if (!mt_state || !a_chr || !b_chr || !oa || !om || !ob || !out_len || !tb_status) return fail(GA_E_ARG, "null argument");
@@ -2612,9 +2920,9 @@ int ga_problem_align(ga_ctx* c, uint32_t* mt_state, const char* a_chr, const cha
     return rc;
 }
 
-int ga_problem_align_many(ga_ctx* c, int32_t count, uint32_t* mt_state, const char* a_chr, const char* b_chr,
-                          char* oa, char* om, char* ob, int64_t cap, int64_t* out_len, int32_t* tb_status,
-                          int64_t* cost_out) {
+static int problem_align_many_impl(ga_ctx* c, int32_t count, uint32_t* mt_state, const char* a_chr, const char* b_chr,
+                                   char* oa, char* om, char* ob, int64_t cap, int64_t* out_len, int32_t* tb_status,
+                                   int64_t* cost_out) {
     if (int r = check_ctx(c)) return r;
     if (c->slab) return fail(GA_E_STATE, "slab contexts use ga_slab_fill_launch");
     if (count < 1) return fail(GA_E_ARG, "count must be >= 1");
@@ -2646,8 +2954,8 @@ int ga_problem_align_many(ga_ctx* c, int32_t count, uint32_t* mt_state, const ch
 }
 
 // ---------------------------------------------------------------- slabs
-int ga_problem_set_slab(ga_ctx* c, const uint8_t* a, int64_t m, const uint8_t* b, int64_t n, const ga_costs* cs,
-                        int64_t col_begin, int64_t col_end) {
+static int problem_set_slab_impl(ga_ctx* c, const uint8_t* a, int64_t m, const uint8_t* b, int64_t n,
+                                 const ga_costs* cs, int64_t col_begin, int64_t col_end) {
     if (int r = check_ctx(c)) return r;
     c->slab = true;
     c->halo_in_ext = c->halo_out_ext = nullptr;
@@ -2776,7 +3084,7 @@ int ga_slab_fill_launch(ga_ctx* c, int32_t flags) {
     return enqueue_fill(c, flags & GA_FILL_TRACEBACK);
 }
 
-int ga_slab_fill_finish(ga_ctx* c, int64_t* cost_out) {
+static int slab_fill_finish_impl(ga_ctx* c, int64_t* cost_out) {
     if (int r = check_ctx(c)) return r;
     return finish_fill(c, cost_out, nullptr);
 }
@@ -2791,8 +3099,8 @@ int ga_slab_walk_prepare(ga_ctx* c, const uint32_t* mt_state) {
     return GA_OK;
 }
 
-int ga_slab_walk(ga_ctx* c, ga_walk_state* st, const char* a_chr, const char* b_chr, char* oa, char* om, char* ob,
-                 int64_t cap, int64_t* out_len) {
+static int slab_walk_impl(ga_ctx* c, ga_walk_state* st, const char* a_chr, const char* b_chr, char* oa, char* om,
+                          char* ob, int64_t cap, int64_t* out_len) {
     if (int r = check_ctx(c)) return r;
     if (!st || !a_chr || !b_chr || !oa || !om || !ob || !out_len) return fail(GA_E_ARG, "null argument");
     if (!c->filled_tb) return fail(GA_E_STATE, "slab walk needs a GA_FILL_TRACEBACK fill first");
@@ -3009,7 +3317,132 @@ int ga_last_timings(ga_ctx* c, float* out4) {
     return GA_OK;
 }
 
+// ---- guard mode ----
+// the entries that run kernels and wait for them end with the guards' check (guard mode off: one branch)
+int ga_problem_set(ga_ctx* c, const uint8_t* a, int64_t m, const uint8_t* b, int64_t n, const ga_costs* cs,
+                   const int32_t* row0, const int32_t* col0) {
+    return guard_end(c, problem_set_impl(c, a, m, b, n, cs, row0, col0));
+}
+
+int ga_problem_fill(ga_ctx* c, int32_t flags, int64_t* cost_out, int32_t* full_out) {
+    return guard_end(c, problem_fill_impl(c, flags, cost_out, full_out));
+}
+
+int ga_batch_costs_ex(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                      const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                      int64_t* cost_out) {
+    return guard_end(c, batch_costs_ex_impl(c, codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs,
+                                            cost_out));
+}
+
+int ga_batch_align_ex(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                      const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                      const uint64_t* seeds, const char* chars, char* out_a, char* out_mid, char* out_b,
+                      const int64_t* out_off, int64_t* out_len, int32_t* tb_status, int64_t* cost_out, uint32_t flags) {
+    return guard_end(c, batch_align_ex_impl(c, codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, seeds,
+                                            chars, out_a, out_mid, out_b, out_off, out_len, tb_status, cost_out,
+                                            flags));
+}
+
+int ga_debug_pair_tables(ga_ctx* c, const uint64_t* seeds, const int32_t* steps, int64_t nitems, int32_t route,
+                         uint32_t* tab_out, int32_t* status_out) {
+    return guard_end(c, debug_pair_tables_impl(c, seeds, steps, nitems, route, tab_out, status_out));
+}
+
+int ga_problem_set_cells(ga_ctx* c, const int32_t* cells, int64_t* cost_out) {
+    return guard_end(c, problem_set_cells_impl(c, cells, cost_out));
+}
+
+int ga_problem_traceback(ga_ctx* c, uint32_t* mt_state, const char* a_chr, const char* b_chr, char* oa, char* om,
+                         char* ob, int64_t cap, int64_t* out_len, int32_t* tb_status) {
+    return guard_end(c, problem_traceback_impl(c, mt_state, a_chr, b_chr, oa, om, ob, cap, out_len, tb_status));
+}
+
+int ga_problem_align(ga_ctx* c, uint32_t* mt_state, const char* a_chr, const char* b_chr, char* oa, char* om,
+                     char* ob, int64_t cap, int64_t* out_len, int32_t* tb_status, int64_t* cost_out) {
+    return guard_end(c, problem_align_impl(c, mt_state, a_chr, b_chr, oa, om, ob, cap, out_len, tb_status, cost_out));
+}
+
+int ga_problem_align_many(ga_ctx* c, int32_t count, uint32_t* mt_state, const char* a_chr, const char* b_chr,
+                          char* oa, char* om, char* ob, int64_t cap, int64_t* out_len, int32_t* tb_status,
+                          int64_t* cost_out) {
+    return guard_end(c, problem_align_many_impl(c, count, mt_state, a_chr, b_chr, oa, om, ob, cap, out_len, tb_status,
+                                                cost_out));
+}
+
+int ga_problem_set_slab(ga_ctx* c, const uint8_t* a, int64_t m, const uint8_t* b, int64_t n, const ga_costs* cs,
+                        int64_t col_begin, int64_t col_end) {
+    return guard_end(c, problem_set_slab_impl(c, a, m, b, n, cs, col_begin, col_end));
+}
+
+int ga_slab_fill_finish(ga_ctx* c, int64_t* cost_out) {
+    return guard_end(c, slab_fill_finish_impl(c, cost_out));
+}
+
+int ga_slab_walk(ga_ctx* c, ga_walk_state* st, const char* a_chr, const char* b_chr, char* oa, char* om, char* ob,
+                 int64_t cap, int64_t* out_len) {
+    return guard_end(c, slab_walk_impl(c, st, a_chr, b_chr, oa, om, ob, cap, out_len));
+}
+
+int ga_debug_guard_report(ga_ctx* c, char* out, int64_t cap, int64_t* needed) {
+    if (int r = check_ctx(c)) return r;
+    if (!needed || (cap > 0 && !out) || cap < 0) return fail(GA_E_ARG, "null argument");
+    if (!c->guard.G) return fail(GA_E_STATE, "guard mode is off (option GA_GUARD_BYTES)");
+    std::vector<gaguard::Violation> vs;
+    if (int r = guard_collect(c, false, vs)) return r;
+    std::string js = "{\"guard_bytes\": " + std::to_string(c->guard.G) + ", \"fill\": " + std::to_string((int)c->guard.fill) +
+                     ", \"poison\": " + (c->guard.poison ? "true" : "false") + ", \"violations\": [";
+    for (size_t k = 0; k < vs.size(); k++)
+        js += std::string(k ? ", " : "") + "{\"name\": \"" + vs[k].name + "\", \"side\": \"" +
+              (vs[k].side == gaguard::kFront ? "front" : "rear") + "\", \"offset\": " + std::to_string(vs[k].offset) +
+              ", \"last\": " + std::to_string(vs[k].last) + ", \"changed\": " + std::to_string(vs[k].changed) +
+              ", \"payload\": " + std::to_string(vs[k].payload) + "}";
+    js += "], \"buffers\": [";
+    bool first = true;
+    auto item = [&](const std::string& name, size_t payload, bool guarded) {
+        js += std::string(first ? "" : ", ") + "{\"name\": \"" + name + "\", \"payload\": " + std::to_string(payload) +
+              ", \"guarded\": " + (guarded ? "true" : "false") + "}";
+        first = false;
+    };
+    for (const DevBuf* b : c->guard.dev)
+        if (b->p) item(b->name, b->size, true);
+    for (const PinBuf* b : c->guard.pin)
+        if (b->p) item(b->name, b->size, true);
+    if (c->link.p) item("link", c->link.cap, false);  // exported by IPC handle: outside guard mode (guard_each)
+    js += "]}";
+    *needed = (int64_t)js.size() + 1;
+    if (cap >= *needed) std::memcpy(out, js.c_str(), js.size() + 1);
+    return GA_OK;
+}
+
+int ga_debug_guard_poke(ga_ctx* c, const char* name, int32_t side, int64_t offset, int64_t nbytes) {
+    if (int r = check_ctx(c)) return r;
+    if (!name) return fail(GA_E_ARG, "null argument");
+    const GuardCfg& g = c->guard;
+    if (!g.G) return fail(GA_E_STATE, "guard mode is off (option GA_GUARD_BYTES)");
+    // inside one guard of an allocation of ours, whatever the caller asks
+    if ((side != gaguard::kFront && side != gaguard::kRear) || offset < 0 || nbytes < 1 || offset >= (int64_t)g.G ||
+        nbytes > (int64_t)g.G - offset)
+        return fail(GA_E_ARG, "ga_debug_guard_poke: side 0 or 1, and [offset, offset + nbytes) inside [0, GA_GUARD_BYTES)");
+    const std::vector<uint8_t> other((size_t)nbytes, (uint8_t)~g.fill);
+    for (DevBuf* b : g.dev)
+        if (b->p && b->name == name) {
+            HIPCHK(hipDeviceSynchronize());
+            uint8_t* at = b->as<uint8_t>() + (side == gaguard::kFront ? -(ptrdiff_t)g.G : (ptrdiff_t)b->size) + offset;
+            HIPCHK(hipMemcpy(at, other.data(), (size_t)nbytes, hipMemcpyHostToDevice));
+            return GA_OK;
+        }
+    for (PinBuf* b : g.pin)
+        if (b->p && b->name == name) {
+            std::memcpy(b->host<uint8_t>() + (side == gaguard::kFront ? -(ptrdiff_t)g.G : (ptrdiff_t)b->size) + offset,
+                        other.data(), (size_t)nbytes);
+            return GA_OK;
+        }
+    return fail(GA_E_ARG, std::string("ga_debug_guard_poke: no allocated guarded buffer named '") + name + "'");
+}
+
 }  // extern "C"
+
 
 namespace ga {
 // The rank sets of a cell from its saturated differences (as ga_walk.h sets_from_code): per level the v_perm

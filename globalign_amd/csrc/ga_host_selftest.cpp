@@ -4,7 +4,8 @@
 //     genrand_uint32) and the dispatcher's level rule (globaligner.py:595-685);
 //   * the problem checks (ga_check.h): argument validation, the int32 range guard, the profile / word widths;
 //   * the fill planner (ga_plan.h): the kernel, geometry and checkpoint spacing of the shapes the project's records
-//     pin (profiles/r06, DESIGN.md 5.2 / 5.6 / 5.8.1, tests/test_gpu_rc_default_width.py), and every error return.
+//     pin (profiles/r06, DESIGN.md 5.2 / 5.6 / 5.8.1, tests/test_gpu_rc_default_width.py), and every error return;
+//   * the guard bands' layout, scan and report (ga_guard.h) on a host model of a guarded buffer.
 // No HIP: the engine's library is tested on the GPU; this binary covers the host logic under the sanitizers.
 //
 //   ga_host_selftest            all checks; exit status 0 when every one passes
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "ga_check.h"
+#include "ga_guard.h"
 #include "ga_plan.h"
 #include "ga_rng.h"
 
@@ -274,6 +276,34 @@ void test_plan() {
         expect_plan("C3 pipeline fill", pl, kLane, 4, 391, 4, 98);
         CHECK(pl.qrows <= 2048, "C3 pipeline fill: %d profile rows", pl.qrows);
     }
+    {
+        // the guard tests' edge sweep (tests/test_gpu_guard.py): every shape of the recompute walk's cross plans the
+        // lane kernel at the width asked for, and so does every shape of the lane fills' sweep, score only at 1 to 8
+        // columns per lane and with traceback words at 1 to 4 -- none is declined
+        for (int td : {1, 2, 4, 8}) {
+            Knobs kn = unset;
+            kn.lane_T_req = td;
+            const int64_t w = 64 * td, k = (256 + 1 + w - 1) / w;
+            for (int64_t r : {1, 17, 48, 63, 64, 65, 130})
+                for (int64_t n : {(int64_t)256, k * w - 1, k * w, k * w + 1, (k + 2) * w + 17}) {
+                    const FillPlan pl = plan_fill(shape(256 + r, n, 5), rc, kn, kLds);
+                    CHECK(pl.err == GA_OK && pl.kind == kLane && pl.T == td && pl.nstripes == (n + w - 1) / w,
+                          "guard sweep rc %lld x %lld at %d columns per lane: error %d kind %d T %d", (long long)(256 + r),
+                          (long long)n, td, pl.err, pl.kind, pl.T);
+                }
+            kn.diag_req = 3;  // GA_FILL_MODE=lane
+            kn.nwc_req = 4;
+            for (int64_t m : {1, 17, 48, 63, 64, 65, 130})
+                for (int64_t n : {(int64_t)1, w - 1, w, w + 1, 3 * w + 17})
+                    for (const Request& rq : {score, tb}) {
+                        if (rq.tb && td == 8) continue;  // no traceback-word variant at 8 columns per lane
+                        const FillPlan pl = plan_fill(shape(m, n, 5), rq, kn, kLds);
+                        CHECK(pl.err == GA_OK && pl.kind == kLane && pl.T == td && pl.nwc == 4,
+                              "guard sweep lane %lld x %lld at %d columns per lane, tb %d: error %d kind %d T %d",
+                              (long long)m, (long long)n, td, (int)rq.tb, pl.err, pl.kind, pl.T);
+                    }
+        }
+    }
     // the recompute fill's width rules at tests/test_gpu_rc_default_width.py's shapes
     expect_plan("DNA default", plan_fill(shape(2500, 2600), rc, unset, kLds), kLane, 2);
     expect_plan("DNA, GA_RC_NARROW=0", plan_fill(shape(2500, 2600), rc, wide, kLds), kLane, 4);
@@ -344,6 +374,120 @@ void test_plan() {
     }
 }
 
+// The guard bands' layout arithmetic (ga_guard.h), on a host model of one guarded buffer that follows DevBuf::ensure
+// step by step: allocate G + cap + G, lay the pattern, re-lay the rear guard when the request changes.
+struct GuardModel {
+    size_t G;
+    uint8_t fill;
+    std::vector<uint8_t> raw;
+    size_t cap = 0, size = 0;
+    GuardModel(size_t G_, uint8_t fill_) : G(G_), fill(fill_) {}
+    uint8_t* payload() { return raw.data() + gaguard::payload_off(G); }
+    void ensure(size_t bytes) {
+        if (bytes <= cap && !raw.empty()) {
+            if (bytes == size) return;
+            const gaguard::Range r = gaguard::relay_range(size, bytes, G);
+            CHECK(r.hi <= cap + G, "re-lay %zu -> %zu leaves the allocation", size, bytes);
+            std::memset(payload() + r.lo, fill, r.hi - r.lo);
+            size = bytes;
+            return;
+        }
+        cap = std::max<size_t>(bytes, 256);
+        raw.assign(gaguard::alloc_bytes(cap, G), 0);  // (a vector of exactly the allocation: ASan sees an overrun)
+        std::memset(raw.data(), fill, G);
+        std::memset(raw.data() + gaguard::rear_off(bytes, G), fill, cap + G - bytes);
+        size = bytes;
+    }
+    std::vector<gaguard::Violation> check() {
+        std::vector<gaguard::Violation> out;
+        gaguard::Violation v;
+        if (gaguard::make_violation("buf", gaguard::kFront, gaguard::scan(raw.data(), G, fill), size, G, v)) out.push_back(v);
+        if (gaguard::make_violation("buf", gaguard::kRear, gaguard::scan(raw.data() + gaguard::rear_off(size, G), G, fill), size, G, v))
+            out.push_back(v);
+        return out;
+    }
+};
+
+void test_guard() {
+    using namespace gaguard;
+    for (long long g : {0LL, 256LL, 4096LL, 1LL << 20}) CHECK(valid_guard_bytes(g), "GA_GUARD_BYTES=%lld refused", g);
+    for (long long g : {-256LL, 1LL, 255LL, 257LL, 4097LL, (1LL << 20) + 256}) CHECK(!valid_guard_bytes(g), "GA_GUARD_BYTES=%lld accepted", g);
+    CHECK(valid_fill(0) && valid_fill(255) && !valid_fill(256) && !valid_fill(-1), "GA_GUARD_FILL range");
+    for (size_t G : {(size_t)256, (size_t)4096})
+        for (size_t bytes : {(size_t)0, (size_t)1, (size_t)255, (size_t)256, (size_t)257, (size_t)33333}) {
+            GuardModel b(G, 0xA5);
+            b.ensure(bytes);
+            CHECK(payload_off(G) % kAlign == 0, "payload alignment at G=%zu", G);
+            CHECK(b.cap == std::max<size_t>(bytes, 256), "cap %zu for %zu bytes", b.cap, bytes);
+            CHECK(b.raw.size() == G + b.cap + G, "allocation of %zu bytes", bytes);
+            CHECK(rear_off(bytes, G) + G <= b.raw.size(), "rear guard of %zu bytes inside the allocation", bytes);
+            CHECK(b.check().empty(), "fresh buffer of %zu bytes not clean", bytes);
+            // the whole payload may be written: nothing is reported
+            std::memset(b.payload(), 0x11, bytes);
+            CHECK(b.check().empty(), "payload writes of %zu bytes reported", bytes);
+            // the first and the last byte of each guard, alone and together
+            struct Poke { int side; size_t idx, n; };
+            for (const Poke& pk : {Poke{kFront, 0, 1}, Poke{kFront, G - 1, 1}, Poke{kRear, 0, 1}, Poke{kRear, G - 1, 1},
+                                   Poke{kFront, 0, G}, Poke{kRear, 0, G}, Poke{kRear, 3, 5}}) {
+                uint8_t* at = (pk.side == kFront ? b.raw.data() : b.raw.data() + rear_off(bytes, G)) + pk.idx;
+                std::memset(at, 0x5A, pk.n);
+                const auto vs = b.check();
+                CHECK(vs.size() == 1, "%zu violations, expected one", vs.size());
+                if (vs.size() == 1) {
+                    const long long want = pk.side == kFront ? (long long)pk.idx - (long long)G : (long long)(bytes + pk.idx);
+                    CHECK(vs[0].side == pk.side && vs[0].offset == want && vs[0].changed == pk.n &&
+                              vs[0].last == want + (long long)pk.n - 1 && vs[0].payload == bytes && vs[0].name == "buf",
+                          "report '%s' for side %d idx %zu n %zu of %zu bytes", describe(vs[0]).c_str(), pk.side, pk.idx, pk.n, bytes);
+                }
+                std::memset(at, 0xA5, pk.n);
+                CHECK(b.check().empty(), "guard not clean after the pattern was restored");
+            }
+        }
+    // two guards at once, and the text of a report
+    {
+        GuardModel b(256, 0xFF);
+        b.ensure(1001);  // an unaligned end: the rear guard starts at payload byte 1001
+        b.raw[256 - 8] = 0;
+        b.payload()[1001 + 7] = 0;
+        b.payload()[1001 + 9] = 0;
+        const auto vs = b.check();
+        CHECK(vs.size() == 2 && describe(vs) == "buf front -8 n=1 last=-8 payload=1001; buf rear +1008 n=2 last=+1010 payload=1001",
+              "report '%s'", describe(vs).c_str());
+    }
+    // shrink, then grow, inside one allocation: the bytes both requests cover keep their contents, the rear guard
+    // follows the request, and what the old guard covered is pattern again (no stale guard inside the payload is
+    // mistaken for data, no stale payload inside the guard for a stray store)
+    {
+        const size_t G = 256;
+        GuardModel b(G, 0xA5);
+        b.ensure(5000);
+        for (size_t k = 0; k < 5000; k++) b.payload()[k] = (uint8_t)(k * 7 + 1) | 1;
+        const uint8_t* before = b.raw.data();
+        b.ensure(129);
+        CHECK(b.raw.data() == before && b.cap == 5000 && b.size == 129, "a smaller request reallocated");
+        CHECK(b.check().empty(), "after the shrink: %s", describe(b.check()).c_str());
+        bool kept = true;
+        for (size_t k = 0; k < 129; k++) kept = kept && b.payload()[k] == ((uint8_t)(k * 7 + 1) | 1);
+        CHECK(kept, "the shrink lost payload below the new end");
+        b.payload()[129] = 0;  // one past the smaller request: the moved guard sees it
+        auto vs = b.check();
+        CHECK(vs.size() == 1 && vs[0].side == kRear && vs[0].offset == 129 && vs[0].payload == 129, "store past a shrunk request: %s",
+              describe(vs).c_str());
+        b.ensure(4097);
+        CHECK(b.raw.data() == before && b.size == 4097, "growing inside cap reallocated");
+        CHECK(b.check().empty(), "after the growth: %s", describe(b.check()).c_str());
+        kept = true;
+        for (size_t k = 0; k < 129; k++) kept = kept && b.payload()[k] == ((uint8_t)(k * 7 + 1) | 1);
+        CHECK(kept, "the growth lost payload below the old end");
+        b.ensure(5000);
+        CHECK(b.check().empty() && rear_off(5000, G) + G == b.raw.size(), "back at the full size");
+        b.ensure(5001);  // past cap: a new allocation
+        CHECK(b.cap == 5001 && b.check().empty(), "growth past cap");
+        const Range r = relay_range(700, 300, G);
+        CHECK(r.lo == 300 && r.hi == 700 + G, "relay_range(700, 300) = [%zu, %zu)", r.lo, r.hi);
+    }
+}
+
 double ms_since(std::chrono::steady_clock::time_point t) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
 }
@@ -377,6 +521,7 @@ int main(int argc, char** argv) {
     test_table(79, 50000);
     test_checks();
     test_plan();
+    test_guard();
     if (failures) {
         std::fprintf(stderr, "%d check(s) failed\n", failures);
         return 1;

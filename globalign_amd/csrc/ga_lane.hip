@@ -456,7 +456,13 @@ __global__ void __launch_bounds__(lane_block_threads(NWC)) fill_lane_kernel(Fill
     // buffer's end for the others, whose stores the buffer's range check then drops: no exec change, and no scratch
     // writes (they were three quarters of the store's bytes); off = cb + 8 rlo for every lane, one v_add with an
     // SGPR (a per-lane multiplier took a 64-bit v_mad_u64_u32): the other lanes' 0x7ffffff0 + 8 rlo stays past
-    // the buffer's (m + 1) * 8 bytes and below 2^32 while rc_rows_fit(m) (ga_check.h), which the host requires
+    // the buffer's (m + 1) * 8 bytes and below 2^32 while rc_rows_fit(m) (ga_check.h), which the host requires.
+    // With the lean ramp (it_lo = 0) the store also runs for r0 < 64, where rlo + lane - 48 is negative for the low
+    // lanes of 48..63: their 8 rlo wraps to just under 2^32, far past num_records = (m + 1) * 8, and the range check
+    // drops them like the others -- which is why num_records must stay exactly the stripe's rows (guard mode,
+    // DESIGN.md 8, changes neither it nor the base).  Row 0 itself is written once, at r0 = 48 by lane 62, with a
+    // ramp value (h1' in [o, 2o]) and not the boundary's: colck row 0 is never read, the recompute blocks' edge
+    // window begins at row t0 + RC_EDGE_FIRST >= 1 (rc_windows, ga_rcwalk.hip; asserted in rc_walk_launch).
     const unsigned ck_cb = lane >= 48 ? (unsigned)(lane - 48) * 8u : 0x7ffffff0u;
     lk_v4i ck_rsrc = {0, 0, 0, 0};
     if (RC && p.colck != nullptr) {

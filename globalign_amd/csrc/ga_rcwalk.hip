@@ -44,7 +44,9 @@ __device__ __forceinline__ void st16_sc1(uint4* p, uint4 v) {
 }
 
 // A block's code window (dword i: a[base+i .. base+i+3]) and left-edge window (rows t0+1 ..) into LDS: four rounds of
-// loads issued before any store, so the block waits for one memory latency, not one per 64 entries.
+// loads issued before any store, so the block waits for one memory latency, not one per 64 entries.  The edge rows
+// begin at t0 + RC_EDGE_FIRST >= 1: row 0 of a colck stripe is never read (the lean ramp of the fill leaves a ramp
+// value there, ga_lane.hip), and a change that reads it must first make the fill write the boundary's value.
 __device__ __forceinline__ void rc_windows(const RcArgs& r, uint32_t* awin, int2* ewin, int nst, int base, int t0, int s,
                                            int lane) {
     const int m = r.m;
@@ -67,7 +69,7 @@ __device__ __forceinline__ void rc_windows(const RcArgs& r, uint32_t* awin, int2
     for (int i0 = lane; i0 < nst + 8; i0 += 256) {
         int2 v[4];
 #pragma unroll
-        for (int q = 0; q < 4; q++) v[q] = E[min(t0 + 1 + i0 + 64 * q, m)];
+        for (int q = 0; q < 4; q++) v[q] = E[min(t0 + RC_EDGE_FIRST + i0 + 64 * q, m)];
 #pragma unroll
         for (int q = 0; q < 4; q++)
             if (i0 + 64 * q < nst + 8) ewin[i0 + 64 * q] = v[q];

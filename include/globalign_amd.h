@@ -28,6 +28,7 @@ extern "C" {
 #define GA_E_STATE -4    /* call order violated (e.g. traceback before fill) */
 #define GA_E_TIMEOUT -5  /* a device-side wait exceeded its spin bound      */
 #define GA_E_NOMEM -6    /* device memory too small for the chosen path      */
+#define GA_E_GUARD -7    /* guard mode: bytes outside a buffer were changed   */
 
 /* Python-visible outcome of a traceback (dp_array_backward semantics). */
 #define GA_TB_OK 0
@@ -299,6 +300,25 @@ void* ga_ctx_stream(ga_ctx* ctx);
 int ga_ctx_wait_stream(ga_ctx* ctx, void* stream);
 /* The priority the context's stream was created with (hipDeviceGetStreamPriorityRange units). */
 int ga_ctx_stream_priority(ga_ctx* ctx, int* priority);
+
+/* ---- guard mode (tests) ------------------------
+ * Under the context option GA_GUARD_BYTES=G every device and pinned buffer of
+ * the context has G pattern bytes in front of and behind its payload, and every
+ * entry that runs kernels and waits for them checks them before it returns:
+ * GA_E_GUARD, with ga_last_error naming buffer, side, offset of the first
+ * changed byte relative to the payload, count and payload size.  No reference
+ * counterpart.
+ * ga_debug_guard_report: the same check without an error, as JSON text
+ * {"guard_bytes", "fill", "poison", "violations": [{"name", "side", "offset",
+ * "last", "changed", "payload"}], "buffers": [{"name", "payload", "guarded"}]}
+ * (buffers: the allocated ones).  *needed receives the text's size with its
+ * terminator; it is written when cap suffices.  It repairs nothing.
+ * ga_debug_guard_poke: a host-side copy of nbytes bytes that differ from the
+ * pattern into a guard of buffer `name` (side 0 front, 1 rear; offset counts
+ * from that guard's first byte), so that a test can see the check report it;
+ * it cannot leave the guard.  Both need guard mode (GA_E_STATE without). */
+int ga_debug_guard_report(ga_ctx* ctx, char* out, int64_t cap, int64_t* needed);
+int ga_debug_guard_poke(ga_ctx* ctx, const char* name, int32_t side, int64_t offset, int64_t nbytes);
 
 /* ---- measurement --------------------------------------------------------- */
 /* Device time (ms, HIP events on the launch stream) of the last fill kernel
