@@ -44,6 +44,7 @@ class EngineError(RuntimeError):
 EXPORTS = [
     "ga_last_error", "ga_device_count", "ga_ctx_create", "ga_ctx_create_opts", "ga_ctx_destroy", "ga_build_flags", "ga_problem_set", "ga_problem_fill", "ga_batch_costs", "ga_batch_costs_ex", "ga_batch_align", "ga_batch_align_timings", "ga_debug_seed_state",
     "ga_batch_align_ex", "ga_batch_align_info", "ga_debug_pair_tables",
+    "ga_batch_sample", "ga_batch_sample_info", "ga_batch_sample_timings",
     "ga_problem_set_cells",
     "ga_problem_traceback", "ga_problem_align", "ga_problem_align_many", "ga_problem_set_slab", "ga_slab_buffers", "ga_slab_bind_halos",
     "ga_slab_link", "ga_slab_link_export", "ga_slab_link_import", "ga_enable_peer_access",
@@ -114,6 +115,10 @@ def load_library():
                                      pi64, p32, pi64]
         L.ga_batch_align_ex.argtypes = L.ga_batch_align.argtypes + [C.c_uint32]
         L.ga_batch_align_info.argtypes = [vp, p32]
+        L.ga_batch_sample.argtypes = [vp, vp, pi64, i64, p32, p32, p32, i64, C.POINTER(GaCosts), pi64, vp, vp, vp, vp, vp,
+                                      pi64, pi64, p32, pi64, C.c_uint32]
+        L.ga_batch_sample_info.argtypes = [vp, pi64]
+        L.ga_batch_sample_timings.argtypes = [vp, C.POINTER(C.c_float)]
         L.ga_debug_pair_tables.argtypes = [vp, vp, p32, i64, i32, pu32, p32]
         L.ga_batch_align_timings.argtypes = [vp, C.POINTER(C.c_float)]
         L.ga_debug_seed_state.argtypes = [C.c_uint64, pu32]
@@ -342,6 +347,77 @@ class Engine:
                                          status.ctypes.data_as(p32), costs.ctypes.data_as(p64), RNG_TABLES[rng_tables]))
         self.m = self.n = 0
         return costs, status, lengths, offsets, bufs
+
+    def batch_sample(self, codes, seq_off, pair_a, pair_b, tables, sample_off, seeds, chars, pair_max_cost=None,
+                     rng_tables=None):
+        """Many seeded alignments of every pair from one fill of the pair (ga_batch_sample): batch_align's arguments,
+        sample_off (int64, P + 1 entries from 0: pair k has the samples sample_off[k] .. sample_off[k + 1]) and seeds
+        (uint64, one per sample).
+        -> (costs int64 per pair, status int32 per sample, lengths int64 per sample, offsets int64 (samples + 1),
+        (seq_1_aligned, middle, seq_2_aligned) uint8 buffers): sample f's strings are the lengths[f] bytes at
+        offsets[f] of each buffer.  Afterwards no problem counts as loaded."""
+        if rng_tables not in RNG_TABLES:
+            raise ValueError(f"rng_tables must be None, 'host' or 'device', not {rng_tables!r}")
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        chars = np.ascontiguousarray(chars, dtype=np.uint8)
+        seq_off = np.ascontiguousarray(seq_off, dtype=np.int64)
+        pair_a = np.ascontiguousarray(pair_a, dtype=np.int32)
+        pair_b = np.ascontiguousarray(pair_b, dtype=np.int32)
+        sample_off = np.ascontiguousarray(sample_off, dtype=np.int64)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        if pair_a.shape != pair_b.shape or pair_a.ndim != 1 or seq_off.ndim != 1 or len(seq_off) < 1:
+            raise ValueError("pair_a and pair_b must be 1-d and of equal length, seq_off 1-d and non-empty")
+        if int(seq_off[-1]) != codes.size or chars.size != codes.size:
+            raise ValueError("seq_off must end at len(codes), and chars must hold one byte per code")
+        P = len(pair_a)
+        if sample_off.shape != (P + 1,) or int(sample_off[0]) != 0 or (np.diff(sample_off) < 0).any():
+            raise ValueError("sample_off must have one entry per pair and one more, start at 0 and not decrease")
+        S = int(sample_off[-1])
+        if seeds.shape != (S,):
+            raise ValueError("seeds must have one entry per sample")
+        if P and (min(pair_a.min(), pair_b.min()) < 0 or max(pair_a.max(), pair_b.max()) >= len(seq_off) - 1):
+            raise ValueError("sequence index out of range")
+        p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        pmc = None
+        if pair_max_cost is not None:
+            pair_max_cost = np.ascontiguousarray(pair_max_cost, dtype=np.int32)
+            if pair_max_cost.shape != pair_a.shape:
+                raise ValueError("pair_max_cost must have one entry per pair")
+            pmc = pair_max_cost.ctypes.data_as(p32)
+        lens = np.diff(seq_off)
+        per_pair = lens[pair_a] + lens[pair_b] + 1
+        offsets = np.concatenate([[0], np.cumsum(np.repeat(per_pair, np.diff(sample_off)))]).astype(np.int64)
+        bufs = tuple(np.empty(max(int(offsets[-1]), 1), dtype=np.uint8) for _ in range(3))
+        costs = np.zeros(P, dtype=np.int64)
+        lengths = np.zeros(max(S, 1), dtype=np.int64)
+        status = np.zeros(max(S, 1), dtype=np.int32)
+        _check(self._L.ga_batch_sample(self._h, codes.ctypes.data, seq_off.ctypes.data_as(p64), len(seq_off) - 1,
+                                       pair_a.ctypes.data_as(p32), pair_b.ctypes.data_as(p32), pmc, P,
+                                       C.byref(tables.struct), sample_off.ctypes.data_as(p64), seeds.ctypes.data,
+                                       chars.ctypes.data, bufs[0].ctypes.data, bufs[1].ctypes.data, bufs[2].ctypes.data,
+                                       offsets.ctypes.data_as(p64), lengths.ctypes.data_as(p64),
+                                       status.ctypes.data_as(p32), costs.ctypes.data_as(p64), RNG_TABLES[rng_tables]))
+        self.m = self.n = 0
+        return costs, status[:S], lengths[:S], offsets, bufs
+
+    def batch_sample_info(self):
+        """{filled_pairs, single_fill_pairs, looped_pairs, walk_items, fill_launches, walk_launches, device_items,
+        host_items} of the last batch_sample (ga_batch_sample_info): the pairs batch_words_kernel filled, those the
+        single-pair fill filled once for all their samples, those looped sample by sample through the single-pair
+        path; the walks batch_walks_kernel made, the fill and walk launches, and the walks whose tie-break table the
+        device / the host made."""
+        out = (C.c_int64 * 8)()
+        _check(self._L.ga_batch_sample_info(self._h, out))
+        return dict(zip(("filled_pairs", "single_fill_pairs", "looped_pairs", "walk_items", "fill_launches",
+                         "walk_launches", "device_items", "host_items"), (int(x) for x in out)))
+
+    def batch_sample_timings(self):
+        """{words_ms, walks_ms, table_ms, decode_ms, call_ms, walk_ns_per_step, single_fill_ms} of the last
+        batch_sample, summed over its launches."""
+        out = (C.c_float * 8)()
+        _check(self._L.ga_batch_sample_timings(self._h, out))
+        return dict(words_ms=out[0], walks_ms=out[1], table_ms=out[2], decode_ms=out[3], call_ms=out[4],
+                    walk_ns_per_step=out[5], single_fill_ms=out[6])
 
     def batch_align_info(self):
         """{device_items, host_items, fell_back, generator_blocks} of the last batch_align or debug_pair_tables

@@ -1,7 +1,7 @@
 // ga_batch.h -- host-side planning of a batch of score-only alignments (ga_batch_costs) and of a batch of alignments
 // with strings (ga_batch_align, at the end); no HIP: built into the engine, into the kernels' translation unit for the
-// work-item layout, and into the planner self-tests, ga_batch_selftest.cpp and ga_batch_align_selftest.cpp, under
-// AddressSanitizer / UBSan.
+// work-item layout, and into the planner self-tests, ga_batch_selftest.cpp, ga_batch_align_selftest.cpp and
+// ga_batch_sample_selftest.cpp (ga_batch_sample's planner, after ga_batch_align's), under AddressSanitizer / UBSan.
 //
 // A batch is a list of sequences (codes concatenated, seq_off[s] .. seq_off[s + 1]) and a list of pairs of sequence
 // indices.  The planner checks every pair as check_problem (ga_check.h) checks a single problem -- with that pair's
@@ -231,6 +231,134 @@ inline int plan_batch_align(const uint8_t* codes, const int64_t* seq_off, int64_
         out.ops_words += (steps + 15) / 16;
         out.tb_words = std::max(out.tb_words, tb_slice_words(it.m, it.T, it.nstripes, out.CB));
     }
+    return GA_OK;
+}
+
+}  // namespace gabatch
+
+// ------------------------------------------------------------------ many seeded walks of a pair (ga_batch_sample)
+// The fill of a pair does not depend on the seed, its walk does: batch_words_kernel fills every kernel pair once and
+// keeps its traceback words in a slice of the pair's own, batch_walks_kernel then walks it once per sample, one wave
+// per walk (ga_batch.hip).
+
+// What batch_words_kernel needs per pair beyond its ga_batch_item (same index in the chunk's work list).
+struct ga_batch_words_item {
+    int64_t tb_off;    // the pair's slice of the chunk's traceback words (u32 words)
+    int64_t tb_words;  // its length: tb_slice_words of the pair
+};
+
+// One walk: a sample of a pair.
+struct ga_batch_sample_item {
+    int64_t tab_off;  // the sample's m + n tie-break entries in the walk launch's table
+    int64_t ops_off;  // its ceil((m + n) / 16) u32 words of packed levels
+    int32_t fill;     // the pair's index in its chunk's work list
+    int32_t out;      // the sample's flat index (pair order, then sample order): walk results and strings go there
+};
+
+namespace gabatch {
+
+constexpr int64_t kWalkTableEntriesCap = 1ll << 28;  // tie-break entries of one walk launch (1 GiB of u32)
+
+struct SampleLimits : AlignLimits {
+    // u32 words of traceback scratch of one fill chunk, all its pairs (GA_BATCH_SAMPLE_CHUNK_WORDS overrides)
+    int64_t chunk_tb_words = kTbScratchBytesCap / 4;
+    // tie-break entries of one walk launch (GA_BATCH_SAMPLE_WALK_ENTRIES overrides)
+    int64_t walk_entries = kWalkTableEntriesCap;
+};
+
+// Walk items [first, first + count) of SamplePlan::walk share one launch; tab_off / ops_off count from its start.
+struct WalkLaunch {
+    int64_t first = 0, count = 0;
+    int64_t tab_entries = 0, ops_words = 0;
+};
+
+// Kernel pairs [first, first + count) of SamplePlan::kernel are filled by one launch, their slices side by side in
+// tb_words u32 words; walk launches [launch_first, launch_first + launch_count) walk them.
+struct FillChunk {
+    int64_t first = 0, count = 0;
+    int64_t tb_words = 0;
+    int64_t launch_first = 0, launch_count = 0;
+};
+
+struct SamplePlan : Plan {
+    int CB = 1;
+    std::vector<ga_batch_words_item> words;   // parallel to `kernel`; tb_off counts from the chunk's start
+    std::vector<ga_batch_sample_item> walk;   // chunk by chunk, pair by pair in work-list order, sample by sample
+    std::vector<FillChunk> chunks;
+    std::vector<WalkLaunch> launches;
+};
+
+// The walk items of one fill's pairs items[0 .. count) -- pair items[t] has the samples sample_off[items[t].out] ..
+// sample_off[items[t].out + 1] and is walk item field `fill` = t -- appended to `walk`, cut into launches of at most
+// walk_entries table entries (a single item above that gets a launch of its own), appended to `launches`.
+inline void plan_walk_launches(const ga_batch_item* items, int64_t count, const int64_t* sample_off, int64_t walk_entries,
+                               std::vector<ga_batch_sample_item>& walk, std::vector<WalkLaunch>& launches) {
+    const int64_t walk_cap = std::max<int64_t>(walk_entries, 1);
+    WalkLaunch wl;
+    wl.first = (int64_t)walk.size();
+    for (int64_t t = 0; t < count; t++) {
+        const int64_t steps = (int64_t)items[t].m + items[t].n;
+        for (int64_t f = sample_off[items[t].out]; f < sample_off[items[t].out + 1]; f++) {
+            if (wl.count > 0 && wl.tab_entries + steps > walk_cap) {
+                launches.push_back(wl);
+                wl = WalkLaunch();
+                wl.first = (int64_t)walk.size();
+            }
+            walk.push_back(ga_batch_sample_item{wl.tab_entries, wl.ops_words, (int32_t)t, (int32_t)f});
+            wl.count++;
+            wl.tab_entries += steps;
+            wl.ops_words += (steps + 15) / 16;
+        }
+    }
+    if (wl.count > 0) launches.push_back(wl);
+}
+
+// plan_batch_align's checks, error order, stripe geometry and routing, a pair's traceback words measured against a
+// fill chunk's cap instead of a wave's share (lim.tb_words_cap is set from lim.chunk_tb_words here).  Pair k has the
+// samples sample_off[k] .. sample_off[k + 1].  A walk launch takes items while their table entries stay within
+// lim.walk_entries (a single item above it gets a launch of its own); a pair's samples may span several walk
+// launches of its chunk, a pair never appears in two chunks.
+inline int plan_batch_sample(const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                             const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                             const int64_t* sample_off, const SampleLimits& lim, SamplePlan& out, std::string& err) {
+    out = SamplePlan();
+    auto fail = [&](int code, const std::string& msg) {
+        err = msg;
+        return code;
+    };
+    AlignLimits al = lim;
+    al.tb_words_cap = std::max<int64_t>(lim.chunk_tb_words, 0);
+    AlignPlan base;
+    if (int r = plan_batch_align(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, al, base, err)) return r;
+    if (npairs == 0) return GA_OK;
+    if (!sample_off) return fail(GA_E_ARG, "null argument");
+    if (sample_off[0] != 0) return fail(GA_E_ARG, "sample_off must start at 0");
+    for (int64_t k = 0; k < npairs; k++)
+        if (sample_off[k + 1] < sample_off[k]) return fail(GA_E_ARG, "sample_off must not decrease");
+    if (sample_off[npairs] > (int64_t)INT32_MAX) return fail(GA_E_RANGE, "a batch holds at most 2^31 - 1 samples");
+    static_cast<Plan&>(out) = std::move(static_cast<Plan&>(base));
+    out.CB = base.CB;
+    out.words.reserve(out.kernel.size());
+    auto close_chunk = [&](FillChunk& ch) {
+        ch.launch_first = (int64_t)out.launches.size();
+        plan_walk_launches(out.kernel.data() + ch.first, ch.count, sample_off, lim.walk_entries, out.walk, out.launches);
+        ch.launch_count = (int64_t)out.launches.size() - ch.launch_first;
+        out.chunks.push_back(ch);
+    };
+    FillChunk ch;
+    for (int64_t t = 0; t < (int64_t)out.kernel.size(); t++) {
+        const ga_batch_item& it = out.kernel[(size_t)t];
+        const int64_t w = tb_slice_words(it.m, it.T, it.nstripes, out.CB);  // <= al.tb_words_cap: the routing's rule
+        if (ch.count > 0 && ch.tb_words + w > al.tb_words_cap) {
+            close_chunk(ch);
+            ch = FillChunk();
+            ch.first = t;
+        }
+        out.words.push_back(ga_batch_words_item{ch.tb_words, w});
+        ch.tb_words += w;
+        ch.count++;
+    }
+    if (ch.count > 0) close_chunk(ch);
     return GA_OK;
 }
 

@@ -1,5 +1,6 @@
 // ga_batch.hip -- batch_fill_kernel: many score-only alignments in one launch, one wave per pair (gfx950), and
-// batch_align_kernel (further down): the same with traceback words and the traceback walk, for alignment strings.
+// batch_align_kernel (further down): the same with traceback words and the traceback walk, for alignment strings;
+// batch_words_kernel and batch_walks_kernel (after it): that fill and that walk as two launches, many walks per fill.
 //
 // For each pair this replaces make_dp_array (globaligner.py:756-821), dp_array_forward (:366-392) and the min of
 // the last cell (:425) -- what the single-pair path spreads over the boundary launches and a fill -- in the shifted
@@ -17,6 +18,7 @@
 #include <stdint.h>
 
 #include "ga_batch.h"
+#include "ga_batch_layout.h"
 #include "ga_device.h"
 #include "ga_row.h"
 #include "ga_walk.h"
@@ -322,13 +324,15 @@ __global__ void __launch_bounds__(64 * gabatch::kWavesPerGroup) batch_fill_kerne
 // v_readlane.  Every step lowers i + j and the walk ends at i == 0 or j == 0, so it makes at most m + n - 1 steps
 // whatever the words and the table hold.  The words are read with vector loads only (the scalar cache could hold a
 // previous pair's lines of this slice), after the fence that follows the fill's stores.
-template <int CB>
+// LAYOUT (ga_batch_layout.h): where a cell's word lies in tbw -- LAYOUT_BATCH, batch_pair's words, or LAYOUT_STRIPE,
+// a single-pair fill's at `tc` 16-byte words per lane (batch_walks_kernel's large route).
+template <int CB, int LAYOUT = gabatch::LAYOUT_BATCH>
 __device__ int4 batch_walk(const AlignArgs& q, const ga_batch_item& it, const ga_batch_walk_item& wi,
-                           const uint32_t* tbw, int lane) {
-    constexpr int RPW = 4 / CB;
+                           const uint32_t* tbw, int lane, int tc = 0) {
+    using Addr = gabatch::TbAddr<CB, LAYOUT>;
     constexpr unsigned MASK = CB == 4 ? 0xffffffffu : (1u << (8 * CB)) - 1u;
     const int m = it.m, n = it.n, o = q.b.o;
-    const int npitch = 64 * it.T * it.nstripes, total = m + n;
+    const int geom = LAYOUT == gabatch::LAYOUT_BATCH ? 64 * it.T * it.nstripes : tc, total = m + n;
     const uint8_t* a = q.b.codes + it.a_off;
     const uint8_t* b = q.b.codes + it.b_off;
     const uint32_t* tab = q.rng + wi.tab_off;
@@ -338,8 +342,8 @@ __device__ int4 batch_walk(const AlignArgs& q, const ga_batch_item& it, const ga
     unsigned L5 = 0, opsw = 0;  // 5 * the level the walk entered the cell with; the level word being packed
     while (i > 0 && j > 0 && D < total) {
         const int ci = max(i - lr, 1), cj = max(j - lc, 1);
-        const uint32_t wd = tbw[(unsigned)((ci - 1) / RPW) * (unsigned)npitch + (unsigned)(cj - 1)];
-        const unsigned code = (wd >> (((ci - 1) & (RPW - 1)) * 8 * CB)) & MASK;
+        const uint32_t wd = tbw[Addr::word(ci, cj, geom)];
+        const unsigned code = (wd >> Addr::shift(ci)) & MASK;
         const int shf = (int)cell_shifts(sets_from_code(code, CB, o), a[ci - 1] == b[cj - 1]);
         const int tv = (int)tab[min(D + (lane & 7), total - 1)];  // lane s: the entry of the group's step s
         int di = 0, dj = 0;
@@ -432,6 +436,138 @@ __global__ void __launch_bounds__(64 * gabatch::kWavesPerGroup) batch_align_kern
             q.walk_out[2 * (long long)it.out + 1] = make_int4((int)(t1 - t0), (int)(t2 - t1), 0, 0);
         }
     }
+}
+
+// ------------------------------------------------------------------ batch_words_kernel, batch_walks_kernel
+// Many seeded walks of a pair from one fill (ga_batch_sample).  batch_words_kernel is
+// batch_align_kernel's ticket loop with the fill only: every pair's words go to the pair's own slice of the chunk's
+// scratch and stay there.  batch_walks_kernel, a later launch on the same stream, has one work item per sample: a wave
+// takes an item, finds its pair and walks the pair's words under the sample's table.  The order between the two is
+// stream order and nothing else: no wave waits for another, the words are read-only in the walks kernel.
+
+template <typename QT, int CB>
+__global__ void __launch_bounds__(64 * gabatch::kWavesPerGroup) batch_words_kernel(WordsArgs q) {
+    __shared__ QT tab[gabatch::kLdsTableBytes / sizeof(QT)];
+    __shared__ int gh_s[256], gv_s[256];
+    __shared__ int2 edge_s[gabatch::kWavesPerGroup][gabatch::kLdsEdgeRows];
+    const BatchArgs& p = q.b;
+    const int K = p.K;
+    for (int x = threadIdx.x; x < K * K; x += blockDim.x) tab[x] = (QT)p.subp[x];
+    for (int x = threadIdx.x; x < K; x += blockDim.x) {
+        gh_s[x] = p.gh[x];
+        gv_s[x] = p.gv[x];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long gw = (long long)blockIdx.x * gabatch::kWavesPerGroup + w;
+    int2* edge_g = p.scratch ? p.scratch + gw * 2 * p.scratch_rows : nullptr;
+    for (;;) {
+        unsigned t = 0;
+        if (lane == 0) t = __hip_atomic_fetch_add(p.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        t = (unsigned)__builtin_amdgcn_readfirstlane((int)t);
+        if (t >= (unsigned)p.nitems) break;
+        const ga_batch_item it = p.items[t];
+        const ga_batch_words_item ws = q.words[t];
+        const bool hbm = it.nstripes > 1 && it.m > gabatch::kLdsEdgeRows;
+        // the edge column must fit this wave's slices and the traceback words the pair's own slice, which must lie
+        // inside the chunk's words; the walks need two letters a side (ga_batch.h plans it so)
+        const bool fits = !(hbm && (edge_g == nullptr || it.m > p.scratch_rows)) && it.m >= 2 && it.n >= 2 &&
+                          it.T >= 1 && it.T <= gabatch::kMaxT && it.nstripes >= 1 &&
+                          (long long)((it.m + 4 / CB - 1) / (4 / CB)) * 64 * it.T * it.nstripes <= ws.tb_words &&
+                          (long long)64 * it.T * it.nstripes >= it.n && ws.tb_off >= 0 &&
+                          ws.tb_off <= q.tb_words && ws.tb_words <= q.tb_words - ws.tb_off;
+        uint32_t* tbw = q.tb + (fits ? ws.tb_off : 0);
+        switch (fits ? it.T : 0) {
+            case 1: align_pair_either<QT, 1, CB>(p, it, hbm, tab, gh_s, gv_s, edge_s[w], edge_g, lane, tbw); break;
+            case 2: align_pair_either<QT, 2, CB>(p, it, hbm, tab, gh_s, gv_s, edge_s[w], edge_g, lane, tbw); break;
+            case 3: align_pair_either<QT, 3, CB>(p, it, hbm, tab, gh_s, gv_s, edge_s[w], edge_g, lane, tbw); break;
+            case 4: align_pair_either<QT, 4, CB>(p, it, hbm, tab, gh_s, gv_s, edge_s[w], edge_g, lane, tbw); break;
+            case 5: align_pair_either<QT, 5, CB>(p, it, hbm, tab, gh_s, gv_s, edge_s[w], edge_g, lane, tbw); break;
+            case 6: align_pair_either<QT, 6, CB>(p, it, hbm, tab, gh_s, gv_s, edge_s[w], edge_g, lane, tbw); break;
+            case 7: align_pair_either<QT, 7, CB>(p, it, hbm, tab, gh_s, gv_s, edge_s[w], edge_g, lane, tbw); break;
+            case 8: align_pair_either<QT, 8, CB>(p, it, hbm, tab, gh_s, gv_s, edge_s[w], edge_g, lane, tbw); break;
+            default: p.cost_out[it.out] = BATCH_BAD_ITEM;  // (every lane, as batch_pair's cost)
+        }
+    }
+}
+
+template <int CB, int LAYOUT>
+__global__ void __launch_bounds__(64 * gabatch::kWavesPerGroup) batch_walks_kernel(WalksArgs q) {
+    const int lane = threadIdx.x & 63;
+    // batch_walk reads the codes, the gap-open cost, the tables and the level words out of an AlignArgs
+    AlignArgs aq{};
+    aq.b.codes = q.codes;
+    aq.b.o = q.o;
+    aq.rng = q.rng;
+    aq.ops = q.ops;
+    for (;;) {
+        // the only lane-divergent branch of the loop; the wave is whole again at the readfirstlane
+        unsigned t = 0;
+        if (lane == 0) t = __hip_atomic_fetch_add(q.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        t = (unsigned)__builtin_amdgcn_readfirstlane((int)t);
+        if (t >= (unsigned)q.nwalk) break;
+        const ga_batch_sample_item wi = q.witems[t];
+        const bool known = wi.fill >= 0 && wi.fill < q.nfill;
+        const ga_batch_item it = q.items[known ? wi.fill : 0];
+        const ga_batch_words_item ws = q.words[known ? wi.fill : 0];
+        const long long steps = (long long)it.m + it.n;
+        // the pair's codes, the walk's table entries and level words, and the pair's words must lie inside the
+        // launch's buffers (ga_batch.h plans it so); a walk needs two letters a side
+        bool fits = known && it.m >= 2 && it.n >= 2 && it.a_off >= 0 && it.b_off >= 0 &&
+                    (long long)it.a_off + it.m <= q.ncodes && (long long)it.b_off + it.n <= q.ncodes &&
+                    wi.tab_off >= 0 && wi.tab_off <= q.rng_entries && steps <= q.rng_entries - wi.tab_off &&
+                    wi.ops_off >= 0 && wi.ops_off <= q.ops_words && (steps + 15) / 16 <= q.ops_words - wi.ops_off &&
+                    ws.tb_off >= 0 && ws.tb_off <= q.tb_words;
+        if (LAYOUT == gabatch::LAYOUT_BATCH) {
+            fits = fits && it.T >= 1 && it.T <= gabatch::kMaxT && it.nstripes >= 1 &&
+                   (long long)64 * it.T * it.nstripes >= it.n &&
+                   (long long)((it.m + 4 / CB - 1) / (4 / CB)) * 64 * it.T * it.nstripes <= ws.tb_words &&
+                   ws.tb_words <= q.tb_words - ws.tb_off;
+        } else {
+            fits = fits && q.tc >= 1 && (long long)q.tc * (16 / CB) >= it.m &&
+                   (long long)((it.n + 63) / 64) * q.tc * 256 <= q.tb_words - ws.tb_off;
+        }
+        int4 end = make_int4(-1, 0, 0, 0);
+        int ticks = 0;
+        if (fits) {
+            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+            end = batch_walk<CB, LAYOUT>(aq, it, ga_batch_walk_item{wi.tab_off, wi.ops_off}, q.tb + ws.tb_off, lane, q.tc);
+            ticks = (int)(__builtin_amdgcn_s_memrealtime() - t0);
+        }
+        // every lane stores the same words (no lane-divergent branch at an item's end, see batch_pair)
+        q.walk_out[2 * (long long)t] = end;
+        q.walk_out[2 * (long long)t + 1] = make_int4(0, ticks, 0, 0);
+    }
+}
+
+template <typename QT>
+static void launch_batch_words_q(hipStream_t s, const WordsArgs& q, int CB, int groups) {
+    const int threads = 64 * gabatch::kWavesPerGroup;
+    if (CB == 1) batch_words_kernel<QT, 1><<<groups, threads, 0, s>>>(q);
+    else if (CB == 2) batch_words_kernel<QT, 2><<<groups, threads, 0, s>>>(q);
+    else batch_words_kernel<QT, 4><<<groups, threads, 0, s>>>(q);
+}
+
+void launch_batch_words(hipStream_t s, const WordsArgs& q, int qbytes, int CB, int waves) {
+    const int groups = waves / gabatch::kWavesPerGroup;
+    if (qbytes == 1) launch_batch_words_q<int8_t>(s, q, CB, groups);
+    else if (qbytes == 2) launch_batch_words_q<int16_t>(s, q, CB, groups);
+    else launch_batch_words_q<int32_t>(s, q, CB, groups);
+}
+
+template <int LAYOUT>
+static void launch_batch_walks_l(hipStream_t s, const WalksArgs& q, int CB, int groups) {
+    const int threads = 64 * gabatch::kWavesPerGroup;
+    if (CB == 1) batch_walks_kernel<1, LAYOUT><<<groups, threads, 0, s>>>(q);
+    else if (CB == 2) batch_walks_kernel<2, LAYOUT><<<groups, threads, 0, s>>>(q);
+    else batch_walks_kernel<4, LAYOUT><<<groups, threads, 0, s>>>(q);
+}
+
+void launch_batch_walks(hipStream_t s, const WalksArgs& q, int CB, int layout, int waves) {
+    const int groups = waves / gabatch::kWavesPerGroup;
+    if (layout == gabatch::LAYOUT_STRIPE) launch_batch_walks_l<gabatch::LAYOUT_STRIPE>(s, q, CB, groups);
+    else launch_batch_walks_l<gabatch::LAYOUT_BATCH>(s, q, CB, groups);
 }
 
 template <typename QT>

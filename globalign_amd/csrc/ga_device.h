@@ -6,6 +6,8 @@
 
 struct ga_batch_item;  // ga_batch.h
 struct ga_batch_walk_item;
+struct ga_batch_words_item;
+struct ga_batch_sample_item;
 namespace gabrng {
 struct Item;  // ga_batch_rng.h
 }
@@ -246,6 +248,38 @@ struct AlignArgs {
 // a multiple of gabatch::kWavesPerGroup; CB: bytes of a traceback word (1, 2 or 4)
 void launch_batch_fill(hipStream_t s, const BatchArgs& p, int qbytes, int waves);
 void launch_batch_align(hipStream_t s, const AlignArgs& q, int qbytes, int CB, int waves);
+// many seeded walks of a pair from one fill (ga_batch_sample): batch_words_kernel fills a chunk's
+// pairs and keeps every pair's traceback words in the pair's own slice; batch_walks_kernel, a later launch on the
+// same stream, walks a pair once per sample, one wave per walk
+struct WordsArgs {
+    BatchArgs b;
+    const ga_batch_words_item* words;  // parallel to b.items: each pair's slice of tb
+    uint32_t* tb;                      // the chunk's traceback words
+    long long tb_words;
+};
+struct WalksArgs {
+    const uint8_t* codes;                // every sequence's codes, concatenated
+    long long ncodes;
+    int o;
+    const ga_batch_item* items;          // the chunk's work list, as the fill had it
+    const ga_batch_words_item* words;    // parallel to items
+    int nfill;
+    const ga_batch_sample_item* witems;  // this launch's walks
+    int nwalk;
+    unsigned* ticket;                    // the walks' own ticket word
+    const uint32_t* rng;                 // the walks' tie-break entries, walk t at witems[t].tab_off
+    long long rng_entries;
+    uint32_t* ops;                       // the chosen levels, walk t at witems[t].ops_off
+    long long ops_words;
+    int4* walk_out;                      // [nwalk][2] {dispatches, i, j, reason} (dispatches -1: the item does not
+                                         // fit the launch), {0, walk ticks, 0, 0}, indexed by the walk's place in witems
+    const uint32_t* tb;                  // the words, written by an earlier launch and only read here
+    long long tb_words;
+    int tc;                              // LAYOUT_STRIPE: 16-byte words per lane of the fill that wrote tb
+};
+// layout: gabatch::LAYOUT_BATCH (batch_words_kernel's words) or LAYOUT_STRIPE (a single-pair fill's, ga_batch_layout.h)
+void launch_batch_words(hipStream_t s, const WordsArgs& q, int qbytes, int CB, int waves);
+void launch_batch_walks(hipStream_t s, const WalksArgs& q, int CB, int layout, int waves);
 // the device-routed items' tie-break tables, one wave per item (batch_rng_kernel, ga_batch_rng.hip)
 struct RngArgs {
     const gabrng::Item* items;   // seed, steps and tab_off of each item

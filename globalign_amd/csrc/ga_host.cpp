@@ -31,6 +31,7 @@
 #include "ga_check.h"
 #include "ga_batch.h"
 #include "ga_batch_align.h"
+#include "ga_batch_layout.h"
 #include "ga_batch_rng.h"
 #include "ga_guard.h"
 #include "ga_plan.h"
@@ -435,6 +436,11 @@ struct ga_ctx {
     bool rbase_ready = false;
     hipEvent_t rev[2] = {nullptr, nullptr};  // (created with the first generator launch)
     int32_t batch_rng_info[4] = {0, 0, 0, 0};  // device-routed items, host-routed items, fell back, generator blocks
+    // ga_batch_sample adds the pairs' slices (ga_batch_words_item), the chunk's traceback words, a
+    // walk launch's items and the walks' own ticket word; ga_batch_sample_info's and _timings's figures of its last call
+    DevBuf bs_words, bs_tb, bs_witems, bs_ticket;
+    int64_t batch_sample_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    float batch_sample_ms[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int walk_jump_diag[3] = {0, 0, 0};  // the tie-to-tie walk's trips, region re-checks, ties (result[12..14])
     DevBuf jlut;           // the jump workers' LUT for gap open jlut_o (ga::jump_lut_build)
     int jlut_o = -1;
@@ -486,7 +492,7 @@ void guard_each(ga_ctx* c, F&& dev, P&& pin) {
     GA_D(halo_in), GA_D(dbg), GA_D(wdbg), GA_D(colck), GA_D(stck), GA_D(rc_tb), GA_D(rc_flags), GA_D(rc_pos), GA_D(rc_own);
     GA_D(qprof), GA_D(bt_codes), GA_D(bt_items), GA_D(bt_sub), GA_D(bt_gh), GA_D(bt_gv), GA_D(bt_ticket), GA_D(bt_out);
     GA_D(bt_scratch), GA_D(bt_witems), GA_D(bt_rng), GA_D(bt_ops), GA_D(bt_walk), GA_D(bt_tb), GA_D(bt_ritems);
-    GA_D(bt_rstatus), GA_D(bt_rbase), GA_D(jlut);
+    GA_D(bt_rstatus), GA_D(bt_rbase), GA_D(jlut), GA_D(bs_words), GA_D(bs_tb), GA_D(bs_witems), GA_D(bs_ticket);
     GA_P(res_pin), GA_P(prog), GA_P(pipe_pin), GA_P(chain_tab), GA_P(chain_ctl), GA_P(chain_io), GA_P(rc_ops_pin);
     GA_P(rc_ops_prog), GA_P(up_pin);
 #undef GA_D
@@ -2755,6 +2761,294 @@ static int batch_align_ex_impl(ga_ctx* c, const uint8_t* codes, const int64_t* s
     return GA_OK;
 }
 
+// ga_batch_sample: every pair filled once, then walked once per sample.  Kernel pairs go chunk by
+// chunk through batch_words_kernel and, walk launch by walk launch, through batch_walks_kernel; a pair that left the
+// kernel route for its size is filled once by the single-pair engine with stored words and walked by the same kernel
+// in the fill's layout; what remains is looped sample by sample through ga_problem_align.
+static int batch_sample_impl(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                             const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                             const int64_t* sample_off, const uint64_t* seeds, const char* chars, char* out_a,
+                             char* out_mid, char* out_b, const int64_t* out_off, int64_t* out_len, int32_t* tb_status,
+                             int64_t* cost_out, uint32_t flags) {
+    if (int r = check_ctx(c)) return r;
+    if ((flags & ~GA_BATCH_TABLES_MASK) || (flags & GA_BATCH_TABLES_MASK) > GA_BATCH_TABLES_DEVICE)
+        return fail(GA_E_ARG, "bad flags: bits 0-1 choose the tables (0 default, 1 host, 2 device)");
+    for (int64_t& x : c->batch_sample_info) x = 0;
+    for (float& x : c->batch_sample_ms) x = 0.f;
+    if (npairs == 0) return GA_OK;  // an empty batch: no launch
+    if (!sample_off || !seeds || !chars || !out_a || !out_mid || !out_b || !out_off || !out_len || !tb_status || !cost_out)
+        return fail(GA_E_ARG, "null argument");
+    const double t_call = now_ms();
+    const int64_t max_waves = batch_max_waves(c);
+    gabatch::SampleLimits lim;
+    if (const char* e = c->knob("GA_BATCH_ALIGN_MAX_CELLS")) lim.max_cells = std::max<int64_t>(0, atoll(e));
+    if (const char* e = c->knob("GA_BATCH_SAMPLE_CHUNK_WORDS")) lim.chunk_tb_words = std::max<int64_t>(1, atoll(e));
+    if (const char* e = c->knob("GA_BATCH_SAMPLE_WALK_ENTRIES")) lim.walk_entries = std::max<int64_t>(1, atoll(e));
+    lim.scratch_rows_cap = gabatch::scratch_rows_cap(max_waves);
+    gabatch::SamplePlan plan;
+    std::string why;
+    if (int r = gabatch::plan_batch_sample(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, sample_off,
+                                           lim, plan, why))
+        return fail(r, why);
+    auto len_of = [&](int64_t s) { return seq_off[s + 1] - seq_off[s]; };
+    for (int64_t k = 0; k < npairs; k++)
+        for (int64_t f = sample_off[k]; f < sample_off[k + 1]; f++)
+            if (out_off[f] < 0 || out_off[f + 1] - out_off[f] < len_of(pair_a[k]) + len_of(pair_b[k]))
+                return fail(GA_E_ARG, "pair " + std::to_string(k) + ": output capacity too small");
+    if (!plan.single.empty() && c->slab)
+        return fail(GA_E_STATE, "pair " + std::to_string(plan.single[0]) +
+                                    ": needs the single-pair path, which a slab context cannot run");
+    const char* nt = c->knob("GA_BATCH_RNG_THREADS");
+    const size_t ncodes = (size_t)seq_off[nseq];
+    double walk_ticks = 0, walk_steps = 0;
+
+    // The walk launches `launches` over `witems` (both counted from 0 here) of the pairs `fitems`, whose work list and
+    // slices are on the device at fitems_dev / fwords_dev and whose words lie in tb (tb_words u32s, `layout`, `tc`);
+    // bt_codes holds the batch's codes.  Tables by the call's route; a walk launch whose generator reached a word cap
+    // runs again with host tables (the fill stays).  Then the copies back and the strings.
+    auto run_walks = [&](const std::vector<ga_batch_item>& fitems, const ga_batch_item* fitems_dev,
+                         const ga_batch_words_item* fwords_dev, const uint32_t* tb, int64_t tb_words, int CB, int layout,
+                         int tc, const ga_batch_sample_item* witems, const gabatch::WalkLaunch* launches,
+                         int64_t nlaunch) -> int {
+        for (int64_t L = 0; L < nlaunch; L++) {
+            const gabatch::WalkLaunch& wl = launches[L];
+            const ga_batch_sample_item* wi = witems + wl.first;
+            const int64_t nw = wl.count;
+            HIPCHK(c->bs_witems.ensure(sizeof(ga_batch_sample_item) * nw));
+            HIPCHK(c->bs_ticket.ensure(sizeof(unsigned)));
+            HIPCHK(c->bt_walk.ensure(sizeof(int4) * 2 * nw));
+            HIPCHK(c->bt_rng.ensure(sizeof(uint32_t) * wl.tab_entries));
+            HIPCHK(c->bt_ops.ensure(sizeof(uint32_t) * wl.ops_words));
+            HIPCHK(hipMemcpyAsync(c->bs_witems.p, wi, sizeof(ga_batch_sample_item) * nw, hipMemcpyHostToDevice, c->stream));
+            const int W = gabatch::kWavesPerGroup;
+            const int waves = (int)((std::min<int64_t>(max_waves, nw) + W - 1) / W * W);
+            std::vector<int4> walked((size_t)nw * 2);
+            std::vector<uint32_t> ops((size_t)wl.ops_words);
+            RngRoute route = rng_route(c, flags);
+            for (int attempt = 0;; attempt++) {
+                // every walk's table from its own seed: the device-routed items' by batch_rng_kernel ahead of the
+                // walks on the same stream, the others' on a few host threads meanwhile (threads sized by items)
+                std::vector<gabrng::Item> dev;
+                std::vector<ga_batch_item> host_items;
+                std::vector<ga_batch_walk_item> host_walk;
+                for (int64_t t = 0; t < nw; t++) {
+                    ga_batch_item it = fitems[(size_t)wi[t].fill];
+                    const int64_t steps = (int64_t)it.m + it.n;
+                    if (gabrng::route_device(route.want_device, steps, route.max_steps)) {
+                        dev.push_back(gabrng::Item{seeds[wi[t].out], wi[t].tab_off, (int32_t)steps, 0});
+                    } else {
+                        it.out = wi[t].out;  // (build_pair_tables takes the item's seed from seeds[out])
+                        host_items.push_back(it);
+                        host_walk.push_back(ga_batch_walk_item{wi[t].tab_off, wi[t].ops_off});
+                    }
+                }
+                int groups = 0;
+                if (!dev.empty())
+                    if (int r = enqueue_batch_rng(c, dev, c->bt_rng.as<uint32_t>(), route.cap_words, &groups)) return r;
+                const double t_tab = now_ms();
+                std::vector<uint32_t> tab(host_items.empty() ? 0 : (size_t)wl.tab_entries);
+                if (!host_items.empty()) {
+                    const int64_t nhost = (int64_t)host_items.size();
+                    gabatch::build_pair_tables(host_items.data(), host_walk.data(), nhost, seeds,
+                                               gabatch::rng_threads(nt ? atoi(nt) : 0, nhost), tab.data());
+                    int64_t first = host_walk[0].tab_off, last = first;
+                    for (int64_t t = 0; t < nhost; t++) {
+                        const int64_t off = host_walk[(size_t)t].tab_off;
+                        if (off != last) {
+                            if (int r = upload_table_range(c, tab.data(), c->bt_rng.as<uint32_t>(), first, last)) return r;
+                            first = off;
+                        }
+                        last = off + host_items[(size_t)t].m + host_items[(size_t)t].n;
+                    }
+                    if (int r = upload_table_range(c, tab.data(), c->bt_rng.as<uint32_t>(), first, last)) return r;
+                }
+                const float host_tab_ms = (float)(now_ms() - t_tab);
+                c->batch_sample_info[6] += (int64_t)dev.size();
+                c->batch_sample_info[7] += (int64_t)host_items.size();
+                // the walks' ticket starts at zero for every launch
+                HIPCHK(hipMemsetAsync(c->bs_ticket.p, 0, sizeof(unsigned), c->stream));
+                HIPCHK(hipEventRecord(c->wev[0], c->stream));
+                const ga::WalksArgs q{c->bt_codes.as<uint8_t>(), (long long)ncodes, cs->gap_open, fitems_dev, fwords_dev,
+                                      (int)fitems.size(), c->bs_witems.as<ga_batch_sample_item>(), (int)nw,
+                                      c->bs_ticket.as<unsigned>(), c->bt_rng.as<uint32_t>(), (long long)wl.tab_entries,
+                                      c->bt_ops.as<uint32_t>(), (long long)wl.ops_words, c->bt_walk.as<int4>(), tb,
+                                      (long long)tb_words, tc};
+                ga::launch_batch_walks(c->stream, q, CB, layout, waves);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipEventRecord(c->wev[1], c->stream));
+                c->batch_sample_info[5]++;
+                HIPCHK(hipMemcpyAsync(walked.data(), c->bt_walk.p, sizeof(int4) * 2 * nw, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipMemcpyAsync(ops.data(), c->bt_ops.p, sizeof(uint32_t) * ops.size(), hipMemcpyDeviceToHost,
+                                      c->stream));
+                std::vector<int32_t> rstatus(dev.size());
+                if (!dev.empty())
+                    HIPCHK(hipMemcpyAsync(rstatus.data(), c->bt_rstatus.p, sizeof(int32_t) * dev.size(),
+                                          hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipStreamSynchronize(c->stream));
+                float walk_ms = 0.f, gen_ms = 0.f;
+                HIPCHK(hipEventElapsedTime(&walk_ms, c->wev[0], c->wev[1]));
+                c->batch_sample_ms[1] += walk_ms;
+                if (!dev.empty()) HIPCHK(hipEventElapsedTime(&gen_ms, c->rev[0], c->rev[1]));
+                c->batch_sample_ms[2] += gen_ms + std::max(0.f, host_tab_ms - gen_ms);
+                bool capped = false;
+                for (const int32_t st : rstatus) capped |= st != gabrng::kComplete;
+                if (!capped) break;
+                // an item stopped at its word cap: its walk read unwritten entries (harmlessly: a walk makes at most
+                // m + n - 1 steps whatever the table holds); nothing of this launch is decoded, it runs again with
+                // host tables
+                if (attempt > 0) return fail(GA_E_STATE, "the host tables' walk launch reports a generator status");
+                route = rng_route(c, GA_BATCH_TABLES_HOST);
+            }
+            const double t_dec = now_ms();
+            std::vector<int64_t> lens((size_t)nw);
+            gabatch::run_shares(nw, gabatch::rng_threads(nt ? atoi(nt) : 0, nw), [&](int64_t first, int64_t stride) {
+                for (int64_t t = first; t < nw; t += stride) {
+                    const ga_batch_item& it = fitems[(size_t)wi[t].fill];
+                    const size_t f = (size_t)wi[t].out;
+                    const int4 wr = walked[2 * (size_t)t];
+                    tb_status[f] = GA_TB_OK;
+                    lens[(size_t)t] = out_len[f] =
+                        wr.x < 0 ? -3
+                        : wr.x > (int64_t)it.m + it.n
+                            ? -2
+                            : gabatch::decode_levels(ops.data() + wi[t].ops_off, wr.x, it.m, it.n, wr.y, wr.z, wr.w,
+                                                     chars + it.a_off, chars + it.b_off, out_a + out_off[f],
+                                                     out_mid + out_off[f], out_b + out_off[f], out_off[f + 1] - out_off[f]);
+                }
+            });
+            c->batch_sample_ms[3] += (float)(now_ms() - t_dec);
+            for (int64_t t = 0; t < nw; t++) {
+                const int64_t k = fitems[(size_t)wi[t].fill].out;
+                // (batch_single_pair names the pair of a large-route walk itself)
+                const std::string at = layout == gabatch::LAYOUT_BATCH ? "pair " + std::to_string(k) + ": " : std::string();
+                if (lens[(size_t)t] == -3) return fail(GA_E_STATE, at + "walk item does not fit the batch launch");
+                if (lens[(size_t)t] < 0) return fail(GA_E_STATE, at + "the walk's levels do not decode");
+                walk_ticks += walked[2 * (size_t)t + 1].y;
+                walk_steps += walked[2 * (size_t)t].x;
+            }
+            c->batch_sample_info[3] += nw;
+        }
+        return GA_OK;
+    };
+
+    // the kernel pairs, fill chunk by fill chunk
+    for (const gabatch::FillChunk& ch : plan.chunks) {
+        const std::vector<ga_batch_item> items(plan.kernel.begin() + ch.first, plan.kernel.begin() + ch.first + ch.count);
+        BatchStage bs;
+        if (int r = stage_batch(c, codes, seq_off, nseq, npairs, cs, items, plan.scratch_rows, bs)) return r;
+        HIPCHK(c->bs_words.ensure(sizeof(ga_batch_words_item) * items.size()));
+        if (c->bs_tb.ensure(sizeof(uint32_t) * (size_t)ch.tb_words) != hipSuccess) {
+            (void)hipStreamSynchronize(c->stream);  // the staged uploads read this call's buffers
+            return fail(GA_E_NOMEM, "no device memory for the batch's traceback words");
+        }
+        HIPCHK(hipMemcpyAsync(c->bs_words.p, plan.words.data() + ch.first, sizeof(ga_batch_words_item) * items.size(),
+                              hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipEventRecord(c->fb.ev[0], c->stream));
+        const ga::WordsArgs q{bs.args, c->bs_words.as<ga_batch_words_item>(), c->bs_tb.as<uint32_t>(),
+                              (long long)ch.tb_words};
+        ga::launch_batch_words(c->stream, q, plan.qbytes, plan.CB, bs.waves);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->fb.ev[1], c->stream));
+        c->batch_sample_info[4]++;
+        std::vector<long long> got((size_t)npairs);
+        HIPCHK(hipMemcpyAsync(got.data(), c->bt_out.p, sizeof(long long) * npairs, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipEventElapsedTime(&c->fill_ms, c->fb.ev[0], c->fb.ev[1]));
+        c->batch_sample_ms[0] += c->fill_ms;
+        for (const ga_batch_item& it : items) {
+            if (got[(size_t)it.out] == INT64_MIN)
+                return fail(GA_E_STATE, "pair " + std::to_string(it.out) + ": work item does not fit the batch launch");
+            cost_out[it.out] = got[(size_t)it.out];
+        }
+        c->batch_sample_info[0] += (int64_t)items.size();
+        if (int r = run_walks(items, c->bt_items.as<ga_batch_item>(), c->bs_words.as<ga_batch_words_item>(),
+                              c->bs_tb.as<uint32_t>(), ch.tb_words, plan.CB, gabatch::LAYOUT_BATCH, 0,
+                              plan.walk.data(), plan.launches.data() + ch.launch_first, ch.launch_count))
+            return r;
+    }
+
+    if (!plan.single.empty()) {
+        // They go through the context's problem slot, so no problem is loaded afterwards.
+        uint32_t state[MTN + 1];
+        for (const int64_t k : plan.single) {
+            const int64_t sa = pair_a[k], sb = pair_b[k];
+            const int64_t m = len_of(sa), n = len_of(sb);
+            bool filled = false;
+            if (std::min(m, n) >= 2) {
+                // A pair that left the kernel route for its size: one single-pair fill with stored words, as
+                // ga_problem_align's stored-words route up to the walk, where the words fit band_rows' budget; its
+                // samples then walk c->fb.tb in that fill's layout.
+                c->rc_used = false;
+                auto fill = [&](int64_t, int64_t) -> int {
+                    if (band_rows(c) != 0) return GA_OK;
+                    if (int r = enqueue_fill(c, GA_FILL_TRACEBACK)) return r;
+                    if (int r = finish_fill(c, &cost_out[k], nullptr)) return r;
+                    c->batch_sample_ms[6] += c->fill_ms;
+                    const gaplan::FillPlan& pl = c->plan;
+                    const int64_t tb_words = (int64_t)pl.nstripes * pl.T * pl.TC * 256;
+                    if ((int64_t)pl.TC * (16 / c->CB) < m || tb_words < gabatch::stripe_words(n, pl.TC))
+                        return fail(GA_E_STATE, "the fill's words do not cover the pair");
+                    ga_batch_item it{};
+                    it.a_off = (int32_t)seq_off[sa];
+                    it.m = (int32_t)m;
+                    it.b_off = (int32_t)seq_off[sb];
+                    it.n = (int32_t)n;
+                    it.out = (int32_t)k;
+                    const std::vector<ga_batch_item> items(1, it);
+                    const ga_batch_words_item ws{0, tb_words};
+                    std::vector<ga_batch_sample_item> walk;
+                    std::vector<gabatch::WalkLaunch> launches;
+                    gabatch::plan_walk_launches(items.data(), 1, sample_off, lim.walk_entries, walk, launches);
+                    HIPCHK(c->bt_codes.ensure(ncodes));
+                    HIPCHK(c->bt_items.ensure(sizeof(ga_batch_item)));
+                    HIPCHK(c->bs_words.ensure(sizeof(ga_batch_words_item)));
+                    HIPCHK(hipMemcpyAsync(c->bt_codes.p, codes, ncodes, hipMemcpyHostToDevice, c->stream));
+                    HIPCHK(hipMemcpyAsync(c->bt_items.p, items.data(), sizeof(ga_batch_item), hipMemcpyHostToDevice, c->stream));
+                    HIPCHK(hipMemcpyAsync(c->bs_words.p, &ws, sizeof(ws), hipMemcpyHostToDevice, c->stream));
+                    c->batch_sample_info[1]++;
+                    c->batch_sample_info[4]++;
+                    filled = true;
+                    return run_walks(items, c->bt_items.as<ga_batch_item>(), c->bs_words.as<ga_batch_words_item>(),
+                                     c->fb.tb.as<uint32_t>(), tb_words, c->CB, gabatch::LAYOUT_STRIPE, pl.TC, walk.data(),
+                                     launches.data(), (int64_t)launches.size());
+                };
+                if (int r = batch_single_pair(c, codes, seq_off, pair_a, pair_b, pair_max_cost, cs, k, fill)) return r;
+                c->filled_tb = false;
+            }
+            if (filled) continue;
+            // a one-letter sequence (only such a pair can raise the reference's IndexError or take its first-step
+            // quirk), or words beyond the budget: sample by sample through the single-pair path, each from its seeded
+            // state (the state it leaves is dropped)
+            c->rc_used = false;
+            for (int64_t f = sample_off[k]; f < sample_off[k + 1]; f++) {
+                auto align = [&](int64_t a_seq, int64_t b_seq) {
+                    seed_state(seeds[f], state);
+                    return ga_problem_align(c, state, chars + seq_off[a_seq], chars + seq_off[b_seq], out_a + out_off[f],
+                                            out_mid + out_off[f], out_b + out_off[f], out_off[f + 1] - out_off[f],
+                                            &out_len[f], &tb_status[f], &cost_out[k]);
+                };
+                if (int r = batch_single_pair(c, codes, seq_off, pair_a, pair_b, pair_max_cost, cs, k, align)) return r;
+            }
+            c->batch_sample_info[2]++;
+        }
+    }
+    c->batch_sample_ms[4] = (float)(now_ms() - t_call);
+    c->batch_sample_ms[5] = (float)(10.0 * walk_ticks / std::max(walk_steps, 1.0));  // (a tick is 10 ns)
+    return GA_OK;
+}
+
+int ga_batch_sample_info(ga_ctx* c, int64_t* out8) {
+    if (!c || !out8) return fail(GA_E_ARG, "null argument");
+    for (int q = 0; q < 8; q++) out8[q] = c->batch_sample_info[q];
+    return GA_OK;
+}
+
+int ga_batch_sample_timings(ga_ctx* c, float* out8) {
+    if (!c || !out8) return fail(GA_E_ARG, "null argument");
+    for (int q = 0; q < 8; q++) out8[q] = c->batch_sample_ms[q];
+    return GA_OK;
+}
+
 int ga_batch_align_timings(ga_ctx* c, float* out6) {
     if (!c || !out6) return fail(GA_E_ARG, "null argument");
     for (int q = 0; q < 6; q++) out6[q] = c->batch_align_ms[q];
@@ -3342,6 +3636,16 @@ int ga_batch_align_ex(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, i
     return guard_end(c, batch_align_ex_impl(c, codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, seeds,
                                             chars, out_a, out_mid, out_b, out_off, out_len, tb_status, cost_out,
                                             flags));
+}
+
+int ga_batch_sample(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                    const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                    const int64_t* sample_off, const uint64_t* seeds, const char* chars, char* out_a, char* out_mid,
+                    char* out_b, const int64_t* out_off, int64_t* out_len, int32_t* tb_status, int64_t* cost_out,
+                    uint32_t flags) {
+    return guard_end(c, batch_sample_impl(c, codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, sample_off,
+                                          seeds, chars, out_a, out_mid, out_b, out_off, out_len, tb_status, cost_out,
+                                          flags));
 }
 
 int ga_debug_pair_tables(ga_ctx* c, const uint64_t* seeds, const int32_t* steps, int64_t nitems, int32_t route,

@@ -26,7 +26,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _native
-from .results import AlignmentResults, BatchAlignments, BatchScores, final_cost_to_score
+from .results import AlignmentResults, BatchAlignments, BatchSamples, BatchScores, final_cost_to_score
 from .scoring import MAX_SEQ_LEN_PROD, get_max_val, validate_and_transform_args
 
 __version__ = "0.1.0"
@@ -184,6 +184,57 @@ class GlobalAligner:
         return BatchAlignments(strings[0], strings[1], strings[2], costs, b.scores(costs), b.scoring_mat, b.costing_mat,
                                b.gap_open_score, b.gap_open_cost)
 
+    def sample_alignments(self, seqs_1, seqs_2, samples=None, seeds=0, tables="host"):
+        """Many alignments of seqs_1[k] with seqs_2[k] for every k, each under a random seed of its own, from ONE fill
+        of the pair: the reference breaks traceback ties with random.choice, so a pair has a family of co-optimal
+        alignments, and only the walk depends on the seed.  ``samples`` is an int S >= 1 (every pair gets S) or one
+        int >= 1 per pair.  ``seeds`` is an int base -- the samples are numbered flat in pair order, f = 0, 1, ...,
+        and sample f uses base + f -- or a sequence with, per pair, the sequence of that pair's seeds (``samples`` may
+        then be None; if given it must agree).  Every effective seed lies in [0, 2**64).
+        Sample t of pair k is, byte for byte, what ``random.seed(s_kt)`` followed by
+        ``GlobalAligner(**settings).align(seqs_1[k], seqs_2[k])`` returns -- entry f of align_pairs on the lists with
+        every pair repeated once per sample; the process-global ``random`` state is left as it was.  Validation, the
+        IndexError of a one-letter pair (raised for the lowest pair any of whose samples raises it) and ``tables`` are
+        align_pairs's.
+        -> BatchSamples."""
+        if tables not in ("host", "device"):
+            raise ValueError(f"tables must be 'host' or 'device', not {tables!r}")
+        seqs_1, seqs_2 = list(seqs_1), list(seqs_2)
+        if len(seqs_1) != len(seqs_2):
+            raise ValueError(f"sample_alignments needs as many first as second sequences, got {len(seqs_1)} and "
+                             f"{len(seqs_2)}")
+        if not self.traceback:
+            raise ValueError("sample_alignments returns alignment strings; an aligner made with traceback=False scores "
+                             "batches with score_pairs")
+        if len(self.devices) > 1:
+            raise ValueError(f"sample_alignments runs on one GPU; this aligner was made with devices={self.devices}")
+        P = len(seqs_1)
+        counts, flat = _sample_seeds(samples, seeds, P)
+        sample_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        if P == 0:
+            e = self._empty_batch((0,))
+            return BatchSamples([], [], [], e.costs, e.scores, [], *e[2:])
+        b = self._prepare_batch(seqs_1 + seqs_2, np.arange(P, dtype=np.int64), np.arange(P, 2 * P, dtype=np.int64))
+        if b.text is None:
+            raise ValueError("sample_alignments takes sequences of one-byte (latin-1) letters")
+        eng = _native.default_engine(self.device)
+        route = {} if tables == "host" else {"rng_tables": tables}
+        costs, status, lengths, offsets, bufs = eng.batch_sample(b.codes, b.seq_off, b.pair_a, b.pair_b, b.tables,
+                                                                 sample_off, flat, np.frombuffer(b.text, dtype=np.uint8),
+                                                                 b.pair_max_cost, **route)
+        failed = np.flatnonzero(status == _native.GA_TB_INDEX_ERROR)
+        if failed.size:
+            k = int(np.searchsorted(sample_off, failed[0], side="right")) - 1
+            raise IndexError(f"pair {k}: string index out of range")  # the reference's, SURVEY A.5
+        texts = [buf.tobytes().decode("latin-1") for buf in bufs]
+        lo, hi = offsets[:-1].tolist(), (offsets[:-1] + lengths).tolist()
+        cut = sample_off.tolist()
+        strings = [[[t[x:y] for x, y in zip(lo[cut[k]:cut[k + 1]], hi[cut[k]:cut[k + 1]])] for k in range(P)]
+                   for t in texts]
+        return BatchSamples(strings[0], strings[1], strings[2], costs, b.scores(costs),
+                            [flat[cut[k]:cut[k + 1]].copy() for k in range(P)], b.scoring_mat, b.costing_mat,
+                            b.gap_open_score, b.gap_open_cost)
+
     def _empty_batch(self, shape):
         """No pairs: empty arrays, no launch.  The option checks still run, through the single call's validation of
         a placeholder pair; the matrices are reported only where they do not depend on the sequences (a named or
@@ -331,6 +382,60 @@ def _pair_seeds(seeds, P):
     if isinstance(seeds, numbers.Integral):
         return np.uint64(values[0]) + np.arange(P, dtype=np.uint64)
     return np.array(values, dtype=np.uint64)
+
+
+def _sample_seeds(samples, seeds, P):
+    """sample_alignments's samples and seeds as (counts: P ints >= 1, flat: the uint64 seeds of all samples in pair
+    order).  seeds is an int base (sample f of the flat numbering: base + f; samples is then needed) or one sequence
+    of ints per pair; the type and range errors are _pair_seeds's."""
+    counts = None
+    if samples is not None:
+        if isinstance(samples, numbers.Integral):
+            counts = [int(samples)] * P
+            if int(samples) < 1:
+                raise ValueError("samples must be at least 1")
+        else:
+            if isinstance(samples, (str, bytes)):
+                raise TypeError("samples must be an int or a sequence of ints")
+            try:
+                counts = list(samples)
+            except TypeError:
+                raise TypeError("samples must be an int or a sequence of ints") from None
+            if len(counts) != P:
+                raise ValueError(f"sample_alignments needs one sample count per pair, got {len(counts)} for {P} pairs")
+            if not all(isinstance(v, numbers.Integral) for v in counts):
+                raise TypeError("samples must be ints")
+            counts = [int(v) for v in counts]
+            if any(v < 1 for v in counts):
+                raise ValueError("every pair needs at least 1 sample")
+    if isinstance(seeds, numbers.Integral):
+        if counts is None:
+            if P:
+                raise ValueError("samples is needed with an int seed base")
+            counts = []
+        return counts, _pair_seeds(seeds, sum(counts))
+    if isinstance(seeds, (str, bytes)):
+        raise TypeError("seeds must be an int or a sequence of sequences of ints")
+    try:
+        per_pair = list(seeds)
+    except TypeError:
+        raise TypeError("seeds must be an int or a sequence of sequences of ints") from None
+    if len(per_pair) != P:
+        raise ValueError(f"sample_alignments needs one sequence of seeds per pair, got {len(per_pair)} for {P} pairs")
+    flat = []
+    for k, own in enumerate(per_pair):
+        if isinstance(own, (numbers.Integral, str, bytes)):
+            raise TypeError("seeds must be an int or a sequence of sequences of ints")
+        try:
+            own = list(own)
+        except TypeError:
+            raise TypeError("seeds must be an int or a sequence of sequences of ints") from None
+        if not own:
+            raise ValueError(f"pair {k} needs at least 1 seed")
+        flat.append(_pair_seeds(own, len(own)))
+    if counts is not None and counts != [len(x) for x in flat]:
+        raise ValueError("samples does not agree with the number of seeds given per pair")
+    return [len(x) for x in flat], (np.concatenate(flat) if flat else np.zeros(0, dtype=np.uint64))
 
 
 def _one_letter_sequences(upper, text, seq_off):

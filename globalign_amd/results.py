@@ -151,3 +151,34 @@ class BatchAlignments(NamedTuple):
         return AlignmentResults(self.seq_1_aligned[k], self.middle_part[k], self.seq_2_aligned[k], int(self.costs[k]),
                                 int(self.scores[k]), self.scoring_mat, self.costing_mat, self.gap_open_score,
                                 self.gap_open_cost, None)
+
+
+class BatchSamples(NamedTuple):
+    """Many seeded alignments of every pair (GlobalAligner.sample_alignments): per pair a list with one string per
+    sample, for each of the three lines; the pair's cost and score, which do not depend on the seed, in numpy int64
+    arrays of shape (P,); per pair the uint64 array of its samples' seeds; and the settings, as BatchAlignments
+    reports them."""
+    seq_1_aligned: list
+    middle_part: list
+    seq_2_aligned: list
+    costs: "numpy.ndarray"
+    scores: "numpy.ndarray"
+    seeds: list
+    scoring_mat: dict
+    costing_mat: dict
+    gap_open_score: int
+    gap_open_cost: int
+
+    def result(self, k, t):
+        """Sample t of pair k as an AlignmentResults (output=None), with the batch's matrices."""
+        return AlignmentResults(self.seq_1_aligned[k][t], self.middle_part[k][t], self.seq_2_aligned[k][t],
+                                int(self.costs[k]), int(self.scores[k]), self.scoring_mat, self.costing_mat,
+                                self.gap_open_score, self.gap_open_cost, None)
+
+    def distinct(self, k):
+        """Pair k's different alignments with how many samples gave each: a list of ((seq_1_aligned, middle_part,
+        seq_2_aligned), count) in order of first appearance."""
+        counts = {}
+        for key in zip(self.seq_1_aligned[k], self.middle_part[k], self.seq_2_aligned[k]):
+            counts[key] = counts.get(key, 0) + 1
+        return list(counts.items())

@@ -173,6 +173,43 @@ int ga_batch_align_ex(ga_ctx* ctx, const uint8_t* codes, const int64_t* seq_off,
  * reached a word cap and the pairs were redone with host tables (the first two then describe the device attempt),
  * workgroups of the generator's launch} of the last ga_batch_align(_ex) or ga_debug_pair_tables. */
 int ga_batch_align_info(ga_ctx* ctx, int32_t* out4);
+/* Many seeded alignments of every pair from one fill of the pair.  Pair k has
+ * the samples sample_off[k] .. sample_off[k + 1] (npairs + 1 entries, starting
+ * at 0, not decreasing); sample f is aligned under seeds[f] and is, byte for
+ * byte, entry f of ga_batch_align_ex on the pair lists with pair k repeated
+ * once per sample: its strings go to out_a / out_mid / out_b at out_off[f]
+ * (nsamples + 1 entries), out_len[f] bytes each, tb_status[f] receives GA_TB_OK
+ * or GA_TB_INDEX_ERROR; cost_out[k] receives pair k's cost, which does not
+ * depend on the seed.  codes .. costs, chars and flags are ga_batch_align_ex's,
+ * with the same checks, errors ("pair <k>: ...") and table routes; under the
+ * device route a walk launch whose generator reaches a word cap runs again with
+ * host tables.
+ * A kernel pair is filled once by batch_words_kernel, which keeps its traceback
+ * words in a slice of the pair's own, and walked once per sample by
+ * batch_walks_kernel, one wave per walk, in a later launch on the same stream.
+ * The pairs are cut into fill chunks whose slices stay within
+ * GA_BATCH_SAMPLE_CHUNK_WORDS u32 words (option, default 2^31: 8 GiB) and a
+ * chunk's walks into launches of at most GA_BATCH_SAMPLE_WALK_ENTRIES table
+ * entries (option, default 2^28: 1 GiB).  A pair of two letters or more a side
+ * that leaves the kernel route (above GA_BATCH_ALIGN_MAX_CELLS cells, LDS, edge
+ * scratch, or a slice over the chunk cap) is filled once by the single-pair
+ * fill with stored traceback words, if they fit the traceback budget
+ * (GA_TB_BUDGET_MB), and its samples are walked by the same kernel; any other
+ * pair is looped sample by sample through ga_problem_align. */
+int ga_batch_sample(ga_ctx* ctx, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                    const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* costs,
+                    const int64_t* sample_off, const uint64_t* seeds, const char* chars, char* out_a, char* out_mid,
+                    char* out_b, const int64_t* out_off, int64_t* out_len, int32_t* tb_status, int64_t* cost_out,
+                    uint32_t flags);
+/* out8 = {pairs filled by batch_words_kernel, pairs filled by the single-pair fill, pairs looped sample by sample,
+ * walk items, fill launches (batch_words_kernel's and single-pair fills), walk launches (a repeated one counts
+ * twice), walk items whose table the device made, walk items whose table the host made} of the last
+ * ga_batch_sample. */
+int ga_batch_sample_info(ga_ctx* ctx, int64_t* out8);
+/* out8 = {batch_words_kernel ms, batch_walks_kernel ms, tables ms (the generator's time plus the host table time it
+ * did not hide), host string decode ms, whole call wall ms, the walks' ns per dispatch (average of what each wave
+ * timed), single-pair fills ms, 0} of the last ga_batch_sample, summed over its launches. */
+int ga_batch_sample_timings(ga_ctx* ctx, float* out8);
 /* The tie-break tables alone, with no alignment: item t's steps[t] entries under seeds[t], concatenated in
  * tab_out, by route 1 (host) or 2 (device; an item over GA_BATCH_RNG_DEVICE_MAX_STEPS is built on the host, as
  * in the real call).  status_out[t]: 0 complete, 1 the word cap was reached (entries past the stop are

@@ -18,10 +18,18 @@ JSON line per workload with pairs, cells, ms (median of 5 calls after 2 warm-ups
                                                 time (runs on older trees too)
     python tools/batch_bench.py --align-crossover   one pair per align_pairs call through the batch kernel and through
                                                 the single-pair path, at growing sizes (GA_BATCH_ALIGN_MAX_CELLS)
+    python tools/batch_bench.py --sample        S1, S2, S3 through sample_alignments, each beside what
+                                                the tree could do for the same request before that call existed --
+                                                align_pairs on the repeated lists with the same seeds (S1, S2), a loop
+                                                of random.seed(s) + align over 32 of the seeds (S3) --, in alternating
+                                                rounds of one process: median, least and most of 5 after 2 warm-ups,
+                                                with the engine's own parts of the last call
 
 Workloads (SplitMix64 sequences of tests.conftest, lengths from a seeded random.Random):
   B1  4096 DNA pairs, lengths 200-400         B2  1024 BLOSUM62 pairs, lengths 100-600
-  B3  score_matrix of 256 DNA sequences of about 300"""
+  B3  score_matrix of 256 DNA sequences of about 300
+  S1  256 of B1's pairs x 16 samples          S2  one 300 x 257 DNA pair (random.Random(5)) x 4096 samples
+  S3  one 10k x 10k DNA pair x 256 samples (the single-pair fill's words, walked by batch_walks_kernel)"""
 import argparse
 import json
 import os
@@ -189,6 +197,67 @@ def align_crossover():
         del _native.OPTIONS["GA_BATCH_ALIGN_MAX_CELLS"]
 
 
+def sample_workloads():
+    def rounds(new, old):
+        for _ in range(WARMUP):
+            new(), old()
+        ms = ([], [])
+        for _ in range(REPEATS):
+            for which, call in enumerate((new, old)):
+                t0 = time.perf_counter()
+                call()
+                ms[which].append((time.perf_counter() - t0) * 1e3)
+        return ms
+
+    def spread(ms):
+        return dict(ms=round(statistics.median(ms), 4), ms_min=round(min(ms), 4), ms_max=round(max(ms), 4))
+
+    def run(name, pairs, count, old_samples=None):
+        """pairs x count samples from seed base 1; the other side: the same request (old_samples of the samples of
+        each pair, per-sample figures reported for both)."""
+        al = GlobalAligner(max_seq_len_prod=None, **DNA)
+        a, b = [p[0] for p in pairs], [p[1] for p in pairs]
+        eng, parts = _native.default_engine(0), {}
+
+        def new():
+            al.sample_alignments(a, b, samples=count, seeds=1)
+            parts["new"] = eng.batch_sample_timings()
+            parts["info"] = eng.batch_sample_info()
+
+        if old_samples is None:
+            flat_a = [x for x in a for _ in range(count)]
+            flat_b = [x for x in b for _ in range(count)]
+            n_old = len(flat_a)
+
+            def old():
+                al.align_pairs(flat_a, flat_b, seeds=1)
+                parts["old"] = eng.batch_align_timings()
+        else:
+            n_old = len(pairs) * old_samples
+
+            def old():
+                for k in range(len(pairs)):
+                    for t in range(old_samples):
+                        random.seed(1 + k * count + t)
+                        al.align(a[k], b[k])
+
+        ms_new, ms_old = rounds(new, old)
+        n_new = len(pairs) * count
+        print(json.dumps(dict(workload=name, pairs=len(pairs), samples=n_new, cells=sum(len(x) * len(y) for x, y in pairs),
+                              sample_alignments=dict(spread(ms_new), us_per_sample=round(statistics.median(ms_new) / n_new * 1e3, 3),
+                                                     **{k: round(v, 4) for k, v in parts["new"].items()}),
+                              info=parts["info"],
+                              before=dict(spread(ms_old), samples=n_old,
+                                          us_per_sample=round(statistics.median(ms_old) / n_old * 1e3, 3),
+                                          **{k: round(v, 4) for k, v in parts.get("old", {}).items()}))), flush=True)
+
+    run("S1", pairs_of(256, 200, 400, "dna", 1), 16)
+    rng = random.Random(5)
+    s2 = ("".join(rng.choice("ACGT") for _ in range(300)), "".join(rng.choice("ACGT") for _ in range(257)))
+    run("S2", [s2], 4096)
+    run("S3", [(splitmix_seq(10000, 1, "dna"), splitmix_seq(10000, 2, "dna"))], 256, old_samples=32)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--loop", type=int, default=0, metavar="K")
@@ -197,8 +266,11 @@ def main():
     ap.add_argument("--align-host", action="store_true")
     ap.add_argument("--align-loop", type=int, default=0, metavar="K")
     ap.add_argument("--align-crossover", action="store_true")
+    ap.add_argument("--sample", action="store_true")
     args = ap.parse_args()
-    if args.loop:
+    if args.sample:
+        sample_workloads()
+    elif args.loop:
         loop(args.loop)
     elif args.align or args.align_host:
         align_workloads(device=args.align)
