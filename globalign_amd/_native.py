@@ -5,6 +5,7 @@ GPU is visible, every entry point raises.  The shared library is built
 in-tree by ``__graft_entry__.build()`` (``make -C globalign_amd/csrc``).
 """
 import ctypes as C
+import dataclasses
 import json
 import os
 import threading
@@ -224,6 +225,78 @@ def options_string(options=None):
 # where a batch's tie-break tables are made (ga_batch_align_ex's flags)
 RNG_TABLES = {None: 0, "host": 1, "device": 2}
 
+_P32, _P64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+
+
+@dataclasses.dataclass
+class BatchArrays:
+    """batch_arrays's result: the arrays as the engine takes them (chars, seeds: None for a call without strings;
+    sample_off: None unless seeds are per sample; pair_max_cost: None for the tables' own)."""
+    codes: np.ndarray
+    seq_off: np.ndarray
+    pair_a: np.ndarray
+    pair_b: np.ndarray
+    chars: np.ndarray = None
+    seeds: np.ndarray = None
+    sample_off: np.ndarray = None
+    pair_max_cost: np.ndarray = None
+    P: int = 0      # pairs
+    S: int = 0      # output slots of a call with strings: samples, or pairs
+
+    @property
+    def pmc(self):  # pair_max_cost as the engine's pointer
+        return None if self.pair_max_cost is None else self.pair_max_cost.ctypes.data_as(_P32)
+
+
+def batch_arrays(codes, seq_off, pair_a, pair_b, pair_max_cost=None, chars=None, seeds=None, sample_off=None):
+    """The arrays of a batched call, contiguous in the engine's dtypes and checked (no device needed).  chars and seeds
+    given: a call with strings (Engine.batch_align), which also checks them and the sequence indices; sample_off
+    given as well: seeds are per sample (Engine.batch_sample), else per pair.  -> BatchArrays."""
+    strings = chars is not None
+    def arr(x, dtype, given=True):
+        return np.ascontiguousarray(x, dtype=dtype) if given else None
+    b = BatchArrays(arr(codes, np.uint8), arr(seq_off, np.int64), arr(pair_a, np.int32), arr(pair_b, np.int32),
+                    arr(chars, np.uint8, strings), arr(seeds, np.uint64, strings),
+                    arr(sample_off, np.int64, sample_off is not None))
+    if b.pair_a.shape != b.pair_b.shape or b.pair_a.ndim != 1 or b.seq_off.ndim != 1 or len(b.seq_off) < 1:
+        raise ValueError("pair_a and pair_b must be 1-d and of equal length, seq_off 1-d and non-empty")
+    if strings:
+        if int(b.seq_off[-1]) != b.codes.size or b.chars.size != b.codes.size:
+            raise ValueError("seq_off must end at len(codes), and chars must hold one byte per code")
+    elif int(b.seq_off[-1]) != b.codes.size:
+        raise ValueError("seq_off must end at len(codes)")
+    b.P = len(b.pair_a)
+    b.S = b.P if strings else 0
+    if b.sample_off is not None:
+        if b.sample_off.shape != (b.P + 1,) or int(b.sample_off[0]) != 0 or (np.diff(b.sample_off) < 0).any():
+            raise ValueError("sample_off must have one entry per pair and one more, start at 0 and not decrease")
+        b.S = int(b.sample_off[-1])
+        if b.seeds.shape != (b.S,):
+            raise ValueError("seeds must have one entry per sample")
+    elif strings and b.seeds.shape != b.pair_a.shape:
+        raise ValueError("seeds must have one entry per pair")
+    if strings and b.P and (min(b.pair_a.min(), b.pair_b.min()) < 0
+                            or max(b.pair_a.max(), b.pair_b.max()) >= len(b.seq_off) - 1):
+        raise ValueError("sequence index out of range")
+    if pair_max_cost is not None:
+        b.pair_max_cost = np.ascontiguousarray(pair_max_cost, dtype=np.int32)
+        if b.pair_max_cost.shape != b.pair_a.shape:
+            raise ValueError("pair_max_cost must have one entry per pair")
+    return b
+
+
+def batch_outputs(b):
+    """Where a call with strings writes: -> (offsets int64 (S + 1: a slot holds its pair's m + n + 1 bytes), the three
+    uint8 buffers, costs int64 per pair, lengths int64 and status int32 per slot, never empty)."""
+    lens = np.diff(b.seq_off)
+    per_slot = lens[b.pair_a] + lens[b.pair_b] + 1
+    if b.sample_off is not None:
+        per_slot = np.repeat(per_slot, np.diff(b.sample_off))
+    offsets = np.concatenate([[0], np.cumsum(per_slot)]).astype(np.int64)
+    bufs = tuple(np.empty(max(int(offsets[-1]), 1), dtype=np.uint8) for _ in range(3))
+    n = max(b.S, 1)
+    return offsets, bufs, np.zeros(b.P, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+
 
 class Engine:
     """One HIP device context (ga_ctx)."""
@@ -279,25 +352,9 @@ class Engine:
         sequence s at codes[seq_off[s]:seq_off[s + 1]]; pair k aligns sequence pair_a[k] with sequence pair_b[k];
         pair_max_cost: the max_cost of each pair's own costing matrix (None: tables.max_cost for all).
         -> int64 array of costs, in pair order.  Afterwards no problem counts as loaded."""
-        codes = np.ascontiguousarray(codes, dtype=np.uint8)
-        seq_off = np.ascontiguousarray(seq_off, dtype=np.int64)
-        pair_a = np.ascontiguousarray(pair_a, dtype=np.int32)
-        pair_b = np.ascontiguousarray(pair_b, dtype=np.int32)
-        if pair_a.shape != pair_b.shape or pair_a.ndim != 1 or seq_off.ndim != 1 or len(seq_off) < 1:
-            raise ValueError("pair_a and pair_b must be 1-d and of equal length, seq_off 1-d and non-empty")
-        if int(seq_off[-1]) != codes.size:
-            raise ValueError("seq_off must end at len(codes)")
-        out = np.zeros(len(pair_a), dtype=np.int64)
-        p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-        pmc = None
-        if pair_max_cost is not None:
-            pair_max_cost = np.ascontiguousarray(pair_max_cost, dtype=np.int32)
-            if pair_max_cost.shape != pair_a.shape:
-                raise ValueError("pair_max_cost must have one entry per pair")
-            pmc = pair_max_cost.ctypes.data_as(p32)
-        _check(self._L.ga_batch_costs_ex(self._h, codes.ctypes.data, seq_off.ctypes.data_as(p64), len(seq_off) - 1,
-                                         pair_a.ctypes.data_as(p32), pair_b.ctypes.data_as(p32), pmc, len(pair_a),
-                                         C.byref(tables.struct), out.ctypes.data_as(p64)))
+        b = batch_arrays(codes, seq_off, pair_a, pair_b, pair_max_cost)
+        out = np.zeros(b.P, dtype=np.int64)
+        _check(self._L.ga_batch_costs_ex(*self._batch_head(b, tables), out.ctypes.data_as(_P64)))
         self.m = self.n = 0
         return out
 
@@ -311,42 +368,8 @@ class Engine:
         counts as loaded."""
         if rng_tables not in RNG_TABLES:
             raise ValueError(f"rng_tables must be None, 'host' or 'device', not {rng_tables!r}")
-        codes = np.ascontiguousarray(codes, dtype=np.uint8)
-        chars = np.ascontiguousarray(chars, dtype=np.uint8)
-        seq_off = np.ascontiguousarray(seq_off, dtype=np.int64)
-        pair_a = np.ascontiguousarray(pair_a, dtype=np.int32)
-        pair_b = np.ascontiguousarray(pair_b, dtype=np.int32)
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        if pair_a.shape != pair_b.shape or pair_a.ndim != 1 or seq_off.ndim != 1 or len(seq_off) < 1:
-            raise ValueError("pair_a and pair_b must be 1-d and of equal length, seq_off 1-d and non-empty")
-        if int(seq_off[-1]) != codes.size or chars.size != codes.size:
-            raise ValueError("seq_off must end at len(codes), and chars must hold one byte per code")
-        if seeds.shape != pair_a.shape:
-            raise ValueError("seeds must have one entry per pair")
-        P = len(pair_a)
-        if P and (min(pair_a.min(), pair_b.min()) < 0 or max(pair_a.max(), pair_b.max()) >= len(seq_off) - 1):
-            raise ValueError("sequence index out of range")
-        p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-        pmc = None
-        if pair_max_cost is not None:
-            pair_max_cost = np.ascontiguousarray(pair_max_cost, dtype=np.int32)
-            if pair_max_cost.shape != pair_a.shape:
-                raise ValueError("pair_max_cost must have one entry per pair")
-            pmc = pair_max_cost.ctypes.data_as(p32)
-        lens = np.diff(seq_off)
-        offsets = np.concatenate([[0], np.cumsum(lens[pair_a] + lens[pair_b] + 1)]).astype(np.int64)
-        bufs = tuple(np.empty(max(int(offsets[-1]), 1), dtype=np.uint8) for _ in range(3))
-        costs = np.zeros(P, dtype=np.int64)
-        lengths = np.zeros(P, dtype=np.int64)
-        status = np.zeros(P, dtype=np.int32)
-        _check(self._L.ga_batch_align_ex(self._h, codes.ctypes.data, seq_off.ctypes.data_as(p64), len(seq_off) - 1,
-                                         pair_a.ctypes.data_as(p32), pair_b.ctypes.data_as(p32), pmc, P,
-                                         C.byref(tables.struct), seeds.ctypes.data, chars.ctypes.data,
-                                         bufs[0].ctypes.data, bufs[1].ctypes.data, bufs[2].ctypes.data,
-                                         offsets.ctypes.data_as(p64), lengths.ctypes.data_as(p64),
-                                         status.ctypes.data_as(p32), costs.ctypes.data_as(p64), RNG_TABLES[rng_tables]))
-        self.m = self.n = 0
-        return costs, status, lengths, offsets, bufs
+        b = batch_arrays(codes, seq_off, pair_a, pair_b, pair_max_cost, chars, seeds)
+        return self._batch_strings(self._L.ga_batch_align_ex, b, tables, (), rng_tables)
 
     def batch_sample(self, codes, seq_off, pair_a, pair_b, tables, sample_off, seeds, chars, pair_max_cost=None,
                      rng_tables=None):
@@ -358,47 +381,22 @@ class Engine:
         offsets[f] of each buffer.  Afterwards no problem counts as loaded."""
         if rng_tables not in RNG_TABLES:
             raise ValueError(f"rng_tables must be None, 'host' or 'device', not {rng_tables!r}")
-        codes = np.ascontiguousarray(codes, dtype=np.uint8)
-        chars = np.ascontiguousarray(chars, dtype=np.uint8)
-        seq_off = np.ascontiguousarray(seq_off, dtype=np.int64)
-        pair_a = np.ascontiguousarray(pair_a, dtype=np.int32)
-        pair_b = np.ascontiguousarray(pair_b, dtype=np.int32)
-        sample_off = np.ascontiguousarray(sample_off, dtype=np.int64)
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        if pair_a.shape != pair_b.shape or pair_a.ndim != 1 or seq_off.ndim != 1 or len(seq_off) < 1:
-            raise ValueError("pair_a and pair_b must be 1-d and of equal length, seq_off 1-d and non-empty")
-        if int(seq_off[-1]) != codes.size or chars.size != codes.size:
-            raise ValueError("seq_off must end at len(codes), and chars must hold one byte per code")
-        P = len(pair_a)
-        if sample_off.shape != (P + 1,) or int(sample_off[0]) != 0 or (np.diff(sample_off) < 0).any():
-            raise ValueError("sample_off must have one entry per pair and one more, start at 0 and not decrease")
-        S = int(sample_off[-1])
-        if seeds.shape != (S,):
-            raise ValueError("seeds must have one entry per sample")
-        if P and (min(pair_a.min(), pair_b.min()) < 0 or max(pair_a.max(), pair_b.max()) >= len(seq_off) - 1):
-            raise ValueError("sequence index out of range")
-        p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-        pmc = None
-        if pair_max_cost is not None:
-            pair_max_cost = np.ascontiguousarray(pair_max_cost, dtype=np.int32)
-            if pair_max_cost.shape != pair_a.shape:
-                raise ValueError("pair_max_cost must have one entry per pair")
-            pmc = pair_max_cost.ctypes.data_as(p32)
-        lens = np.diff(seq_off)
-        per_pair = lens[pair_a] + lens[pair_b] + 1
-        offsets = np.concatenate([[0], np.cumsum(np.repeat(per_pair, np.diff(sample_off)))]).astype(np.int64)
-        bufs = tuple(np.empty(max(int(offsets[-1]), 1), dtype=np.uint8) for _ in range(3))
-        costs = np.zeros(P, dtype=np.int64)
-        lengths = np.zeros(max(S, 1), dtype=np.int64)
-        status = np.zeros(max(S, 1), dtype=np.int32)
-        _check(self._L.ga_batch_sample(self._h, codes.ctypes.data, seq_off.ctypes.data_as(p64), len(seq_off) - 1,
-                                       pair_a.ctypes.data_as(p32), pair_b.ctypes.data_as(p32), pmc, P,
-                                       C.byref(tables.struct), sample_off.ctypes.data_as(p64), seeds.ctypes.data,
-                                       chars.ctypes.data, bufs[0].ctypes.data, bufs[1].ctypes.data, bufs[2].ctypes.data,
-                                       offsets.ctypes.data_as(p64), lengths.ctypes.data_as(p64),
-                                       status.ctypes.data_as(p32), costs.ctypes.data_as(p64), RNG_TABLES[rng_tables]))
+        b = batch_arrays(codes, seq_off, pair_a, pair_b, pair_max_cost, chars, seeds, sample_off)
+        return self._batch_strings(self._L.ga_batch_sample, b, tables, (b.sample_off.ctypes.data_as(_P64),), rng_tables)
+
+    def _batch_head(self, b, tables):
+        """The arguments every batched entry begins with."""
+        return (self._h, b.codes.ctypes.data, b.seq_off.ctypes.data_as(_P64), len(b.seq_off) - 1,
+                b.pair_a.ctypes.data_as(_P32), b.pair_b.ctypes.data_as(_P32), b.pmc, b.P, C.byref(tables.struct))
+
+    def _batch_strings(self, fn, b, tables, extra, rng_tables):
+        """ga_batch_align_ex or ga_batch_sample (`extra`: its arguments before the seeds) into batch_outputs's buffers."""
+        offsets, bufs, costs, lengths, status = batch_outputs(b)
+        _check(fn(*self._batch_head(b, tables), *extra, b.seeds.ctypes.data, b.chars.ctypes.data, bufs[0].ctypes.data,
+                  bufs[1].ctypes.data, bufs[2].ctypes.data, offsets.ctypes.data_as(_P64), lengths.ctypes.data_as(_P64),
+                  status.ctypes.data_as(_P32), costs.ctypes.data_as(_P64), RNG_TABLES[rng_tables]))
         self.m = self.n = 0
-        return costs, status[:S], lengths[:S], offsets, bufs
+        return costs, status[:b.S], lengths[:b.S], offsets, bufs
 
     def batch_sample_info(self):
         """{filled_pairs, single_fill_pairs, looped_pairs, walk_items, fill_launches, walk_launches, device_items,

@@ -1,12 +1,13 @@
 // ga_batch_align.h -- the host's share of a batch of alignments with strings (ga_batch_align; no HIP: built into
 // the engine and into ga_batch_align_selftest.cpp under AddressSanitizer / UBSan / ThreadSanitizer).
 //
-// Every pair of the batch walks with a tie-break stream of its own, the one `random.seed(seed)` starts, so the walks
-// do not depend on each other: build_pair_tables makes the kernel pairs' tables (ga_rng.h) on a few threads, and
-// decode_levels turns a finished walk's packed levels into the three alignment strings with the engine's one decoder
-// (ga_strings.h) in its strict mode, checking that the levels lead to the end cell the walk reported.  Under the
-// device route (ga_batch_align_ex, ga_batch_rng.h) build_pair_tables makes only the tables of the items that stay
-// on the host.
+// Every walk of a batch (a pair of ga_batch_align, a sample of ga_batch_sample) has a tie-break stream of its own,
+// the one `random.seed(seed)` starts, so the walks do not depend on each other.  A walk's table is one gabrng::Item
+// (seed, tab_off, steps): split_tables divides a launch's jobs between the device generator (ga_batch_rng.h) and the
+// host and names the host jobs' upload ranges, build_tables makes the host jobs' tables (ga_rng.h) on a few threads,
+// and decode_walk / decode_levels turn a finished walk's packed levels into the three alignment strings with the
+// engine's one decoder (ga_strings.h) in its strict mode, checking that the levels lead to the end cell the walk
+// reported.
 #pragma once
 #include <stdint.h>
 
@@ -15,6 +16,7 @@
 #include <vector>
 
 #include "ga_batch.h"
+#include "ga_batch_rng.h"
 #include "ga_rng.h"
 #include "ga_strings.h"
 
@@ -45,20 +47,47 @@ inline void run_shares(int64_t nitems, int nthreads, Share share) {
     for (std::thread& th : pool) th.join();
 }
 
-// tab[walk[t].tab_off .. + m + n): the entries of work item t under seeds[items[t].out]; no two items share entries.
-inline void build_pair_tables(const ga_batch_item* items, const ga_batch_walk_item* walk, int64_t nitems,
-                              const uint64_t* seeds, int nthreads, uint32_t* tab) {
-    run_shares(nitems, nthreads, [=](int64_t first, int64_t stride) {
+// tab[jobs[t].tab_off .. + jobs[t].steps): the entries of job t under jobs[t].seed; no two jobs share entries.
+inline void build_tables(const gabrng::Item* jobs, int64_t njobs, int nthreads, uint32_t* tab) {
+    run_shares(njobs, nthreads, [=](int64_t first, int64_t stride) {
         garng::RngTable R;
         uint32_t state[garng::MTN + 1];
-        for (int64_t t = first; t < nitems; t += stride) {
-            const int64_t steps = (int64_t)items[t].m + items[t].n;
-            garng::seed_state(seeds[items[t].out], state);
+        for (int64_t t = first; t < njobs; t += stride) {
+            garng::seed_state(jobs[t].seed, state);
             R.start(state);
-            R.extend(steps);
-            std::copy(R.tab.begin(), R.tab.begin() + steps, tab + walk[t].tab_off);
+            R.extend(jobs[t].steps);
+            std::copy(R.tab.begin(), R.tab.begin() + jobs[t].steps, tab + jobs[t].tab_off);
         }
     });
+}
+
+// A job list by gabrng::route_device: the generator's jobs and the host's, each in list order (dev_at: a device
+// job's place in the list), and the host jobs' entries as the ranges [first, last) they are uploaded in -- in list
+// order, a range grows only while the next host job's tab_off is its end.
+struct TableRange {
+    int64_t first, last;
+};
+struct TableSplit {
+    std::vector<gabrng::Item> dev, host;
+    std::vector<int64_t> dev_at;
+    std::vector<TableRange> ranges;
+};
+inline TableSplit split_tables(const gabrng::Item* jobs, int64_t njobs, bool want_device, int64_t max_steps) {
+    TableSplit sp;
+    for (int64_t t = 0; t < njobs; t++) {
+        const gabrng::Item& jb = jobs[t];
+        if (gabrng::route_device(want_device, jb.steps, max_steps)) {
+            sp.dev.push_back(jb);
+            sp.dev_at.push_back(t);
+            continue;
+        }
+        sp.host.push_back(jb);
+        if (jb.steps <= 0) continue;
+        if (sp.ranges.empty() || sp.ranges.back().last != jb.tab_off)
+            sp.ranges.push_back(TableRange{jb.tab_off, jb.tab_off});
+        sp.ranges.back().last += jb.steps;
+    }
+    return sp;
 }
 
 // The strings of one walk from (m, n): the levels of dispatches [0, D) out of `ops` through ga_strings.h's strict
@@ -72,6 +101,32 @@ inline int64_t decode_levels(const uint32_t* ops, int64_t D, int64_t m, int64_t 
     if (col.i != i_end || col.j != j_end || (col.i > 0 && col.j > 0)) return -2;
     const int64_t len = gastr::finish_strings(reason, col.i, col.j, a_chr, b_chr, oa, om, ob, cap, col.len);
     return len > cap ? -1 : len;
+}
+
+// Where a batch's strings go: walk or sample `slot` has out_off[slot + 1] - out_off[slot] characters at out_off[slot]
+// of each of the three buffers, its length in out_len[slot] and its traceback status in tb_status[slot].
+struct WalkOut {
+    const char* chars;  // every sequence's characters, at its codes' offsets
+    char *out_a, *out_mid, *out_b;
+    const int64_t* out_off;
+    int64_t* out_len;
+    int32_t* tb_status;
+};
+
+// A finished walk of `it` to its slot: wr are the walk's result words {dispatches, i_end, j_end, reason}, ops its
+// level words; no_fit: the launch reported that the item did not fit it.  Sets tb_status and out_len and returns
+// out_len: the length, or -3 (no_fit), -2 (dispatches outside [0, m + n], or levels that do not decode) or -1
+// (decode_levels).
+inline int64_t decode_walk(const ga_batch_item& it, const int32_t* wr, const uint32_t* ops, int64_t slot, bool no_fit,
+                           const WalkOut& o) {
+    const int64_t at = o.out_off[slot];
+    o.tb_status[slot] = GA_TB_OK;
+    return o.out_len[slot] = no_fit ? -3
+                             : wr[0] < 0 || wr[0] > (int64_t)it.m + it.n
+                                 ? -2
+                                 : decode_levels(ops, wr[0], it.m, it.n, wr[1], wr[2], wr[3], o.chars + it.a_off,
+                                                 o.chars + it.b_off, o.out_a + at, o.out_mid + at, o.out_b + at,
+                                                 o.out_off[slot + 1] - at);
 }
 
 }  // namespace gabatch

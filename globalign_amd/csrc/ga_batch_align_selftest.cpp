@@ -1,6 +1,6 @@
 // ga_batch_align_selftest.cpp -- CPU self-test of the host's share of ga_batch_align: the align planner (ga_batch.h
-// plan_batch_align), the per-pair tie-break tables and the levels-to-strings decode (ga_batch_align.h's decode_levels
-// and, under it and under every single-pair walk, ga_strings.h's resumable decoder), plain, under
+// plan_batch_align), the table jobs' split and build and the levels-to-strings decode (ga_batch_align.h's decode_walk /
+// decode_levels and, under them and under every single-pair walk, ga_strings.h's resumable decoder), plain, under
 // AddressSanitizer + UndefinedBehaviorSanitizer and -- for the threaded table build -- under ThreadSanitizer
 // (make -C globalign_amd/csrc batch_align_selftest batch_align_asan batch_align_tsan; run by
 // tests/test_batch_align_host.py).  No HIP: the kernel is tested on the GPU.
@@ -229,6 +229,31 @@ void test_decode() {
                             ob.data(), len - 1) == -1, "capacity");
         CHECK(decode_levels(ops.data(), (int64_t)lv.size(), m, n, i + 1, j, reason, a.data(), b.data(), oa.data(),
                             om.data(), ob.data(), cap) == -2, "end cell");
+        // the same walk through decode_walk: sequences side by side in one chars buffer, output slot 1 of two
+        const std::string chars = "xyz" + a + b;
+        ga_batch_item it{};
+        it.a_off = 3;
+        it.m = m;
+        it.b_off = 3 + m;
+        it.n = n;
+        const int64_t off[3] = {0, 5, 5 + cap};
+        std::vector<char> wa2((size_t)(5 + cap), '?'), wm2(wa2), wb2(wa2);
+        int64_t lens[2] = {77, 77};
+        int32_t status[2] = {77, 77};
+        const WalkOut o{chars.data(), wa2.data(), wm2.data(), wb2.data(), off, lens, status};
+        const int32_t wr[4] = {(int32_t)lv.size(), i, j, reason};
+        CHECK(decode_walk(it, wr, ops.data(), 1, false, o) == len && lens[1] == len && status[1] == GA_TB_OK,
+              "decode_walk's length");
+        CHECK(lens[0] == 77 && status[0] == 77 && wa2[4] == '?' && std::string(wa2.data() + 5, (size_t)len) == wa &&
+                  std::string(wm2.data() + 5, (size_t)len) == wm && std::string(wb2.data() + 5, (size_t)len) == wb,
+              "decode_walk's strings, in its slot only (walk %d)", rep);
+        const int32_t end_off[4] = {wr[0], i + 1, j, reason}, neg[4] = {-1, i, j, reason}, past[4] = {m + n + 1, i, j, reason};
+        CHECK(decode_walk(it, end_off, ops.data(), 1, false, o) == -2 && lens[1] == -2, "decode_walk: end cell");
+        CHECK(decode_walk(it, neg, ops.data(), 1, false, o) == -2 && decode_walk(it, past, ops.data(), 1, false, o) == -2,
+              "decode_walk: dispatches outside [0, m + n]");
+        CHECK(decode_walk(it, wr, ops.data(), 1, true, o) == -3 && lens[1] == -3 && status[1] == GA_TB_OK,
+              "decode_walk: an item that did not fit");
+        CHECK(decode_walk(it, neg, ops.data(), 1, true, o) == -3, "decode_walk: did not fit comes first");
     }
     CHECK(tails[0] > 0 && tails[1] > 0 && tails[2] > 0, "corner %d, row-0 %d and column-0 %d endings all occur", tails[0],
           tails[1], tails[2]);
@@ -392,12 +417,25 @@ void test_seed_and_tables() {
     std::string err;
     CHECK(plan(sq, pa, pb, t, wide_limits(), p, err) == GA_OK, "plan failed: %s", err.c_str());
     std::vector<uint32_t> one((size_t)p.tab_entries, 0xdeadbeefu), many((size_t)p.tab_entries, 0xdeadbeefu);
-    build_pair_tables(p.kernel.data(), p.walk.data(), (int64_t)p.kernel.size(), seeds.data(), 1, one.data());
+    std::vector<gabrng::Item> jobs;
+    for (size_t k = 0; k < p.kernel.size(); k++)
+        jobs.push_back(gabrng::Item{seeds[(size_t)p.kernel[k].out], p.walk[k].tab_off, p.kernel[k].m + p.kernel[k].n, 0});
+    build_tables(jobs.data(), (int64_t)jobs.size(), 1, one.data());
     for (int nt : {2, 3, 8, 64}) {
         std::fill(many.begin(), many.end(), 0xdeadbeefu);
-        build_pair_tables(p.kernel.data(), p.walk.data(), (int64_t)p.kernel.size(), seeds.data(), nt, many.data());
+        build_tables(jobs.data(), (int64_t)jobs.size(), nt, many.data());
         CHECK(one == many, "%d threads give the sequential tables", nt);
     }
+    // every job's table is the one garng::RngTable makes from its seed, and no entry outside the jobs is written
+    std::vector<uint32_t> direct((size_t)p.tab_entries, 0xdeadbeefu);
+    for (const gabrng::Item& jb : jobs) {
+        garng::RngTable R;
+        garng::seed_state(jb.seed, st);
+        R.start(st);
+        R.extend(jb.steps);
+        std::copy(R.tab.begin(), R.tab.begin() + jb.steps, direct.begin() + jb.tab_off);
+    }
+    CHECK(one == direct, "a table per job, made directly");
     // a pair's table is build_rng's from its seeded state, whatever else the batch holds
     for (size_t k = 0; k < p.kernel.size(); k += 50) {
         garng::RngTable R;
@@ -412,9 +450,63 @@ void test_seed_and_tables() {
     CHECK(rng_threads(1, 1 << 20) == 1 && rng_threads(5, 10) == 5 && rng_threads(99, 10) == kMaxRngThreads, "requested");
 }
 
+// split_tables on `jobs` (entries: the table's size): the two lists partition the jobs in order, by the route rule;
+// the ranges cover the host jobs' entries once and nothing else; no range is empty or begins where another ends
+// (the route per job is restated here as the rule's own expression, so the counts want_dev and want_ranges, worked out
+// by hand at every call, are the independent reference for the rule)
+void check_split(const std::vector<gabrng::Item>& jobs, int64_t entries, bool want_device, int64_t limit, size_t want_dev,
+                 size_t want_ranges) {
+    const TableSplit sp = split_tables(jobs.data(), (int64_t)jobs.size(), want_device, limit);
+    auto same = [](const gabrng::Item& x, const gabrng::Item& y) {
+        return x.seed == y.seed && x.tab_off == y.tab_off && x.steps == y.steps && x.pad == y.pad;
+    };
+    CHECK(sp.dev.size() == want_dev && sp.dev.size() + sp.host.size() == jobs.size() && sp.dev_at.size() == sp.dev.size(),
+          "limit %lld: %zu device and %zu host jobs of %zu", (long long)limit, sp.dev.size(), sp.host.size(), jobs.size());
+    std::vector<int> want((size_t)entries, 0), cover((size_t)entries, 0);
+    size_t q = 0, h = 0;
+    for (size_t t = 0; t < jobs.size(); t++) {
+        const bool dev = want_device && jobs[t].steps <= limit;
+        if (dev) {
+            CHECK(q < sp.dev.size() && sp.dev_at[q] == (int64_t)t && same(sp.dev[q], jobs[t]), "job %zu is device job %zu", t, q);
+            q++;
+        } else {
+            CHECK(h < sp.host.size() && same(sp.host[h], jobs[t]), "job %zu is host job %zu", t, h);
+            h++;
+            for (int64_t d = 0; d < jobs[t].steps; d++) want[(size_t)(jobs[t].tab_off + d)]++;
+        }
+    }
+    for (const TableRange& rg : sp.ranges) {
+        CHECK(0 <= rg.first && rg.first < rg.last && rg.last <= entries, "range [%lld, %lld)", (long long)rg.first,
+              (long long)rg.last);
+        for (int64_t d = std::max<int64_t>(rg.first, 0); d < std::min(rg.last, entries); d++) cover[(size_t)d]++;
+        for (const TableRange& other : sp.ranges) CHECK(rg.last != other.first, "ranges touch at %lld", (long long)rg.last);
+    }
+    CHECK(want == cover, "limit %lld: the ranges cover the host jobs' entries, once", (long long)limit);
+    CHECK(sp.ranges.size() == want_ranges, "limit %lld: %zu ranges, want %zu", (long long)limit, sp.ranges.size(), want_ranges);
+}
+
+void test_split() {
+    // steps at entry offsets: two host neighbours, a device job, a host job behind it, jobs at the limit 10 and one
+    // under it, a jump to 100 with a neighbour, a last device job
+    const int32_t steps[] = {12, 15, 8, 11, 10, 9, 20, 11, 3};
+    const int64_t offs[] = {0, 12, 27, 35, 46, 56, 100, 120, 131};
+    std::vector<gabrng::Item> jobs;
+    for (int k = 0; k < 9; k++) jobs.push_back(gabrng::Item{0x1234567800ull + (uint64_t)k, offs[k], steps[k], 0});
+    const int64_t entries = 134;
+    check_split(jobs, entries, true, 9, 3, 3);    // host: [0, 27) [35, 56) [100, 131)
+    check_split(jobs, entries, true, 10, 4, 3);   // host: [0, 27) [35, 46) [100, 131)
+    check_split(jobs, entries, true, 11, 6, 2);   // host: [0, 27) [100, 120)
+    check_split(jobs, entries, true, 1 << 20, 9, 0);
+    check_split(jobs, entries, false, 1 << 20, 0, 2);  // all host: [0, 65) [100, 134)
+    check_split(jobs, entries, true, 0, 0, 2);
+    check_split(std::vector<gabrng::Item>(), 0, true, 10, 0, 0);
+    check_split(std::vector<gabrng::Item>(), 0, false, 10, 0, 0);
+}
+
 }  // namespace
 
 int main() {
+    test_split();
     test_routing_and_order();
     test_limits();
     test_word_widths();

@@ -10,35 +10,44 @@
 //     while the device fill runs;
 //   * string assembly from the walk's per-step levels (take_* :688-753,
 //     the i==0 / j==0 tails :542-581 and the final reverse :584-586): ga_strings.h.
-#include <hip/hip_runtime.h>
 #include <unistd.h>
 
-#include <algorithm>
 #include <condition_variable>
-#include <map>
 #include <mutex>
 #include <thread>
 #include <chrono>
-#include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include <string>
-#include <vector>
 
-#include "../../include/globalign_amd.h"
-#include "ga_device.h"
+#include "ga_host_internal.h"
 #include "ga_lane.h"
 #include "ga_check.h"
-#include "ga_batch.h"
-#include "ga_batch_align.h"
-#include "ga_batch_layout.h"
-#include "ga_batch_rng.h"
-#include "ga_guard.h"
-#include "ga_plan.h"
-#include "ga_rng.h"
 #include "ga_strings.h"
 
-namespace {
+// ------------------------------------------------------------------ context
+// The GA_* variables the shipped library reads from the environment (INTEGRATION.md lists them): the path choices
+// and budgets an operator may want to set.  Every other option -- kernel variants for tests and tuning, fault
+// injection, diagnostics -- reaches a context only through ga_ctx_create_opts, never from the environment, so a
+// stray variable cannot change a production context's kernels or inject a fault (ADVICE r5).  An experiments build
+// (make EXPERIMENTS=1) takes every GA_* variable.
+const char* const kEnvKnobs[] = {"GA_RC",           "GA_RC_MIN_CELLS", "GA_RC_BUDGET_MB",      "GA_RC_EVERY",
+                                 "GA_RC_SERVERS",   "GA_TB_BUDGET_MB", "GA_FILL_MODE",         "GA_COLS_PER_LANE",
+                                 "GA_LANE_COLS_PER_LANE", "GA_PIPE_FILLS", "GA_PIPE_CHAIN",    "GA_STREAM_PRIORITY",
+                                 "GA_HALO_SPIN_LIMIT", "GA_PIPE_TRACE"};
+bool env_knob(const std::string& name) {
+#ifdef GA_EXPERIMENTS
+    return name.compare(0, 3, "GA_") == 0;
+#else
+    for (const char* k : kEnvKnobs)
+        if (name == k) return true;
+    return false;
+#endif
+}
+
+using namespace gahost;
+using namespace garng;
+
+namespace gahost {
 
 thread_local std::string g_err;
 
@@ -46,108 +55,6 @@ int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
-
-#define HIPCHK(expr)                                                                               \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(GA_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));              \
-    } while (0)
-
-// ------------------------------------------------------------------ buffers
-struct DevBuf;
-struct PinBuf;
-// Guard mode (ga_guard.h; options GA_GUARD_BYTES / GA_GUARD_FILL / GA_GUARD_POISON, never the
-// environment): one per context, shared by its buffers and its pipeline slots'.  Every buffer is allocated with G
-// bytes of a pattern in front of and behind what its kernels may write, and guard_check reads them back.
-struct GuardCfg {
-    size_t G = 0;
-    uint8_t fill = (uint8_t)gaguard::kDefaultFill;
-    bool poison = false;   // the payload starts as the pattern too
-    // the chained pipeline's persistent kernel runs (align_chain sets it around the launch): that kernel waits for
-    // this thread, so nothing may wait for the device or free memory; a buffer that asks for another size then is refused
-    bool in_chain = false;
-    std::vector<DevBuf*> dev;
-    std::vector<PinBuf*> pin;
-    // what a re-lay or a reallocation found in the guard it was about to overwrite, kept for the next check
-    std::vector<gaguard::Violation> pending;
-};
-
-// Device memory that grows on demand and is released with its owner (a context or a pipeline slot): nothing copies
-// one, FillBufs, Band and the launches' argument structs hold pointers into it.
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    bool uncached = false;
-    // guard mode (nullptr: off): p and cap are what they are without it -- the kernels' pointer and budget -- inside
-    // an allocation of goff + cap + goff bytes; size is the last request, where the rear guard begins
-    GuardCfg* g = nullptr;
-    size_t goff = 0, size = 0;
-    std::string name;
-    explicit DevBuf(bool uncached_ = false) : uncached(uncached_) {}
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }
-    hipError_t ensure(size_t bytes) {
-        if (g) return ensure_guarded(bytes);
-        if (bytes <= cap && p) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = std::max<size_t>(bytes, 256);
-        hipError_t e = uncached ? hipExtMallocWithFlags(&p, want, hipDeviceMallocUncached) : hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    hipError_t ensure_guarded(size_t bytes);
-    void release() {
-        if (p) (void)hipFree(static_cast<uint8_t*>(p) - goff);
-        p = nullptr;
-        cap = goff = size = 0;
-    }
-    // release() outside the destructor: in guard mode what the guards caught is kept for the next check first
-    void release_checked();
-    template <typename T>
-    T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-// Its pinned-host counterpart: plain pinned memory (staging for asynchronous copies), or mapped and coherent, which the
-// device reads and writes in place through dev().  It grows by free-then-allocate at the ensure() call, never later: a
-// free while a persistent kernel polls host memory would wait for that kernel (align_chain).
-struct PinBuf {
-    void* p = nullptr;
-    void* dp = nullptr;  // the same memory as the device sees it (mapped buffers), looked up once per allocation
-    size_t cap = 0;
-    bool mapped = false;
-    GuardCfg* g = nullptr;  // guard mode, as DevBuf's
-    size_t goff = 0, size = 0;
-    std::string name;
-    explicit PinBuf(bool mapped_ = false) : mapped(mapped_) {}
-    PinBuf(const PinBuf&) = delete;
-    PinBuf& operator=(const PinBuf&) = delete;
-    ~PinBuf() {
-        if (p) (void)hipHostFree(static_cast<uint8_t*>(p) - goff);
-    }
-    hipError_t ensure(size_t bytes) {
-        if (g) return ensure_guarded(bytes);
-        if (bytes <= cap && p) return hipSuccess;
-        void* old = p;
-        p = dp = nullptr;
-        cap = 0;
-        if (old)
-            if (hipError_t e = hipHostFree(old); e != hipSuccess) return e;
-        const unsigned flags = mapped ? hipHostMallocMapped | hipHostMallocCoherent : hipHostMallocDefault;
-        hipError_t e = hipHostMalloc(&p, bytes, flags);
-        if (e == hipSuccess && mapped) e = hipHostGetDevicePointer(&dp, p, 0);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
-    hipError_t ensure_guarded(size_t bytes);
-    template <typename T>
-    T* host() const { return static_cast<T*>(p); }
-    template <typename T>
-    T* dev() const { return static_cast<T*>(dp); }
-};
 
 // One guard of a buffer against the pattern: `img` is the guard's G bytes as the host reads them.
 void guard_scan(GuardCfg* g, const std::string& name, int side, const uint8_t* img, size_t size,
@@ -276,195 +183,8 @@ hipError_t PinBuf::ensure_guarded(size_t bytes) {
     return hipSuccess;
 }
 
-// The buffers one fill writes, and its two timing events (created and destroyed by their owner): the context has
-// one set, every pipeline slot one of its own, so that fills can run side by side.
-struct FillBufs {
-    DevBuf tb;                 // traceback words
-    DevBuf hand;               // workgroup hand-off edges
-    DevBuf flags;              // [0] ticket, [1] abort
-    DevBuf out_last;           // H'(m, n)
-    DevBuf GVp, GHp, top, left, bnd_row, bnd_col, meta, bscr;  // the boundary pass's output (make_dp_array) and scratch
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    // the boundary arrays of an m x n_all problem, and the fill's four result words
-    hipError_t ensure_boundary(int64_t m, int64_t n_all) {
-        const std::pair<DevBuf*, size_t> want[] = {
-            {&bnd_row, sizeof(int) * 3 * (n_all + 1)}, {&bnd_col, sizeof(int) * 3 * (m + 1)},
-            {&GVp, sizeof(int) * (m + 1)},             {&bscr, sizeof(int) * ga::boundary_scratch_ints((int)m, (int)n_all)},
-            {&GHp, sizeof(int) * (n_all + 1)},         {&top, sizeof(int2) * (n_all + 1)},
-            {&left, sizeof(int2) * (m + 1)},           {&meta, sizeof(int) * 8},
-            {&out_last, sizeof(int) * 4}};
-        for (const auto& [buf, bytes] : want)
-            if (hipError_t e = buf->ensure(bytes); e != hipSuccess) return e;
-        return hipSuccess;
-    }
-};
-
-using namespace garng;
 static_assert(gaplan::kFillRows == ga::FROWS, "the planner's chunk rows (ga_plan.h)");
 static_assert(ga::COLCK_PAD == 64, "rc_rows_fit (ga_check.h) assumes a 64-row pad");
-
-}  // namespace
-
-// ------------------------------------------------------------------ context
-// The GA_* variables the shipped library reads from the environment (INTEGRATION.md lists them): the path choices
-// and budgets an operator may want to set.  Every other option -- kernel variants for tests and tuning, fault
-// injection, diagnostics -- reaches a context only through ga_ctx_create_opts, never from the environment, so a
-// stray variable cannot change a production context's kernels or inject a fault (ADVICE r5).  An experiments build
-// (make EXPERIMENTS=1) takes every GA_* variable.
-const char* const kEnvKnobs[] = {"GA_RC",           "GA_RC_MIN_CELLS", "GA_RC_BUDGET_MB",      "GA_RC_EVERY",
-                                 "GA_RC_SERVERS",   "GA_TB_BUDGET_MB", "GA_FILL_MODE",         "GA_COLS_PER_LANE",
-                                 "GA_LANE_COLS_PER_LANE", "GA_PIPE_FILLS", "GA_PIPE_CHAIN",    "GA_STREAM_PRIORITY",
-                                 "GA_HALO_SPIN_LIMIT", "GA_PIPE_TRACE"};
-bool env_knob(const std::string& name) {
-#ifdef GA_EXPERIMENTS
-    return name.compare(0, 3, "GA_") == 0;
-#else
-    for (const char* k : kEnvKnobs)
-        if (name == k) return true;
-    return false;
-#endif
-}
-
-struct ga_ctx {
-    // GA_* tuning / diagnostic overrides, snapshotted when the context is created (ga_ctx_create_opts): the
-    // environment's shipped knobs (kEnvKnobs) at that moment, then the caller's options.  A context's kernel choices
-    // never change under it, whatever the process does to its environment later (nullptr: unset).
-    std::map<std::string, std::string> knobs;
-    const char* knob(const char* name) const {
-        const auto it = knobs.find(name);
-        return it == knobs.end() ? nullptr : it->second.c_str();
-    }
-    // knobs of paths that were measured and dropped: read only by an experiments build
-    // (make EXPERIMENTS=1); the shipped library ignores them
-    const char* xknob(const char* name) const {
-#ifdef GA_EXPERIMENTS
-        return knob(name);
-#else
-        (void)name;
-        return nullptr;
-#endif
-    }
-    int device = 0;
-    int priority = 0;  // of `stream` (the greatest the device offers, see ga_ctx_create)
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_dep = nullptr;  // ga_ctx_wait_stream
-    hipEvent_t wev[2] = {nullptr, nullptr};  // the walk's timing events (the fill's: fb.ev)
-    // problem
-    bool loaded = false, custom = false, filled_tb = false;
-    int64_t m = 0, n = 0;      // local problem (slab: n = local columns)
-    int64_t n_global = 0, col0 = 0;
-    int K = 0, o = 0, big = 0, CB = 1, qbytes = 1;
-    int64_t gh_total = 0;      // GH(n_global): the sum of the horizontal gap costs of seq_2
-    int64_t gh_max = 0;        // max over j = 1 .. n_global of GH(j): with gap costs of mixed sign GH is not monotone
-    int64_t gv_total = 0;      // GV(m): the sum of the vertical gap costs of seq_1
-    // a streamed single call's small results in pinned, coherent host memory (no copy after the walk): [0, 16) the
-    // walk's result words (it writes them there), [16, 20) the fill's H'(m, n) words, [20] its abort word (copied on
-    // the upload stream while the walk runs)
-    PinBuf res_pin{true};
-    hipEvent_t ev_fill = nullptr, ev_res = nullptr;
-    bool rc_pos_zeroed = false;  // rc_pos was cleared on the fill's stream before the fill (rc_align)
-    int qrows = 1024, num_cu = 256;  // the row scan's query-profile ring (load_problem)
-    gaplan::Knobs pk;          // the planner's knobs, parsed once (plan_knobs)
-    // the last enqueued fill's plan (ga_plan.h): kernel, geometry, checkpoint spacing; before the first fill the
-    // loaded problem's row-scan geometry
-    gaplan::FillPlan plan;
-    int64_t GV_m = 0, GH_n = 0;
-    std::vector<uint8_t> h_a, h_b;
-    // device buffers
-    DevBuf a, b, sub, gh, gv, qp, full, rng, ckpt, ops, result;
-    FillBufs fb;  // what a fill writes
-    DevBuf halo_in{true};  // uncached
-    bool slab = false;
-    // slab progress words in pinned, coherent host memory: [0] halo_in rows (written by the host
-    // when a band has arrived), [1] halo_out rows (written by the fill's IO wave)
-    PinBuf prog{true};
-    int2* halo_in_ext = nullptr;   // caller-bound halo buffers (e.g. tensors RCCL sends from / receives into)
-    int2* halo_out_ext = nullptr;
-    // caller-bound progress words (device-visible; e.g. on the reading GPU, written over xGMI by the
-    // writing GPU's fill): nullptr keeps prog_dev[0] / prog_dev[1]
-    uint32_t* in_prog_ext = nullptr;
-    uint32_t* out_prog_ext = nullptr;
-    RngTable walk_rng;             // tie-break table of the global problem (slab walks)
-    // pipelined repeated alignments (ga_problem_align_many): two slots of traceback words, walk
-    // buffers and events; the walk runs on its own stream beside the next fill
-    struct PipeSlot {
-        FillBufs fb;  // each pipelined alignment computes its own boundary (make_dp_array) into its slot
-        DevBuf rng, ops, result;
-        hipEvent_t fdone = nullptr, w0 = nullptr, w1 = nullptr;
-        PinBuf tab_pin;  // pinned staging of the walk's table slice
-    } pipe[6];
-    hipStream_t wstream = nullptr, fstream[4] = {nullptr, nullptr, nullptr, nullptr};  // [0] unused: ctx->stream
-    // CU-masked pipeline streams (GA_PIPE_WALK_CUS > 0): the walk keeps CUs of its own, the fills the rest
-    hipStream_t mwstream = nullptr, mfstream[4] = {nullptr, nullptr, nullptr, nullptr};
-    // default-priority pipeline fill streams (GA_PIPE_FILL_PRIO=normal): four fills on their own pool of
-    // hardware queues, the walk stream keeping the greatest priority (it takes the next free CU)
-    hipStream_t nfstream[4] = {nullptr, nullptr, nullptr, nullptr};
-    int walk_cus = -1;  // CUs reserved for the walk (0: no masks; -1: not yet set up)
-    PinBuf pipe_pin;               // pinned: per slot {out_last[4], GV(m), GH(n), abort, pad}
-    int pipe_fills = 2, pipe_slots = 3;  // fills in flight (one stream each) and slots (fills + the walked one)
-    int hw_queues = 4;                   // GPU_MAX_HW_QUEUES as the process first saw it (ga_ctx_create)
-    int pipe_lane_td = 0, pipe_lane_nwc = 0;  // the pipeline's lane-kernel fill geometry (0: the row scan)
-    RngTable many_rng;
-    // chained pipeline walks (walk_chain_kernel): the tie-break stream in pinned, coherent host memory
-    // and the control words {fills done, walks done, abort, timed out, entries written (8 B at [4])}
-    PinBuf chain_tab{true}, chain_ctl{true};
-    // the chain's stream, at the LEAST priority: HIP gives each priority its own pool of hardware
-    // queues, and no other stream of the process uses this pool, so no fill can ever be queued behind
-    // the persistent chain on an in-order queue it shares (the chain waits for those fills)
-    hipStream_t cwstream = nullptr;
-    // per slot, pinned and coherent: the walk's result words and levels, written by the chain straight
-    // into host memory (a hipMemcpy would wait for a CU, and the fills hold them all)
-    PinBuf chain_io{true};
-    bool walk_rng_ready = false;
-    float fill_ms = 0.f, walk_ms = 0.f, rng_ms = 0.f, call_ms = 0.f;
-    bool dbg_on = false;
-    int walk_waits = 0, walk_tiles = 0, walk_t_tile = 0, walk_t_ring = 0, walk_t_total = 0, walk_c_total = 0, walk_load_ticks = 0, walk_load_count = 0;
-    DevBuf dbg, wdbg;
-    // the recompute walk: the score fill's checkpoints, the tile cache, the blocks' flags
-    DevBuf colck, stck, rc_tb, rc_flags, rc_pos, rc_own;
-    DevBuf qprof;  // the lane fill's query profile (ga::launch_lane_qprof), rebuilt by every lane fill
-    // ga_batch_costs: buffers of its own, so a loaded problem's stay as they are -- every sequence's
-    // codes, the work list, sub' / gap tables, the ticket word, the costs, the waves' HBM edge columns
-    DevBuf bt_codes, bt_items, bt_sub, bt_gh, bt_gv, bt_ticket, bt_out, bt_scratch;
-    // ga_batch_align adds the walk items, the pairs' tie-break tables, their packed levels and walk
-    // results, and the waves' traceback words; ga_batch_align_timings's figures of its last call
-    DevBuf bt_witems, bt_rng, bt_ops, bt_walk, bt_tb;
-    float batch_align_ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // [4], [5]: walk ns per dispatch, fill ns per cell
-    // the device route of the pairs' tables (batch_rng_kernel): its work items, status words and the seeding's base
-    // array (uploaded once), its own timing events, and ga_batch_align_info's figures of the last call
-    DevBuf bt_ritems, bt_rstatus, bt_rbase;
-    bool rbase_ready = false;
-    hipEvent_t rev[2] = {nullptr, nullptr};  // (created with the first generator launch)
-    int32_t batch_rng_info[4] = {0, 0, 0, 0};  // device-routed items, host-routed items, fell back, generator blocks
-    // ga_batch_sample adds the pairs' slices (ga_batch_words_item), the chunk's traceback words, a
-    // walk launch's items and the walks' own ticket word; ga_batch_sample_info's and _timings's figures of its last call
-    DevBuf bs_words, bs_tb, bs_witems, bs_ticket;
-    int64_t batch_sample_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    float batch_sample_ms[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int walk_jump_diag[3] = {0, 0, 0};  // the tie-to-tie walk's trips, region re-checks, ties (result[12..14])
-    DevBuf jlut;           // the jump workers' LUT for gap open jlut_o (ga::jump_lut_build)
-    int jlut_o = -1;
-    // ga_slab_link: this slab's left edge + its progress word, uncached device memory on this GPU that
-    // the left neighbour's fill writes (over xGMI when it runs on another GPU)
-    DevBuf link;
-    // ga_slab_link_import: the right neighbour's link buffer, mapped from another process
-    void* peer_link = nullptr;
-    char peer_handle[64] = {};
-    unsigned rc_epoch = 0;
-    bool rc_used = false;  // the last fill was the recompute path's (ga_problem_align or a slab's)
-    // rc_align's walk levels in pinned host memory and the helper's progress word: decoded while the walk runs
-    PinBuf rc_ops_pin{true}, rc_ops_prog{true};
-    // rc_align's tie-break table: pinned staging, uploaded on a stream of its own while the fill runs, so that the walk
-    // is queued behind the fill at once (a pageable copy on the fill's stream held the calling thread to the fill's end)
-    PinBuf up_pin;
-    hipStream_t ustream = nullptr;
-    hipEvent_t ev_up = nullptr;
-    gaplan::FillPlan rc_plan;  // the plan of the fill the recompute walk reads (rc_fill): stripes, spacing
-    bool rc_jump = false;  // the last recompute walk was the tie-to-tie walk (jump entries)
-    GuardCfg guard;        // guard mode (G = 0: off; guard_attach names and registers every buffer above)
-};
-
-namespace {
 
 int check_ctx(ga_ctx* c) {
     if (!c) return fail(GA_E_ARG, "null context");
@@ -669,21 +389,6 @@ int64_t dev_avail_bytes(ga_ctx* c, int64_t held) {
     if (const char* e = c->knob("GA_DEV_AVAIL_MB")) avail = std::min<int64_t>(avail, atoll(e) << 20);
     return std::max<int64_t>(avail, 0);
 }
-
-// A band of rows of the whole problem (banded traceback): rows r0+1 .. r0+mb, its
-// top row from a checkpoint (nullptr: row 0), no boundary pass; or the checkpointing pass itself; or the recompute
-// walk's score fill; or a pipeline slot's fill (align_many): the planner's request (ga_plan.h; tb, full and
-// has_ckpt are enqueue_fill's to set) and where the fill reads and writes.
-struct Band : gaplan::Request {
-    int64_t r0 = 0;
-    const int2* top = nullptr;  // (H', h2') of row r0, [n+1] (column 0 = the left edge's corner)
-    int2* ckpt = nullptr;       // checkpointing pass: where rows ckpt_rows, 2*ckpt_rows, ... go
-    int ckpt_rows = 0;
-    // pipelined alignments (align_many): a fill with buffers and a stream of its own, so that several fills can
-    // run at once (nullptr: the context's)
-    FillBufs* bufs = nullptr;
-    hipStream_t stream = nullptr;
-};
 
 #ifdef GA_EXPERIMENTS
 constexpr bool kRcJumpDefault = false;  // the tie-to-tie walk unless GA_RC_JUMP says otherwise
@@ -895,7 +600,7 @@ int fill_launch(ga_ctx* c, const FillJob& j, const ga::FillArgs& p) {
 
 // Enqueue boundary + query profile + fill.  Does not synchronise.  The plan it used becomes the context's
 // (ga_ctx::plan) and goes to plan_out.
-int enqueue_fill(ga_ctx* c, int32_t flags, const Band& bd = Band(), gaplan::FillPlan* plan_out = nullptr) {
+int enqueue_fill(ga_ctx* c, int32_t flags, const Band& bd, gaplan::FillPlan* plan_out) {
     if (!c->loaded) return fail(GA_E_STATE, "no problem loaded");
     const bool tb = (flags & (GA_FILL_TRACEBACK | GA_FILL_FULL)) != 0;
     const bool full = (flags & GA_FILL_FULL) != 0;
@@ -2180,119 +1885,7 @@ int align_many(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, cons
     return GA_OK;
 }
 
-// ---------------------------------------------------------------- batches
-// resident waves of a batch launch: two per SIMD on every CU
-int64_t batch_max_waves(const ga_ctx* c) { return (int64_t)c->num_cu * 4 * 2; }
-
-// What ga_batch_costs_ex and ga_batch_align stage alike for the planner's work list, on the context's stream: the
-// launch's waves, and the codes, work list, sub' / gap tables, zeroed ticket, cost and edge-scratch buffers behind
-// `args`.  subp is the upload's source: it lives until the caller has synchronised the stream.
-struct BatchStage {
-    std::vector<int> subp;
-    ga::BatchArgs args{};
-    int waves = 0;
-};
-int stage_batch(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, int64_t npairs, const ga_costs* cs,
-                const std::vector<ga_batch_item>& items, int64_t scratch_rows, BatchStage& bs) {
-    const int K = cs->K, nitems = (int)items.size();
-    // never more waves than pairs; whole workgroups
-    const int W = gabatch::kWavesPerGroup;
-    const int waves = bs.waves = (int)((std::min<int64_t>(batch_max_waves(c), nitems) + W - 1) / W * W);
-    bs.subp = shifted_sub(cs);
-    const size_t ncodes = (size_t)seq_off[nseq];
-    HIPCHK(c->bt_codes.ensure(ncodes));
-    HIPCHK(c->bt_items.ensure(sizeof(ga_batch_item) * nitems));
-    HIPCHK(c->bt_sub.ensure(sizeof(int) * K * K));
-    HIPCHK(c->bt_gh.ensure(sizeof(int) * K));
-    HIPCHK(c->bt_gv.ensure(sizeof(int) * K));
-    HIPCHK(c->bt_ticket.ensure(sizeof(unsigned)));
-    HIPCHK(c->bt_out.ensure(sizeof(long long) * npairs));
-    if (scratch_rows > 0) HIPCHK(c->bt_scratch.ensure(sizeof(int2) * 2 * scratch_rows * waves));
-    HIPCHK(hipMemcpyAsync(c->bt_codes.p, codes, ncodes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->bt_items.p, items.data(), sizeof(ga_batch_item) * nitems, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->bt_sub.p, bs.subp.data(), sizeof(int) * K * K, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->bt_gh.p, cs->gap_h, sizeof(int) * K, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->bt_gv.p, cs->gap_v, sizeof(int) * K, hipMemcpyHostToDevice, c->stream));
-    // the ticket starts at zero for every launch (no last-arriver reset to rely on)
-    HIPCHK(hipMemsetAsync(c->bt_ticket.p, 0, sizeof(unsigned), c->stream));
-    bs.args = ga::BatchArgs{c->bt_codes.as<uint8_t>(), c->bt_items.as<ga_batch_item>(), nitems, c->bt_sub.as<int>(),
-                            c->bt_gh.as<int>(), c->bt_gv.as<int>(), K, cs->gap_open, c->bt_ticket.as<unsigned>(),
-                            c->bt_out.as<long long>(), scratch_rows > 0 ? c->bt_scratch.as<int2>() : nullptr,
-                            scratch_rows};
-    return GA_OK;
-}
-
-// Pair k of a batch through the single-pair path: loaded into the context's problem slot under the pair's own
-// max_cost (its sentinel), then run(sa, sb) on its two sequences' indices.  No problem is loaded afterwards.
-template <typename Run>
-int batch_single_pair(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, const int32_t* pair_a,
-                      const int32_t* pair_b, const int32_t* pair_max_cost, const ga_costs* cs, int64_t k, Run run) {
-    const int64_t sa = pair_a[k], sb = pair_b[k];
-    const int64_t m = seq_off[sa + 1] - seq_off[sa], n = seq_off[sb + 1] - seq_off[sb];
-    ga_costs own = *cs;
-    if (pair_max_cost) own.max_cost = pair_max_cost[k];
-    int r = load_problem(c, codes + seq_off[sa], m, codes + seq_off[sb], n, &own, nullptr, nullptr, 0, n);
-    if (!r) r = run(sa, sb);
-    c->loaded = false;
-    if (r) return fail(r, "pair " + std::to_string(k) + ": " + g_err);
-    return GA_OK;
-}
-
-// How a call's tie-break tables are made: on the device for the items the route rule admits
-// (gabrng::route_device) when the call's flags or the context (GA_BATCH_RNG=device) ask for it, with the item limit
-// GA_BATCH_RNG_DEVICE_MAX_STEPS and the cap's words per dispatch GA_BATCH_RNG_WORD_CAP (both checked at creation).
-struct RngRoute {
-    bool want_device = false;
-    int64_t max_steps = gabrng::kDeviceMaxSteps;
-    int cap_words = gabrng::kCapWordsPerDispatch;
-};
-RngRoute rng_route(const ga_ctx* c, uint32_t flags) {
-    RngRoute r;
-    const uint32_t which = flags & GA_BATCH_TABLES_MASK;
-    const char* dflt = c->knob("GA_BATCH_RNG");
-    r.want_device = which == GA_BATCH_TABLES_DEVICE || (which == GA_BATCH_TABLES_DEFAULT && dflt && !strcmp(dflt, "device"));
-    if (const char* e = c->knob("GA_BATCH_RNG_DEVICE_MAX_STEPS")) r.max_steps = atoll(e);
-    if (const char* e = c->knob("GA_BATCH_RNG_WORD_CAP")) r.cap_words = atoi(e);
-    return r;
-}
-
-// batch_rng_kernel for `items` on the context's stream, between the events c->rev[0] and c->rev[1]: item t's entries
-// go to tab_dev[items[t].tab_off ..), its status word to c->bt_rstatus[t].  `items` is an upload's source: it lives
-// until the caller has synchronised the stream.  groups_out: the workgroups launched.
-int enqueue_batch_rng(ga_ctx* c, const std::vector<gabrng::Item>& items, uint32_t* tab_dev, int cap_words,
-                      int* groups_out) {
-    if (!c->rbase_ready) {
-        // init_genrand(19650218)'s array, the same for every seed: once per context
-        uint32_t base[gabrng::kN];
-        gabrng::base_array(base);
-        HIPCHK(c->bt_rbase.ensure(sizeof(base)));
-        HIPCHK(hipMemcpy(c->bt_rbase.p, base, sizeof(base), hipMemcpyHostToDevice));
-        c->rbase_ready = true;
-    }
-    for (hipEvent_t& e : c->rev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    HIPCHK(c->bt_ritems.ensure(sizeof(gabrng::Item) * items.size()));
-    HIPCHK(c->bt_rstatus.ensure(sizeof(int32_t) * items.size()));
-    HIPCHK(hipMemcpyAsync(c->bt_ritems.p, items.data(), sizeof(gabrng::Item) * items.size(), hipMemcpyHostToDevice,
-                          c->stream));
-    HIPCHK(hipEventRecord(c->rev[0], c->stream));
-    const ga::RngArgs a{c->bt_ritems.as<gabrng::Item>(), (long long)items.size(), c->bt_rbase.as<uint32_t>(), tab_dev,
-                        c->bt_rstatus.as<int32_t>(), cap_words};
-    *groups_out = ga::launch_batch_rng(c->stream, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->rev[1], c->stream));
-    return GA_OK;
-}
-
-// tab[first, last) of a host-built table to its place in the device's, on the context's stream
-int upload_table_range(ga_ctx* c, const uint32_t* tab, uint32_t* tab_dev, int64_t first, int64_t last) {
-    if (last > first)
-        HIPCHK(hipMemcpyAsync(tab_dev + first, tab + first, sizeof(uint32_t) * (size_t)(last - first),
-                              hipMemcpyHostToDevice, c->stream));
-    return GA_OK;
-}
-
-}  // namespace
+}  // namespace gahost
 
 // ====================================================================== C ABI
 extern "C" {
@@ -2504,633 +2097,6 @@ static int problem_fill_impl(ga_ctx* c, int32_t flags, int64_t* cost_out, int32_
     if ((flags & GA_FILL_FULL) && !full_out) return fail(GA_E_ARG, "GA_FILL_FULL needs full_out");
     if (int r = enqueue_fill(c, flags)) return r;
     return finish_fill(c, cost_out, (flags & GA_FILL_FULL) ? full_out : nullptr);
-}
-
-int ga_batch_costs(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
-                   const int32_t* pair_b, int64_t npairs, const ga_costs* cs, int64_t* cost_out) {
-    return ga_batch_costs_ex(c, codes, seq_off, nseq, pair_a, pair_b, nullptr, npairs, cs, cost_out);
-}
-
-static int batch_costs_ex_impl(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq,
-                               const int32_t* pair_a, const int32_t* pair_b, const int32_t* pair_max_cost,
-                               int64_t npairs, const ga_costs* cs, int64_t* cost_out) {
-    if (int r = check_ctx(c)) return r;
-    if (npairs == 0) return GA_OK;  // an empty batch: no launch
-    if (!cost_out) return fail(GA_E_ARG, "null argument");
-    // the planner's routing limits
-    gabatch::Limits lim;
-    if (const char* e = c->knob("GA_BATCH_MAX_CELLS")) lim.max_cells = std::max<int64_t>(0, atoll(e));
-    lim.scratch_rows_cap = gabatch::scratch_rows_cap(batch_max_waves(c));
-    gabatch::Plan plan;
-    std::string why;
-    if (int r = gabatch::plan_batch(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim, plan, why))
-        return fail(r, why);
-    if (!plan.kernel.empty()) {
-        BatchStage bs;
-        if (int r = stage_batch(c, codes, seq_off, nseq, npairs, cs, plan.kernel, plan.scratch_rows, bs)) return r;
-        HIPCHK(hipEventRecord(c->fb.ev[0], c->stream));
-        ga::launch_batch_fill(c->stream, bs.args, plan.qbytes, bs.waves);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(c->fb.ev[1], c->stream));
-        std::vector<long long> got((size_t)npairs);
-        HIPCHK(hipMemcpyAsync(got.data(), c->bt_out.p, sizeof(long long) * npairs, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipEventElapsedTime(&c->fill_ms, c->fb.ev[0], c->fb.ev[1]));
-        for (const ga_batch_item& it : plan.kernel) {
-            if (got[(size_t)it.out] == INT64_MIN)
-                return fail(GA_E_STATE, "pair " + std::to_string(it.out) + ": work item does not fit the batch launch");
-            cost_out[it.out] = got[(size_t)it.out];
-        }
-    }
-    if (!plan.single.empty()) {
-        // the existing score fill, one pair at a time (as ga_problem_set + ga_problem_fill): it goes through the
-        // context's problem slot, so no problem is loaded afterwards.  A slab context keeps its slab: refused.
-        if (c->slab)
-            return fail(GA_E_STATE, "pair " + std::to_string(plan.single[0]) +
-                                        ": needs the single-pair fill, which a slab context cannot run");
-        c->rc_used = false;
-        for (const int64_t k : plan.single) {
-            auto fill = [&](int64_t, int64_t) {
-                const int e = enqueue_fill(c, 0);
-                return e ? e : finish_fill(c, &cost_out[k], nullptr);
-            };
-            if (int r = batch_single_pair(c, codes, seq_off, pair_a, pair_b, pair_max_cost, cs, k, fill)) return r;
-        }
-    }
-    return GA_OK;
-}
-
-int ga_batch_align(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
-                   const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
-                   const uint64_t* seeds, const char* chars, char* out_a, char* out_mid, char* out_b,
-                   const int64_t* out_off, int64_t* out_len, int32_t* tb_status, int64_t* cost_out) {
-    return ga_batch_align_ex(c, codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, seeds, chars, out_a,
-                             out_mid, out_b, out_off, out_len, tb_status, cost_out, GA_BATCH_TABLES_DEFAULT);
-}
-
-static int batch_align_ex_impl(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq,
-                               const int32_t* pair_a, const int32_t* pair_b, const int32_t* pair_max_cost,
-                               int64_t npairs, const ga_costs* cs, const uint64_t* seeds, const char* chars,
-                               char* out_a, char* out_mid, char* out_b, const int64_t* out_off, int64_t* out_len,
-                               int32_t* tb_status, int64_t* cost_out, uint32_t flags) {
-    if (int r = check_ctx(c)) return r;
-    if ((flags & ~GA_BATCH_TABLES_MASK) || (flags & GA_BATCH_TABLES_MASK) > GA_BATCH_TABLES_DEVICE)
-        return fail(GA_E_ARG, "bad flags: bits 0-1 choose the tables (0 default, 1 host, 2 device)");
-    for (int32_t& x : c->batch_rng_info) x = 0;
-    if (npairs == 0) return GA_OK;  // an empty batch: no launch
-    if (!seeds || !chars || !out_a || !out_mid || !out_b || !out_off || !out_len || !tb_status || !cost_out)
-        return fail(GA_E_ARG, "null argument");
-    const double t_call = now_ms();
-    for (float& x : c->batch_align_ms) x = 0.f;
-    const int64_t max_waves = batch_max_waves(c);
-    gabatch::AlignLimits lim;
-    if (const char* e = c->knob("GA_BATCH_ALIGN_MAX_CELLS")) lim.max_cells = std::max<int64_t>(0, atoll(e));
-    lim.scratch_rows_cap = gabatch::scratch_rows_cap(max_waves);
-    lim.tb_words_cap = gabatch::tb_slice_words_cap(max_waves);
-    gabatch::AlignPlan plan;
-    std::string why;
-    if (int r = gabatch::plan_batch_align(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim, plan,
-                                          why))
-        return fail(r, why);
-    auto len_of = [&](int64_t s) { return seq_off[s + 1] - seq_off[s]; };
-    for (int64_t k = 0; k < npairs; k++)
-        if (out_off[k] < 0 || out_off[k + 1] - out_off[k] < len_of(pair_a[k]) + len_of(pair_b[k]))
-            return fail(GA_E_ARG, "pair " + std::to_string(k) + ": output capacity too small");
-    if (!plan.single.empty() && c->slab)
-        return fail(GA_E_STATE, "pair " + std::to_string(plan.single[0]) +
-                                    ": needs the single-pair path, which a slab context cannot run");
-    // The kernel pairs with their tables by `route`; fell_back: the generator reached an item's word cap, nothing of
-    // the launch was decoded and the caller runs the pairs again with host tables.
-    auto kernel_pairs = [&](const RngRoute& route, bool& fell_back) -> int {
-        const int nitems = (int)plan.kernel.size();
-        BatchStage bs;
-        if (int r = stage_batch(c, codes, seq_off, nseq, npairs, cs, plan.kernel, plan.scratch_rows, bs)) return r;
-        // its own: the walk items, the pairs' tables, their level words and walk results, the waves' traceback words
-        HIPCHK(c->bt_witems.ensure(sizeof(ga_batch_walk_item) * nitems));
-        HIPCHK(c->bt_walk.ensure(sizeof(int4) * 2 * npairs));
-        HIPCHK(c->bt_rng.ensure(sizeof(uint32_t) * plan.tab_entries));
-        HIPCHK(c->bt_ops.ensure(sizeof(uint32_t) * plan.ops_words));
-        if (c->bt_tb.ensure(sizeof(uint32_t) * (size_t)plan.tb_words * bs.waves) != hipSuccess) {
-            (void)hipStreamSynchronize(c->stream);  // the staged uploads read this call's buffers
-            return fail(GA_E_NOMEM, "no device memory for the batch's traceback words");
-        }
-        HIPCHK(hipMemcpyAsync(c->bt_witems.p, plan.walk.data(), sizeof(ga_batch_walk_item) * nitems,
-                              hipMemcpyHostToDevice, c->stream));
-        // Every pair's tie-break table from its own seed.  The device-routed items' (gabrng::route_device) are made
-        // by batch_rng_kernel ahead of the walks, on the same stream; the others' on a few host threads meanwhile,
-        // their ranges of the table uploaded behind the generator.
-        std::vector<gabrng::Item> dev;
-        std::vector<ga_batch_item> host_items;
-        std::vector<ga_batch_walk_item> host_walk;
-        for (int t = 0; t < nitems; t++) {
-            const ga_batch_item& it = plan.kernel[(size_t)t];
-            const int64_t steps = (int64_t)it.m + it.n;
-            if (gabrng::route_device(route.want_device, steps, route.max_steps)) {
-                dev.push_back(gabrng::Item{seeds[it.out], plan.walk[(size_t)t].tab_off, (int32_t)steps, 0});
-            } else {
-                host_items.push_back(it);
-                host_walk.push_back(plan.walk[(size_t)t]);
-            }
-        }
-        int groups = 0;
-        if (!dev.empty())
-            if (int r = enqueue_batch_rng(c, dev, c->bt_rng.as<uint32_t>(), route.cap_words, &groups)) return r;
-        const double t_tab = now_ms();
-        std::vector<uint32_t> tab(host_items.empty() ? 0 : (size_t)plan.tab_entries);
-        const char* nt = c->knob("GA_BATCH_RNG_THREADS");
-        const int nthreads = gabatch::rng_threads(nt ? atoi(nt) : 0, nitems);
-        if (!host_items.empty()) {
-            const int64_t nhost = (int64_t)host_items.size();
-            gabatch::build_pair_tables(host_items.data(), host_walk.data(), nhost, seeds,
-                                       gabatch::rng_threads(nt ? atoi(nt) : 0, nhost), tab.data());
-            // (the work list's table ranges follow each other: neighbouring host items go up in one copy)
-            int64_t first = host_walk[0].tab_off, last = first;
-            for (int64_t t = 0; t < nhost; t++) {
-                const int64_t off = host_walk[(size_t)t].tab_off;
-                if (off != last) {
-                    if (int r = upload_table_range(c, tab.data(), c->bt_rng.as<uint32_t>(), first, last)) return r;
-                    first = off;
-                }
-                last = off + host_items[(size_t)t].m + host_items[(size_t)t].n;
-            }
-            if (int r = upload_table_range(c, tab.data(), c->bt_rng.as<uint32_t>(), first, last)) return r;
-        }
-        const float host_tab_ms = (float)(now_ms() - t_tab);
-        c->batch_align_ms[1] = host_tab_ms;
-        c->batch_rng_info[0] = (int32_t)dev.size();
-        c->batch_rng_info[1] = (int32_t)host_items.size();
-        c->batch_rng_info[3] = groups;
-        HIPCHK(hipEventRecord(c->fb.ev[0], c->stream));
-        const ga::AlignArgs q{bs.args, c->bt_witems.as<ga_batch_walk_item>(), c->bt_rng.as<uint32_t>(),
-                              c->bt_ops.as<uint32_t>(), c->bt_walk.as<int4>(), c->bt_tb.as<uint32_t>(), plan.tb_words};
-        ga::launch_batch_align(c->stream, q, plan.qbytes, plan.CB, bs.waves);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(c->fb.ev[1], c->stream));
-        std::vector<long long> got((size_t)npairs);
-        std::vector<int4> walked((size_t)npairs * 2);
-        std::vector<uint32_t> ops((size_t)plan.ops_words);
-        HIPCHK(hipMemcpyAsync(got.data(), c->bt_out.p, sizeof(long long) * npairs, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(walked.data(), c->bt_walk.p, sizeof(int4) * 2 * npairs, hipMemcpyDeviceToHost,
-                              c->stream));
-        HIPCHK(hipMemcpyAsync(ops.data(), c->bt_ops.p, sizeof(uint32_t) * ops.size(), hipMemcpyDeviceToHost, c->stream));
-        // the generator's status words come back with the walks' results, in the same synchronisation
-        std::vector<int32_t> rstatus(dev.size());
-        if (!dev.empty())
-            HIPCHK(hipMemcpyAsync(rstatus.data(), c->bt_rstatus.p, sizeof(int32_t) * dev.size(), hipMemcpyDeviceToHost,
-                                  c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipEventElapsedTime(&c->fill_ms, c->fb.ev[0], c->fb.ev[1]));
-        c->batch_align_ms[0] = c->fill_ms;
-        if (!dev.empty()) {
-            // "tables": the generator's time and whatever of the host's share it did not hide
-            float gen_ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&gen_ms, c->rev[0], c->rev[1]));
-            c->batch_align_ms[1] = gen_ms + std::max(0.f, host_tab_ms - gen_ms);
-            for (const int32_t st : rstatus)
-                if (st != gabrng::kComplete) {
-                    // an item stopped at its word cap: the walks read unwritten entries (harmlessly: a walk makes at
-                    // most m + n - 1 steps whatever the table holds), so nothing of this launch is decoded
-                    fell_back = true;
-                    return GA_OK;
-                }
-        }
-        // the strings, on the table build's threads (every pair writes its own outputs); out_len < 0: see below
-        const double t_dec = now_ms();
-        gabatch::run_shares(nitems, nthreads, [&](int64_t first, int64_t stride) {
-            for (int64_t t = first; t < nitems; t += stride) {
-                const ga_batch_item& it = plan.kernel[(size_t)t];
-                const size_t k = (size_t)it.out;
-                const int4 wr = walked[2 * k];
-                tb_status[k] = GA_TB_OK;
-                cost_out[k] = got[k];
-                out_len[k] =
-                    got[k] == INT64_MIN ? -3
-                    : wr.x < 0 || wr.x > (int64_t)it.m + it.n
-                        ? -2
-                        : gabatch::decode_levels(ops.data() + plan.walk[(size_t)t].ops_off, wr.x, it.m, it.n, wr.y,
-                                                 wr.z, wr.w, chars + it.a_off, chars + it.b_off, out_a + out_off[k],
-                                                 out_mid + out_off[k], out_b + out_off[k],
-                                                 out_off[k + 1] - out_off[k]);
-            }
-        });
-        c->batch_align_ms[2] = (float)(now_ms() - t_dec);
-        double fill_ticks = 0, walk_ticks = 0, steps = 0, cells = 0;
-        for (const ga_batch_item& it : plan.kernel) {
-            const size_t k = (size_t)it.out;
-            if (out_len[k] == -3)
-                return fail(GA_E_STATE, "pair " + std::to_string(k) + ": work item does not fit the batch launch");
-            if (out_len[k] < 0)
-                return fail(GA_E_STATE, "pair " + std::to_string(k) + ": the walk's levels do not decode");
-            fill_ticks += walked[2 * k + 1].x;
-            walk_ticks += walked[2 * k + 1].y;
-            steps += walked[2 * k].x;
-            cells += (double)it.m * it.n;
-        }
-        c->batch_align_ms[4] = (float)(10.0 * walk_ticks / std::max(steps, 1.0));  // (a tick is 10 ns)
-        c->batch_align_ms[5] = (float)(10.0 * fill_ticks / std::max(cells, 1.0));
-        return GA_OK;
-    };
-    if (!plan.kernel.empty()) {
-        bool fell_back = false;
-        if (int r = kernel_pairs(rng_route(c, flags), fell_back)) return r;
-        if (fell_back) {
-            // through the host route; the figures of the device attempt stay in ga_batch_align_info
-            const float tables_ms = c->batch_align_ms[1];
-            const int32_t first_try[4] = {c->batch_rng_info[0], c->batch_rng_info[1], 1, c->batch_rng_info[3]};
-            if (int r = kernel_pairs(rng_route(c, GA_BATCH_TABLES_HOST), fell_back)) return r;
-            c->batch_align_ms[1] += tables_ms;
-            for (int q = 0; q < 4; q++) c->batch_rng_info[q] = first_try[q];
-        }
-    }
-    if (!plan.single.empty()) {
-        // the single-pair path, one pair at a time, from that pair's seeded state (the state it leaves is dropped).
-        // It goes through the context's problem slot, so no problem is loaded afterwards.
-        c->rc_used = false;
-        uint32_t state[MTN + 1];
-        for (const int64_t k : plan.single) {
-            auto align = [&](int64_t sa, int64_t sb) {
-                seed_state(seeds[k], state);
-                return ga_problem_align(c, state, chars + seq_off[sa], chars + seq_off[sb], out_a + out_off[k],
-                                        out_mid + out_off[k], out_b + out_off[k], out_off[k + 1] - out_off[k],
-                                        &out_len[k], &tb_status[k], &cost_out[k]);
-            };
-            if (int r = batch_single_pair(c, codes, seq_off, pair_a, pair_b, pair_max_cost, cs, k, align)) return r;
-        }
-    }
-    c->batch_align_ms[3] = (float)(now_ms() - t_call);
-    return GA_OK;
-}
-
-// ga_batch_sample: every pair filled once, then walked once per sample.  Kernel pairs go chunk by
-// chunk through batch_words_kernel and, walk launch by walk launch, through batch_walks_kernel; a pair that left the
-// kernel route for its size is filled once by the single-pair engine with stored words and walked by the same kernel
-// in the fill's layout; what remains is looped sample by sample through ga_problem_align.
-static int batch_sample_impl(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
-                             const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
-                             const int64_t* sample_off, const uint64_t* seeds, const char* chars, char* out_a,
-                             char* out_mid, char* out_b, const int64_t* out_off, int64_t* out_len, int32_t* tb_status,
-                             int64_t* cost_out, uint32_t flags) {
-    if (int r = check_ctx(c)) return r;
-    if ((flags & ~GA_BATCH_TABLES_MASK) || (flags & GA_BATCH_TABLES_MASK) > GA_BATCH_TABLES_DEVICE)
-        return fail(GA_E_ARG, "bad flags: bits 0-1 choose the tables (0 default, 1 host, 2 device)");
-    for (int64_t& x : c->batch_sample_info) x = 0;
-    for (float& x : c->batch_sample_ms) x = 0.f;
-    if (npairs == 0) return GA_OK;  // an empty batch: no launch
-    if (!sample_off || !seeds || !chars || !out_a || !out_mid || !out_b || !out_off || !out_len || !tb_status || !cost_out)
-        return fail(GA_E_ARG, "null argument");
-    const double t_call = now_ms();
-    const int64_t max_waves = batch_max_waves(c);
-    gabatch::SampleLimits lim;
-    if (const char* e = c->knob("GA_BATCH_ALIGN_MAX_CELLS")) lim.max_cells = std::max<int64_t>(0, atoll(e));
-    if (const char* e = c->knob("GA_BATCH_SAMPLE_CHUNK_WORDS")) lim.chunk_tb_words = std::max<int64_t>(1, atoll(e));
-    if (const char* e = c->knob("GA_BATCH_SAMPLE_WALK_ENTRIES")) lim.walk_entries = std::max<int64_t>(1, atoll(e));
-    lim.scratch_rows_cap = gabatch::scratch_rows_cap(max_waves);
-    gabatch::SamplePlan plan;
-    std::string why;
-    if (int r = gabatch::plan_batch_sample(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, sample_off,
-                                           lim, plan, why))
-        return fail(r, why);
-    auto len_of = [&](int64_t s) { return seq_off[s + 1] - seq_off[s]; };
-    for (int64_t k = 0; k < npairs; k++)
-        for (int64_t f = sample_off[k]; f < sample_off[k + 1]; f++)
-            if (out_off[f] < 0 || out_off[f + 1] - out_off[f] < len_of(pair_a[k]) + len_of(pair_b[k]))
-                return fail(GA_E_ARG, "pair " + std::to_string(k) + ": output capacity too small");
-    if (!plan.single.empty() && c->slab)
-        return fail(GA_E_STATE, "pair " + std::to_string(plan.single[0]) +
-                                    ": needs the single-pair path, which a slab context cannot run");
-    const char* nt = c->knob("GA_BATCH_RNG_THREADS");
-    const size_t ncodes = (size_t)seq_off[nseq];
-    double walk_ticks = 0, walk_steps = 0;
-
-    // The walk launches `launches` over `witems` (both counted from 0 here) of the pairs `fitems`, whose work list and
-    // slices are on the device at fitems_dev / fwords_dev and whose words lie in tb (tb_words u32s, `layout`, `tc`);
-    // bt_codes holds the batch's codes.  Tables by the call's route; a walk launch whose generator reached a word cap
-    // runs again with host tables (the fill stays).  Then the copies back and the strings.
-    auto run_walks = [&](const std::vector<ga_batch_item>& fitems, const ga_batch_item* fitems_dev,
-                         const ga_batch_words_item* fwords_dev, const uint32_t* tb, int64_t tb_words, int CB, int layout,
-                         int tc, const ga_batch_sample_item* witems, const gabatch::WalkLaunch* launches,
-                         int64_t nlaunch) -> int {
-        for (int64_t L = 0; L < nlaunch; L++) {
-            const gabatch::WalkLaunch& wl = launches[L];
-            const ga_batch_sample_item* wi = witems + wl.first;
-            const int64_t nw = wl.count;
-            HIPCHK(c->bs_witems.ensure(sizeof(ga_batch_sample_item) * nw));
-            HIPCHK(c->bs_ticket.ensure(sizeof(unsigned)));
-            HIPCHK(c->bt_walk.ensure(sizeof(int4) * 2 * nw));
-            HIPCHK(c->bt_rng.ensure(sizeof(uint32_t) * wl.tab_entries));
-            HIPCHK(c->bt_ops.ensure(sizeof(uint32_t) * wl.ops_words));
-            HIPCHK(hipMemcpyAsync(c->bs_witems.p, wi, sizeof(ga_batch_sample_item) * nw, hipMemcpyHostToDevice, c->stream));
-            const int W = gabatch::kWavesPerGroup;
-            const int waves = (int)((std::min<int64_t>(max_waves, nw) + W - 1) / W * W);
-            std::vector<int4> walked((size_t)nw * 2);
-            std::vector<uint32_t> ops((size_t)wl.ops_words);
-            RngRoute route = rng_route(c, flags);
-            for (int attempt = 0;; attempt++) {
-                // every walk's table from its own seed: the device-routed items' by batch_rng_kernel ahead of the
-                // walks on the same stream, the others' on a few host threads meanwhile (threads sized by items)
-                std::vector<gabrng::Item> dev;
-                std::vector<ga_batch_item> host_items;
-                std::vector<ga_batch_walk_item> host_walk;
-                for (int64_t t = 0; t < nw; t++) {
-                    ga_batch_item it = fitems[(size_t)wi[t].fill];
-                    const int64_t steps = (int64_t)it.m + it.n;
-                    if (gabrng::route_device(route.want_device, steps, route.max_steps)) {
-                        dev.push_back(gabrng::Item{seeds[wi[t].out], wi[t].tab_off, (int32_t)steps, 0});
-                    } else {
-                        it.out = wi[t].out;  // (build_pair_tables takes the item's seed from seeds[out])
-                        host_items.push_back(it);
-                        host_walk.push_back(ga_batch_walk_item{wi[t].tab_off, wi[t].ops_off});
-                    }
-                }
-                int groups = 0;
-                if (!dev.empty())
-                    if (int r = enqueue_batch_rng(c, dev, c->bt_rng.as<uint32_t>(), route.cap_words, &groups)) return r;
-                const double t_tab = now_ms();
-                std::vector<uint32_t> tab(host_items.empty() ? 0 : (size_t)wl.tab_entries);
-                if (!host_items.empty()) {
-                    const int64_t nhost = (int64_t)host_items.size();
-                    gabatch::build_pair_tables(host_items.data(), host_walk.data(), nhost, seeds,
-                                               gabatch::rng_threads(nt ? atoi(nt) : 0, nhost), tab.data());
-                    int64_t first = host_walk[0].tab_off, last = first;
-                    for (int64_t t = 0; t < nhost; t++) {
-                        const int64_t off = host_walk[(size_t)t].tab_off;
-                        if (off != last) {
-                            if (int r = upload_table_range(c, tab.data(), c->bt_rng.as<uint32_t>(), first, last)) return r;
-                            first = off;
-                        }
-                        last = off + host_items[(size_t)t].m + host_items[(size_t)t].n;
-                    }
-                    if (int r = upload_table_range(c, tab.data(), c->bt_rng.as<uint32_t>(), first, last)) return r;
-                }
-                const float host_tab_ms = (float)(now_ms() - t_tab);
-                c->batch_sample_info[6] += (int64_t)dev.size();
-                c->batch_sample_info[7] += (int64_t)host_items.size();
-                // the walks' ticket starts at zero for every launch
-                HIPCHK(hipMemsetAsync(c->bs_ticket.p, 0, sizeof(unsigned), c->stream));
-                HIPCHK(hipEventRecord(c->wev[0], c->stream));
-                const ga::WalksArgs q{c->bt_codes.as<uint8_t>(), (long long)ncodes, cs->gap_open, fitems_dev, fwords_dev,
-                                      (int)fitems.size(), c->bs_witems.as<ga_batch_sample_item>(), (int)nw,
-                                      c->bs_ticket.as<unsigned>(), c->bt_rng.as<uint32_t>(), (long long)wl.tab_entries,
-                                      c->bt_ops.as<uint32_t>(), (long long)wl.ops_words, c->bt_walk.as<int4>(), tb,
-                                      (long long)tb_words, tc};
-                ga::launch_batch_walks(c->stream, q, CB, layout, waves);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipEventRecord(c->wev[1], c->stream));
-                c->batch_sample_info[5]++;
-                HIPCHK(hipMemcpyAsync(walked.data(), c->bt_walk.p, sizeof(int4) * 2 * nw, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipMemcpyAsync(ops.data(), c->bt_ops.p, sizeof(uint32_t) * ops.size(), hipMemcpyDeviceToHost,
-                                      c->stream));
-                std::vector<int32_t> rstatus(dev.size());
-                if (!dev.empty())
-                    HIPCHK(hipMemcpyAsync(rstatus.data(), c->bt_rstatus.p, sizeof(int32_t) * dev.size(),
-                                          hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipStreamSynchronize(c->stream));
-                float walk_ms = 0.f, gen_ms = 0.f;
-                HIPCHK(hipEventElapsedTime(&walk_ms, c->wev[0], c->wev[1]));
-                c->batch_sample_ms[1] += walk_ms;
-                if (!dev.empty()) HIPCHK(hipEventElapsedTime(&gen_ms, c->rev[0], c->rev[1]));
-                c->batch_sample_ms[2] += gen_ms + std::max(0.f, host_tab_ms - gen_ms);
-                bool capped = false;
-                for (const int32_t st : rstatus) capped |= st != gabrng::kComplete;
-                if (!capped) break;
-                // an item stopped at its word cap: its walk read unwritten entries (harmlessly: a walk makes at most
-                // m + n - 1 steps whatever the table holds); nothing of this launch is decoded, it runs again with
-                // host tables
-                if (attempt > 0) return fail(GA_E_STATE, "the host tables' walk launch reports a generator status");
-                route = rng_route(c, GA_BATCH_TABLES_HOST);
-            }
-            const double t_dec = now_ms();
-            std::vector<int64_t> lens((size_t)nw);
-            gabatch::run_shares(nw, gabatch::rng_threads(nt ? atoi(nt) : 0, nw), [&](int64_t first, int64_t stride) {
-                for (int64_t t = first; t < nw; t += stride) {
-                    const ga_batch_item& it = fitems[(size_t)wi[t].fill];
-                    const size_t f = (size_t)wi[t].out;
-                    const int4 wr = walked[2 * (size_t)t];
-                    tb_status[f] = GA_TB_OK;
-                    lens[(size_t)t] = out_len[f] =
-                        wr.x < 0 ? -3
-                        : wr.x > (int64_t)it.m + it.n
-                            ? -2
-                            : gabatch::decode_levels(ops.data() + wi[t].ops_off, wr.x, it.m, it.n, wr.y, wr.z, wr.w,
-                                                     chars + it.a_off, chars + it.b_off, out_a + out_off[f],
-                                                     out_mid + out_off[f], out_b + out_off[f], out_off[f + 1] - out_off[f]);
-                }
-            });
-            c->batch_sample_ms[3] += (float)(now_ms() - t_dec);
-            for (int64_t t = 0; t < nw; t++) {
-                const int64_t k = fitems[(size_t)wi[t].fill].out;
-                // (batch_single_pair names the pair of a large-route walk itself)
-                const std::string at = layout == gabatch::LAYOUT_BATCH ? "pair " + std::to_string(k) + ": " : std::string();
-                if (lens[(size_t)t] == -3) return fail(GA_E_STATE, at + "walk item does not fit the batch launch");
-                if (lens[(size_t)t] < 0) return fail(GA_E_STATE, at + "the walk's levels do not decode");
-                walk_ticks += walked[2 * (size_t)t + 1].y;
-                walk_steps += walked[2 * (size_t)t].x;
-            }
-            c->batch_sample_info[3] += nw;
-        }
-        return GA_OK;
-    };
-
-    // the kernel pairs, fill chunk by fill chunk
-    for (const gabatch::FillChunk& ch : plan.chunks) {
-        const std::vector<ga_batch_item> items(plan.kernel.begin() + ch.first, plan.kernel.begin() + ch.first + ch.count);
-        BatchStage bs;
-        if (int r = stage_batch(c, codes, seq_off, nseq, npairs, cs, items, plan.scratch_rows, bs)) return r;
-        HIPCHK(c->bs_words.ensure(sizeof(ga_batch_words_item) * items.size()));
-        if (c->bs_tb.ensure(sizeof(uint32_t) * (size_t)ch.tb_words) != hipSuccess) {
-            (void)hipStreamSynchronize(c->stream);  // the staged uploads read this call's buffers
-            return fail(GA_E_NOMEM, "no device memory for the batch's traceback words");
-        }
-        HIPCHK(hipMemcpyAsync(c->bs_words.p, plan.words.data() + ch.first, sizeof(ga_batch_words_item) * items.size(),
-                              hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipEventRecord(c->fb.ev[0], c->stream));
-        const ga::WordsArgs q{bs.args, c->bs_words.as<ga_batch_words_item>(), c->bs_tb.as<uint32_t>(),
-                              (long long)ch.tb_words};
-        ga::launch_batch_words(c->stream, q, plan.qbytes, plan.CB, bs.waves);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(c->fb.ev[1], c->stream));
-        c->batch_sample_info[4]++;
-        std::vector<long long> got((size_t)npairs);
-        HIPCHK(hipMemcpyAsync(got.data(), c->bt_out.p, sizeof(long long) * npairs, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipEventElapsedTime(&c->fill_ms, c->fb.ev[0], c->fb.ev[1]));
-        c->batch_sample_ms[0] += c->fill_ms;
-        for (const ga_batch_item& it : items) {
-            if (got[(size_t)it.out] == INT64_MIN)
-                return fail(GA_E_STATE, "pair " + std::to_string(it.out) + ": work item does not fit the batch launch");
-            cost_out[it.out] = got[(size_t)it.out];
-        }
-        c->batch_sample_info[0] += (int64_t)items.size();
-        if (int r = run_walks(items, c->bt_items.as<ga_batch_item>(), c->bs_words.as<ga_batch_words_item>(),
-                              c->bs_tb.as<uint32_t>(), ch.tb_words, plan.CB, gabatch::LAYOUT_BATCH, 0,
-                              plan.walk.data(), plan.launches.data() + ch.launch_first, ch.launch_count))
-            return r;
-    }
-
-    if (!plan.single.empty()) {
-        // They go through the context's problem slot, so no problem is loaded afterwards.
-        uint32_t state[MTN + 1];
-        for (const int64_t k : plan.single) {
-            const int64_t sa = pair_a[k], sb = pair_b[k];
-            const int64_t m = len_of(sa), n = len_of(sb);
-            bool filled = false;
-            if (std::min(m, n) >= 2) {
-                // A pair that left the kernel route for its size: one single-pair fill with stored words, as
-                // ga_problem_align's stored-words route up to the walk, where the words fit band_rows' budget; its
-                // samples then walk c->fb.tb in that fill's layout.
-                c->rc_used = false;
-                auto fill = [&](int64_t, int64_t) -> int {
-                    if (band_rows(c) != 0) return GA_OK;
-                    if (int r = enqueue_fill(c, GA_FILL_TRACEBACK)) return r;
-                    if (int r = finish_fill(c, &cost_out[k], nullptr)) return r;
-                    c->batch_sample_ms[6] += c->fill_ms;
-                    const gaplan::FillPlan& pl = c->plan;
-                    const int64_t tb_words = (int64_t)pl.nstripes * pl.T * pl.TC * 256;
-                    if ((int64_t)pl.TC * (16 / c->CB) < m || tb_words < gabatch::stripe_words(n, pl.TC))
-                        return fail(GA_E_STATE, "the fill's words do not cover the pair");
-                    ga_batch_item it{};
-                    it.a_off = (int32_t)seq_off[sa];
-                    it.m = (int32_t)m;
-                    it.b_off = (int32_t)seq_off[sb];
-                    it.n = (int32_t)n;
-                    it.out = (int32_t)k;
-                    const std::vector<ga_batch_item> items(1, it);
-                    const ga_batch_words_item ws{0, tb_words};
-                    std::vector<ga_batch_sample_item> walk;
-                    std::vector<gabatch::WalkLaunch> launches;
-                    gabatch::plan_walk_launches(items.data(), 1, sample_off, lim.walk_entries, walk, launches);
-                    HIPCHK(c->bt_codes.ensure(ncodes));
-                    HIPCHK(c->bt_items.ensure(sizeof(ga_batch_item)));
-                    HIPCHK(c->bs_words.ensure(sizeof(ga_batch_words_item)));
-                    HIPCHK(hipMemcpyAsync(c->bt_codes.p, codes, ncodes, hipMemcpyHostToDevice, c->stream));
-                    HIPCHK(hipMemcpyAsync(c->bt_items.p, items.data(), sizeof(ga_batch_item), hipMemcpyHostToDevice, c->stream));
-                    HIPCHK(hipMemcpyAsync(c->bs_words.p, &ws, sizeof(ws), hipMemcpyHostToDevice, c->stream));
-                    c->batch_sample_info[1]++;
-                    c->batch_sample_info[4]++;
-                    filled = true;
-                    return run_walks(items, c->bt_items.as<ga_batch_item>(), c->bs_words.as<ga_batch_words_item>(),
-                                     c->fb.tb.as<uint32_t>(), tb_words, c->CB, gabatch::LAYOUT_STRIPE, pl.TC, walk.data(),
-                                     launches.data(), (int64_t)launches.size());
-                };
-                if (int r = batch_single_pair(c, codes, seq_off, pair_a, pair_b, pair_max_cost, cs, k, fill)) return r;
-                c->filled_tb = false;
-            }
-            if (filled) continue;
-            // a one-letter sequence (only such a pair can raise the reference's IndexError or take its first-step
-            // quirk), or words beyond the budget: sample by sample through the single-pair path, each from its seeded
-            // state (the state it leaves is dropped)
-            c->rc_used = false;
-            for (int64_t f = sample_off[k]; f < sample_off[k + 1]; f++) {
-                auto align = [&](int64_t a_seq, int64_t b_seq) {
-                    seed_state(seeds[f], state);
-                    return ga_problem_align(c, state, chars + seq_off[a_seq], chars + seq_off[b_seq], out_a + out_off[f],
-                                            out_mid + out_off[f], out_b + out_off[f], out_off[f + 1] - out_off[f],
-                                            &out_len[f], &tb_status[f], &cost_out[k]);
-                };
-                if (int r = batch_single_pair(c, codes, seq_off, pair_a, pair_b, pair_max_cost, cs, k, align)) return r;
-            }
-            c->batch_sample_info[2]++;
-        }
-    }
-    c->batch_sample_ms[4] = (float)(now_ms() - t_call);
-    c->batch_sample_ms[5] = (float)(10.0 * walk_ticks / std::max(walk_steps, 1.0));  // (a tick is 10 ns)
-    return GA_OK;
-}
-
-int ga_batch_sample_info(ga_ctx* c, int64_t* out8) {
-    if (!c || !out8) return fail(GA_E_ARG, "null argument");
-    for (int q = 0; q < 8; q++) out8[q] = c->batch_sample_info[q];
-    return GA_OK;
-}
-
-int ga_batch_sample_timings(ga_ctx* c, float* out8) {
-    if (!c || !out8) return fail(GA_E_ARG, "null argument");
-    for (int q = 0; q < 8; q++) out8[q] = c->batch_sample_ms[q];
-    return GA_OK;
-}
-
-int ga_batch_align_timings(ga_ctx* c, float* out6) {
-    if (!c || !out6) return fail(GA_E_ARG, "null argument");
-    for (int q = 0; q < 6; q++) out6[q] = c->batch_align_ms[q];
-    return GA_OK;
-}
-
-int ga_batch_align_info(ga_ctx* c, int32_t* out4) {
-    if (!c || !out4) return fail(GA_E_ARG, "null argument");
-    for (int q = 0; q < 4; q++) out4[q] = c->batch_rng_info[q];
-    return GA_OK;
-}
-
-static int debug_pair_tables_impl(ga_ctx* c, const uint64_t* seeds, const int32_t* steps, int64_t nitems, int32_t route,
-                                  uint32_t* tab_out, int32_t* status_out) {
-    if (int r = check_ctx(c)) return r;
-    if (route != GA_BATCH_TABLES_HOST && route != GA_BATCH_TABLES_DEVICE)
-        return fail(GA_E_ARG, "route must be 1 (host) or 2 (device)");
-    if (nitems < 0 || (nitems > 0 && (!seeds || !steps || !tab_out || !status_out))) return fail(GA_E_ARG, "null argument");
-    for (int32_t& x : c->batch_rng_info) x = 0;
-    c->batch_align_ms[1] = 0.f;
-    // On the device the items lie kGuard words apart, between guard words no entry equals (bits 0 and 31 are never
-    // set in one): a write outside an item's range shows as status 2.
-    constexpr int64_t kGuard = 4;
-    constexpr uint32_t kGuardWord = 0xA5A5A5A5u;
-    const RngRoute rt = rng_route(c, (uint32_t)route);
-    std::vector<gabrng::Item> dev;
-    std::vector<int64_t> dev_of, out_off((size_t)nitems + 1, 0);
-    int64_t dev_words = kGuard;
-    for (int64_t t = 0; t < nitems; t++) {
-        if (steps[t] < 0) return fail(GA_E_ARG, "item " + std::to_string(t) + ": negative steps");
-        out_off[(size_t)t + 1] = out_off[(size_t)t] + steps[t];
-        status_out[t] = gabrng::kComplete;
-        if (gabrng::route_device(rt.want_device, steps[t], rt.max_steps)) {
-            dev.push_back(gabrng::Item{seeds[t], dev_words, steps[t], 0});
-            dev_of.push_back(t);
-            dev_words += steps[t] + kGuard;
-        }
-    }
-    int groups = 0;
-    std::vector<uint32_t> got;
-    std::vector<int32_t> rstatus(dev.size());
-    if (!dev.empty()) {
-        got.resize((size_t)dev_words);
-        HIPCHK(c->bt_rng.ensure(sizeof(uint32_t) * (size_t)dev_words));
-        HIPCHK(hipMemsetAsync(c->bt_rng.p, 0xA5, sizeof(uint32_t) * (size_t)dev_words, c->stream));
-        if (int r = enqueue_batch_rng(c, dev, c->bt_rng.as<uint32_t>(), rt.cap_words, &groups)) return r;
-        HIPCHK(hipMemcpyAsync(got.data(), c->bt_rng.p, sizeof(uint32_t) * got.size(), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(rstatus.data(), c->bt_rstatus.p, sizeof(int32_t) * dev.size(), hipMemcpyDeviceToHost,
-                              c->stream));
-    }
-    // the host's items meanwhile, one after the other
-    {
-        garng::RngTable R;
-        uint32_t state[garng::MTN + 1];
-        size_t q = 0;
-        for (int64_t t = 0; t < nitems; t++) {
-            if (q < dev_of.size() && dev_of[q] == t) {
-                q++;
-                continue;
-            }
-            garng::seed_state(seeds[t], state);
-            R.start(state);
-            R.extend(steps[t]);
-            std::copy(R.tab.begin(), R.tab.begin() + steps[t], tab_out + out_off[(size_t)t]);
-        }
-    }
-    if (!dev.empty()) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipEventElapsedTime(&c->batch_align_ms[1], c->rev[0], c->rev[1]));
-        for (size_t q = 0; q < dev.size(); q++) {
-            const int64_t t = dev_of[q], off = dev[q].tab_off;
-            std::copy(got.begin() + off, got.begin() + off + steps[t], tab_out + out_off[(size_t)t]);
-            bool intact = true;
-            for (int64_t g = 1; g <= kGuard; g++)
-                intact &= got[(size_t)(off - g)] == kGuardWord && got[(size_t)(off + steps[t] + g - 1)] == kGuardWord;
-            status_out[t] = intact ? rstatus[q] : 2;
-        }
-    }
-    c->batch_rng_info[0] = (int32_t)dev.size();
-    c->batch_rng_info[1] = (int32_t)(nitems - (int64_t)dev.size());
-    c->batch_rng_info[3] = groups;
-    return GA_OK;
 }
 
 int ga_debug_seed_state(uint64_t seed, uint32_t* state_out) {
@@ -3620,37 +2586,6 @@ int ga_problem_set(ga_ctx* c, const uint8_t* a, int64_t m, const uint8_t* b, int
 
 int ga_problem_fill(ga_ctx* c, int32_t flags, int64_t* cost_out, int32_t* full_out) {
     return guard_end(c, problem_fill_impl(c, flags, cost_out, full_out));
-}
-
-int ga_batch_costs_ex(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
-                      const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
-                      int64_t* cost_out) {
-    return guard_end(c, batch_costs_ex_impl(c, codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs,
-                                            cost_out));
-}
-
-int ga_batch_align_ex(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
-                      const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
-                      const uint64_t* seeds, const char* chars, char* out_a, char* out_mid, char* out_b,
-                      const int64_t* out_off, int64_t* out_len, int32_t* tb_status, int64_t* cost_out, uint32_t flags) {
-    return guard_end(c, batch_align_ex_impl(c, codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, seeds,
-                                            chars, out_a, out_mid, out_b, out_off, out_len, tb_status, cost_out,
-                                            flags));
-}
-
-int ga_batch_sample(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
-                    const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
-                    const int64_t* sample_off, const uint64_t* seeds, const char* chars, char* out_a, char* out_mid,
-                    char* out_b, const int64_t* out_off, int64_t* out_len, int32_t* tb_status, int64_t* cost_out,
-                    uint32_t flags) {
-    return guard_end(c, batch_sample_impl(c, codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, sample_off,
-                                          seeds, chars, out_a, out_mid, out_b, out_off, out_len, tb_status, cost_out,
-                                          flags));
-}
-
-int ga_debug_pair_tables(ga_ctx* c, const uint64_t* seeds, const int32_t* steps, int64_t nitems, int32_t route,
-                         uint32_t* tab_out, int32_t* status_out) {
-    return guard_end(c, debug_pair_tables_impl(c, seeds, steps, nitems, route, tab_out, status_out));
 }
 
 int ga_problem_set_cells(ga_ctx* c, const int32_t* cells, int64_t* cost_out) {

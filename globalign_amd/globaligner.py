@@ -150,37 +150,18 @@ class GlobalAligner:
         on the GPU ahead of the walks, so the call's time does not depend on the host's cores); the results are the
         same byte for byte.
         -> BatchAlignments."""
-        if tables not in ("host", "device"):
-            raise ValueError(f"tables must be 'host' or 'device', not {tables!r}")
-        seqs_1, seqs_2 = list(seqs_1), list(seqs_2)
-        if len(seqs_1) != len(seqs_2):
-            raise ValueError(f"align_pairs needs as many first as second sequences, got {len(seqs_1)} and "
-                             f"{len(seqs_2)}")
-        if not self.traceback:
-            raise ValueError("align_pairs returns alignment strings; an aligner made with traceback=False scores "
-                             "batches with score_pairs")
-        if len(self.devices) > 1:
-            raise ValueError(f"align_pairs runs on one GPU; this aligner was made with devices={self.devices}")
-        P = len(seqs_1)
-        seeds = _pair_seeds(seeds, P)
-        if P == 0:
+        seeds, b, route = self._strings_batch("align_pairs", seqs_1, seqs_2, tables, lambda P: _pair_seeds(seeds, P))
+        if b is None:
             e = self._empty_batch((0,))
             return BatchAlignments([], [], [], e.costs, e.scores, *e[2:])
-        b = self._prepare_batch(seqs_1 + seqs_2, np.arange(P, dtype=np.int64), np.arange(P, 2 * P, dtype=np.int64))
-        if b.text is None:
-            raise ValueError("align_pairs takes sequences of one-byte (latin-1) letters")
         eng = _native.default_engine(self.device)
-        # (the host route is the engine's call as it always was; only the device route names itself)
-        route = {} if tables == "host" else {"rng_tables": tables}
         costs, status, lengths, offsets, bufs = eng.batch_align(b.codes, b.seq_off, b.pair_a, b.pair_b, b.tables, seeds,
                                                                 np.frombuffer(b.text, dtype=np.uint8), b.pair_max_cost,
                                                                 **route)
         failed = np.flatnonzero(status == _native.GA_TB_INDEX_ERROR)
         if failed.size:
             raise IndexError(f"pair {int(failed[0])}: string index out of range")  # the reference's, SURVEY A.5
-        texts = [buf.tobytes().decode("latin-1") for buf in bufs]
-        lo, hi = offsets[:-1].tolist(), (offsets[:-1] + lengths).tolist()
-        strings = [[t[x:y] for x, y in zip(lo, hi)] for t in texts]
+        strings = _cut_strings(bufs, offsets, lengths)
         return BatchAlignments(strings[0], strings[1], strings[2], costs, b.scores(costs), b.scoring_mat, b.costing_mat,
                                b.gap_open_score, b.gap_open_cost)
 
@@ -197,28 +178,13 @@ class GlobalAligner:
         IndexError of a one-letter pair (raised for the lowest pair any of whose samples raises it) and ``tables`` are
         align_pairs's.
         -> BatchSamples."""
-        if tables not in ("host", "device"):
-            raise ValueError(f"tables must be 'host' or 'device', not {tables!r}")
-        seqs_1, seqs_2 = list(seqs_1), list(seqs_2)
-        if len(seqs_1) != len(seqs_2):
-            raise ValueError(f"sample_alignments needs as many first as second sequences, got {len(seqs_1)} and "
-                             f"{len(seqs_2)}")
-        if not self.traceback:
-            raise ValueError("sample_alignments returns alignment strings; an aligner made with traceback=False scores "
-                             "batches with score_pairs")
-        if len(self.devices) > 1:
-            raise ValueError(f"sample_alignments runs on one GPU; this aligner was made with devices={self.devices}")
-        P = len(seqs_1)
-        counts, flat = _sample_seeds(samples, seeds, P)
-        sample_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        if P == 0:
+        (counts, flat), b, route = self._strings_batch("sample_alignments", seqs_1, seqs_2, tables,
+                                                       lambda P: _sample_seeds(samples, seeds, P))
+        if b is None:
             e = self._empty_batch((0,))
             return BatchSamples([], [], [], e.costs, e.scores, [], *e[2:])
-        b = self._prepare_batch(seqs_1 + seqs_2, np.arange(P, dtype=np.int64), np.arange(P, 2 * P, dtype=np.int64))
-        if b.text is None:
-            raise ValueError("sample_alignments takes sequences of one-byte (latin-1) letters")
+        sample_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         eng = _native.default_engine(self.device)
-        route = {} if tables == "host" else {"rng_tables": tables}
         costs, status, lengths, offsets, bufs = eng.batch_sample(b.codes, b.seq_off, b.pair_a, b.pair_b, b.tables,
                                                                  sample_off, flat, np.frombuffer(b.text, dtype=np.uint8),
                                                                  b.pair_max_cost, **route)
@@ -226,14 +192,37 @@ class GlobalAligner:
         if failed.size:
             k = int(np.searchsorted(sample_off, failed[0], side="right")) - 1
             raise IndexError(f"pair {k}: string index out of range")  # the reference's, SURVEY A.5
-        texts = [buf.tobytes().decode("latin-1") for buf in bufs]
-        lo, hi = offsets[:-1].tolist(), (offsets[:-1] + lengths).tolist()
-        cut = sample_off.tolist()
-        strings = [[[t[x:y] for x, y in zip(lo[cut[k]:cut[k + 1]], hi[cut[k]:cut[k + 1]])] for k in range(P)]
-                   for t in texts]
+        cut = list(zip(sample_off[:-1].tolist(), sample_off[1:].tolist()))
+        strings = [[flat_strings[x:y] for x, y in cut] for flat_strings in _cut_strings(bufs, offsets, lengths)]
         return BatchSamples(strings[0], strings[1], strings[2], costs, b.scores(costs),
-                            [flat[cut[k]:cut[k + 1]].copy() for k in range(P)], b.scoring_mat, b.costing_mat,
+                            [flat[x:y].copy() for x, y in cut], b.scoring_mat, b.costing_mat,
                             b.gap_open_score, b.gap_open_cost)
+
+    def _strings_batch(self, method, seqs_1, seqs_2, tables, seeds_of):
+        """The front half of align_pairs and sample_alignments (`method`: the name in the messages): the checks in their
+        order, the seeds by seeds_of(P), and the batch.  -> (seeds, the _prepare_batch namespace or None for no pairs,
+        the engine call's route arguments)."""
+        if tables not in ("host", "device"):
+            raise ValueError(f"tables must be 'host' or 'device', not {tables!r}")
+        seqs_1, seqs_2 = list(seqs_1), list(seqs_2)
+        if len(seqs_1) != len(seqs_2):
+            raise ValueError(f"{method} needs as many first as second sequences, got {len(seqs_1)} and "
+                             f"{len(seqs_2)}")
+        if not self.traceback:
+            raise ValueError(f"{method} returns alignment strings; an aligner made with traceback=False scores "
+                             "batches with score_pairs")
+        if len(self.devices) > 1:
+            raise ValueError(f"{method} runs on one GPU; this aligner was made with devices={self.devices}")
+        P = len(seqs_1)
+        seeds = seeds_of(P)
+        # (the host route is the engine's call as it always was; only the device route names itself)
+        route = {} if tables == "host" else {"rng_tables": tables}
+        if P == 0:
+            return seeds, None, route
+        b = self._prepare_batch(seqs_1 + seqs_2, np.arange(P, dtype=np.int64), np.arange(P, 2 * P, dtype=np.int64))
+        if b.text is None:
+            raise ValueError(f"{method} takes sequences of one-byte (latin-1) letters")
+        return seeds, b, route
 
     def _empty_batch(self, shape):
         """No pairs: empty arrays, no launch.  The option checks still run, through the single call's validation of
@@ -358,6 +347,12 @@ class GlobalAligner:
                                      pair_max_cost=pair_max_cost, text=text, scoring_mat=scoring_mat,
                                      costing_mat=costing_mat, gap_open_score=gap_open_score,
                                      gap_open_cost=gap_open_cost, scores=scores)
+
+
+def _cut_strings(bufs, offsets, lengths):
+    """The engine's three output buffers as three lists of strings: slot f's are the lengths[f] bytes at offsets[f]."""
+    lo, hi = offsets[:-1].tolist(), (offsets[:-1] + lengths).tolist()
+    return [[t[x:y] for x, y in zip(lo, hi)] for t in (buf.tobytes().decode("latin-1") for buf in bufs)]
 
 
 def _pair_seeds(seeds, P):

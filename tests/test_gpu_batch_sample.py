@@ -264,6 +264,37 @@ def test_large_route_at_small_size(ga, large_batch, monkeypatch):
     assert _engine().batch_sample_info()["filled_pairs"] == 4
 
 
+def test_large_route_with_both_table_routes(ga, large_batch, monkeypatch):
+    """The single-pair fills' walk launches under tables="device" with the generator's limit at 600 dispatches: the
+    pairs of 194 and 557 have their tables from the device, those of 1026 and 1570 from the host."""
+    pairs, counts, base, want = large_batch
+    set_knob(monkeypatch, "GA_BATCH_ALIGN_MAX_CELLS", 4096)
+    set_knob(monkeypatch, "GA_BATCH_RNG_DEVICE_MAX_STEPS", 600)
+    assert min(m + n for m, n in LARGE_SHAPES) < 600 < max(m + n for m, n in LARGE_SHAPES)
+    _check_samples(ga, DNA, pairs, counts, base, want=want, tables="device")
+    info = _engine().batch_sample_info()
+    n_dev = sum(c for (m, n), c in zip(LARGE_SHAPES, counts) if m + n <= 600)
+    assert info["single_fill_pairs"] == 4 and info["filled_pairs"] == 0 and info["walk_items"] == 16
+    assert n_dev == 8 and info["device_items"] == n_dev and info["host_items"] == 16 - n_dev
+
+
+def test_large_route_fallback_at_the_word_cap(ga, large_batch, monkeypatch):
+    """GA_BATCH_RNG_WORD_CAP=24 with every pair's tables on the device (walks of 194-1570 dispatches take 32 words each
+    on average): each single-pair fill's walk launch runs again with host tables, the fills do not."""
+    pairs, counts, base, want = large_batch
+    set_knob(monkeypatch, "GA_BATCH_ALIGN_MAX_CELLS", 4096)
+    set_knob(monkeypatch, "GA_BATCH_RNG_DEVICE_MAX_STEPS", 2000)
+    _check_samples(ga, DNA, pairs, counts, base, want=want, tables="device")
+    uncapped = _engine().batch_sample_info()
+    assert uncapped["single_fill_pairs"] == 4 and uncapped["device_items"] == 16 and uncapped["host_items"] == 0
+    set_knob(monkeypatch, "GA_BATCH_RNG_WORD_CAP", 24)
+    _check_samples(ga, DNA, pairs, counts, base, want=want, tables="device")
+    info = _engine().batch_sample_info()
+    assert info["walk_launches"] == 2 * uncapped["walk_launches"] == 8
+    assert info["fill_launches"] == uncapped["fill_launches"] and info["single_fill_pairs"] == 4
+    assert info["device_items"] == 16 and info["host_items"] == 16 and info["walk_items"] == 16
+
+
 def test_large_route_at_the_defaults(ga):
     """One 2000 x 1500 pair (3e6 cells, above the default limit of 2^20) x 8 samples."""
     pair = (splitmix_seq(2000, 1, "dna"), splitmix_seq(1500, 2, "dna"))
