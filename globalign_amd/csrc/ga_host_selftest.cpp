@@ -2,7 +2,8 @@
 // UndefinedBehaviorSanitizer (make -C globalign_amd/csrc asan; run by tests/test_host_asan.py):
 //   * the tie-break table (ga_rng.h): RngTable's four-word scan, its resumable extend() and state_after(), against a draw-by-draw restatement of CPython's random.choice (_randbelow_with_getrandbits over
 //     genrand_uint32) and the dispatcher's level rule (globaligner.py:595-685);
-//   * the problem checks (ga_check.h): argument validation, the int32 range guard, the profile / word widths;
+//   * the problem checks (ga_check.h): argument validation, the int32 range guard, the profile / word widths, and the
+//     limit tables of tests/limit_costs.py at the last factor the guard accepts and the first it refuses;
 //   * the fill planner (ga_plan.h): the kernel, geometry and checkpoint spacing of the shapes the project's records
 //     pin (profiles/r06, DESIGN.md 5.2 / 5.6 / 5.8.1, tests/test_gpu_rc_default_width.py), and every error return;
 //   * the guard bands' layout, scan and report (ga_guard.h) on a host model of a guarded buffer.
@@ -18,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "ga_batch.h"
 #include "ga_check.h"
 #include "ga_guard.h"
 #include "ga_plan.h"
@@ -199,6 +201,126 @@ void test_checks() {
           "boundary values in the range guard");
     // the lean checkpoint store's 32-bit buffer: recompute checkpoints refused past it
     CHECK(rc_rows_fit(100000) && !rc_rows_fit((int64_t)1 << 28), "rc_rows_fit");
+}
+
+// A K = 5 table over A C G T and '-' as CostTables lays a costing dict out: sub[x][4] = gap_v[x], sub[4][y] = gap_h[y].
+struct Table5 {
+    int32_t sub[25] = {}, gh[5] = {}, gv[5] = {};
+    ga_costs cs{5, sub, gh, gv, 0, 0};
+    Table5() = default;
+    Table5(const Table5&) = delete;
+    // sub' = d under the gap costs gh4 / gv4
+    void set(const int64_t (&d)[4][4], const int64_t (&gh4)[4], const int64_t (&gv4)[4], int o) {
+        int64_t mx = 0;
+        for (int x = 0; x < 4; x++) {
+            gh[x] = (int32_t)gh4[x];
+            gv[x] = (int32_t)gv4[x];
+            sub[x * 5 + 4] = gv[x];
+            sub[4 * 5 + x] = gh[x];
+            mx = std::max<int64_t>(mx, std::max(gh4[x], gv4[x]));
+            for (int y = 0; y < 4; y++) {
+                sub[x * 5 + y] = (int32_t)(d[x][y] + gv4[x] + gh4[y]);
+                mx = std::max<int64_t>(mx, sub[x * 5 + y]);
+            }
+        }
+        cs.gap_open = o;
+        cs.max_cost = (int32_t)mx;
+    }
+};
+
+// The limit families of tests/limit_costs.py at the factors its restated guard gives (tests/test_limit_costs_cpu.py
+// pins the same figures): check_problem accepts the factor and refuses factor + 1; the profile and word widths switch
+// where the restatement says they do.
+void test_limit_tables() {
+    std::vector<uint8_t> a(4096, 0), b(4096, 1);
+    ProblemShape ps;
+    std::string err;
+    auto check = [&](Table5& t, int64_t m, int64_t n) {
+        return check_problem(a.data(), m, b.data(), n, &t.cs, nullptr, nullptr, 0, n, ps, err);
+    };
+    // V16: match 0 / mismatch 5 / gaps 2-3, times f
+    auto v16 = [](Table5& t, int64_t f, int o) {
+        const int64_t gv[4] = {2 * f, 3 * f, 2 * f, 3 * f}, gh[4] = {3 * f, 2 * f, 3 * f, 2 * f};
+        int64_t d[4][4];
+        for (int x = 0; x < 4; x++)
+            for (int y = 0; y < 4; y++) d[x][y] = (x == y ? 0 : 5 * f) - gv[x] - gh[y];
+        t.set(d, gh, gv, o);
+    };
+    // Vphi: gap costs G + small offsets, sub' fixed within int8
+    auto vphi = [](Table5& t, int64_t G, int o) {
+        const int64_t d[4][4] = {{-127, 127, 12, 6}, {12, -127, 5, 12}, {6, 12, -127, -3}, {127, 0, 12, -127}};
+        const int64_t gv[4] = {G + 1, G + 4, G + 6, G + 9}, gh[4] = {G + 2, G + 3, G + 7, G + 8};
+        t.set(d, gh, gv, o);
+    };
+    struct Lim { const char* what; bool phi; int sign; int64_t m, n; int o; int64_t f; int qbytes; const char* why; };
+    const Lim lims[] = {
+        {"V16 1100 x 600", false, 1, 1100, 600, 32766, 6553, 2, "substitution costs exceed the int16 query profile"},
+        {"V16 4096 x 1024", false, 1, 4096, 1024, 5, 5516, 2, "problem exceeds the int32 score range of the device path"},
+        {"Vphi 777 x 2049", true, 1, 777, 2049, 7, 25415, 1, "problem exceeds the int32 score range of the device path"},
+        {"V- 2049 x 700", true, -1, 2049, 700, 5, 32462, 1, "problem exceeds the int32 score range of the device path"},
+    };
+    for (const Lim& L : lims)
+        for (int excess = 0; excess < 2; excess++) {
+            Table5 t;
+            if (L.phi) vphi(t, L.sign * (L.f + excess), L.o);
+            else v16(t, L.f + excess, L.o);
+            const int r = check(t, L.m, L.n);
+            if (!excess)
+                CHECK(r == GA_OK && ps.qbytes == L.qbytes, "%s at factor %lld: %d (%s), qbytes %d", L.what, (long long)L.f, r,
+                      err.c_str(), ps.qbytes);
+            else
+                CHECK(r == GA_E_RANGE && err == L.why, "%s at factor %lld: %d (%s)", L.what, (long long)L.f + 1, r, err.c_str());
+        }
+    {
+        // V32: the batch planner's range check of a pair (4-byte table entries, no profile limit)
+        for (int excess = 0; excess < 2; excess++) {
+            Table5 t;
+            v16(t, 221364 + excess, 32766);
+            int64_t big = 0;
+            const int r = gabatch::check_pair_range(65, 70, &t.cs, t.cs.max_cost, costs_maxabs(&t.cs), big);
+            CHECK(r == (excess ? GA_E_RANGE : GA_OK) && profile_bytes(&t.cs) == 0, "V32 65 x 70 at factor %d: %d", 221364 + excess, r);
+        }
+    }
+    {
+        // the profile width by the largest |sub'|, on either sign: int8 to 127, int16 to 32767, refused beyond
+        const int64_t gv[4] = {20, 25, 31, 40}, gh[4] = {23, 28, 35, 43};
+        struct W { int64_t v; int qbytes; };
+        for (const W& w : {W{127, 1}, W{128, 2}, W{32767, 2}, W{32768, 0}})
+            for (int sign : {1, -1}) {
+                int64_t d[4][4] = {};
+                d[2][3] = sign * w.v;
+                Table5 t;
+                t.set(d, gh, gv, 6);
+                CHECK(profile_bytes(&t.cs) == w.qbytes, "profile_bytes at sub' = %lld", (long long)(sign * w.v));
+                const int r = check(t, 70, 130);
+                if (w.qbytes)
+                    CHECK(r == GA_OK && ps.qbytes == w.qbytes, "sub' = %lld: %d (%s)", (long long)(sign * w.v), r, err.c_str());
+                else
+                    CHECK(r == GA_E_RANGE && err == "substitution costs exceed the int16 query profile", "sub' = %lld: %d (%s)",
+                          (long long)(sign * w.v), r, err.c_str());
+            }
+    }
+    // the traceback word by o + 1: its fields hold values up to o + 1
+    CHECK(tb_word_bytes(6) == 1 && tb_word_bytes(7) == 2 && tb_word_bytes(126) == 2 && tb_word_bytes(127) == 4 &&
+              tb_word_bytes(32766) == 4 && tb_word_bytes(32767) == 0,
+          "tb_word_bytes at the field widths");
+    {
+        Table5 t;
+        v16(t, 1, 32766);
+        CHECK(check(t, 70, 130) == GA_OK && ps.CB == 4, "o = 32766: %s", err.c_str());
+        t.cs.gap_open = 32767;
+        CHECK(check(t, 70, 130) == GA_E_RANGE && err == "gap_open cost too large for the traceback word", "o = 32767: %s", err.c_str());
+        // caller-supplied boundary values: the largest B the guard admits at 130 x 321, and B + 1
+        t.cs.gap_open = 6;
+        const int64_t m = 130, n = 321, B = ((int64_t)INT32_MAX - 1) / 4 - (m + n + 2) * (3 * costs_maxabs(&t.cs) + 6);
+        for (int sign : {1, -1})
+            for (int excess = 0; excess < 2; excess++) {
+                std::vector<int32_t> row0(3 * (n + 1), 0), col0(3 * (m + 1), 0);
+                col0[3 * m + 1] = (int32_t)(sign * (B + excess));
+                const int r = check_problem(a.data(), m, b.data(), n, &t.cs, row0.data(), col0.data(), 0, n, ps, err);
+                CHECK(r == (excess ? GA_E_RANGE : GA_OK), "boundary value %lld: %d", (long long)(sign * (B + excess)), r);
+            }
+    }
 }
 
 // ---------------------------------------------------------------- the fill planner (ga_plan.h)
@@ -520,6 +642,7 @@ int main(int argc, char** argv) {
     test_table(78, 1);
     test_table(79, 50000);
     test_checks();
+    test_limit_tables();
     test_plan();
     test_guard();
     if (failures) {

@@ -19,12 +19,14 @@ import numpy as np
 import pytest
 
 from tests import general_costs as gc
-from tests.conftest import set_knob, del_knob
+from tests import gpu_parity as gp
+from tests.conftest import set_knob
 
 pytestmark = pytest.mark.gpu
 
 
 # ---------------------------------------------------------------- shared, cached references
+# (the engine calls themselves are tests/gpu_parity.py's, shared with tests/test_gpu_limits.py)
 @functools.lru_cache(maxsize=None)
 def _problem(case):
     """(costing dict, seq_1, seq_2, gap open cost) of a case."""
@@ -32,27 +34,18 @@ def _problem(case):
     return gc.table(case[0], case[1]), s1, s2, case[4]
 
 
-def _mt(seed):
-    return np.array(random.Random(seed).getstate()[1], dtype=np.uint32)
+_mt = gp.mt
 
 
 @functools.lru_cache(maxsize=None)
 def _ref_chain(case, seed, count=1):
     """`count` consecutive oracle alignments of a case from random.seed(seed): [(cost, strings, status, mt words)]."""
-    from oracle import core
-    cmat, s1, s2, o = _problem(case)
-    mt, out = _mt(seed), []
-    for _ in range(count):
-        r = core.align(s1, s2, cmat, o, mt)
-        mt = np.asarray(r["mt_out"], dtype=np.uint32).copy()
-        out.append((r["cost"], tuple(r["strings"]), r["status"], tuple(mt.tolist())))
-    return out
+    return gp.ref_chain(_problem(case), seed, count)
 
 
 def _tables(case):
-    from globalign_amd import _native
-    cmat, s1, s2, o = _problem(case)
-    tables = _native.CostTables(cmat, o)
+    cmat = _problem(case)[0]
+    tables, s1, s2 = gp.tables(_problem(case))
     assert tables.gap_h.tolist()[:4] == gc.gap_h(cmat) and tables.gap_v.tolist()[:4] == gc.gap_v(cmat)
     return tables, s1, s2
 
@@ -64,46 +57,13 @@ def _int8(case):
 def _align(monkeypatch, case, seed, knobs, fill=None, walk=None):
     """Engine.align of a case under `knobs` against the oracle: cost, strings, status and every MT word; fill / walk:
     what fill_kind() / walk_kind() must report (fill: a kind, or (kind, columns per lane))."""
-    from globalign_amd import _native
-    for k, v in knobs.items():
-        set_knob(monkeypatch, k, v)
-    tables, s1, s2 = _tables(case)
-    cost_ref, strings_ref, status_ref, mt_ref = _ref_chain(case, seed)[0]
-    eng = _native.Engine(0)
-    try:
-        eng.load(tables.codes(s1), tables.codes(s2), tables)
-        cost, strings, status, mt_after = eng.align(_mt(seed), s1, s2)
-        kind, wkind = eng.fill_kind(), eng.walk_kind()
-    finally:
-        eng.close()
-    if fill is not None:
-        want = fill if isinstance(fill, tuple) else (fill,)
-        assert kind[:len(want)] == want, (kind, want)
-    if walk is not None:
-        assert wkind == walk, (wkind, kind)
-    assert status == (0 if status_ref == "ok" else _native.GA_TB_INDEX_ERROR)
-    assert int(cost) == cost_ref
-    assert tuple(strings) == strings_ref
-    assert tuple(np.asarray(mt_after, dtype=np.uint32).tolist()) == mt_ref
-    return kind
+    _tables(case)
+    return gp.align(monkeypatch, _problem(case), seed, knobs, _ref_chain(case, seed)[0], fill=fill, walk=walk)
 
 
 def _score(monkeypatch, case, knobs, fill, load_kw=None, problem=None):
     """Engine.fill(traceback=False) under `knobs` -> the cost; fill: the fill_kind() prefix that must have run."""
-    from globalign_amd import _native
-    for k, v in knobs.items():
-        set_knob(monkeypatch, k, v)
-    cmat, s1, s2, o = problem or _problem(case)
-    tables = _native.CostTables(cmat, o)
-    eng = _native.Engine(0)
-    try:
-        eng.load(tables.codes(s1), tables.codes(s2), tables, **(load_kw or {}))
-        cost = int(eng.fill(traceback=False)[0])
-        kind = eng.fill_kind()
-    finally:
-        eng.close()
-    assert kind[:len(fill)] == fill, (kind, fill)
-    return cost, kind
+    return gp.score(monkeypatch, problem or _problem(case), knobs, fill, load_kw)
 
 
 @functools.lru_cache(maxsize=None)
@@ -120,46 +80,20 @@ def _ids(cases):
 @functools.lru_cache(maxsize=None)
 def _full_reference(case, custom):
     """core.fill_full over the reference's boundary, or (custom) over random caller triples -> (dp, row0, col0)."""
-    from oracle import core
-    cmat, s1, s2, o = _problem(case)
-    tab = core.Tables(cmat)
-    a, b = tab.codes(s1), tab.codes(s2)
-    m, n = len(a), len(b)
+    boundary = None
     if custom:
+        m, n = case[2], case[3]
         rng = np.random.default_rng(5)
         row0 = rng.integers(0, 400, size=3 * (n + 1)).astype(np.int64)
         col0 = rng.integers(0, 400, size=3 * (m + 1)).astype(np.int64)
         row0[:3] = col0[:3] = 0
-    else:
-        row0, col0 = core.boundary(tab, a, b, o, (tab.max_cost + 1) * max(m, n))
-    dp = np.zeros((m + 1, n + 1, 3), np.int64)
-    dp[0, :, :] = row0.reshape(n + 1, 3)
-    dp[:, 0, :] = col0.reshape(m + 1, 3)
-    core.fill_full(tab, a, b, o, dp)
-    dp.setflags(write=False)
-    return dp, row0, col0
+        boundary = (row0, col0)
+    return gp.full_reference(_problem(case), boundary)
 
 
 def _full_cells(monkeypatch, case, t, custom=False):
-    from globalign_amd import _native
-    if t is None:
-        del_knob(monkeypatch, "GA_COLS_PER_LANE")
-    else:
-        set_knob(monkeypatch, "GA_COLS_PER_LANE", t)
-    dp, row0, col0 = _full_reference(case, custom)
-    tables, s1, s2 = _tables(case)
-    eng = _native.Engine(0)
-    try:
-        eng.load(tables.codes(s1), tables.codes(s2), tables, **(dict(row0=row0, col0=col0) if custom else {}))
-        cost, full = eng.fill(full=True)
-        kind = eng.fill_kind()
-    finally:
-        eng.close()
-    assert kind[0] == "row", kind
-    assert int(cost) == int(dp[-1, -1].min())
-    bad = np.argwhere(full[1:, 1:].astype(np.int64) != dp[1:, 1:])
-    assert bad.size == 0, [(int(i) + 1, int(j) + 1, int(k), int(full[i + 1, j + 1, k]), int(dp[i + 1, j + 1, k]))
-                           for i, j, k in bad[:6]]
+    _tables(case)
+    gp.full_cells(monkeypatch, _problem(case), t, _full_reference(case, custom), custom)
 
 
 @pytest.mark.parametrize("t", [None, 2, 8])
@@ -287,15 +221,7 @@ def test_pipeline_align_many(monkeypatch, case, mode):
 # ---------------------------------------------------------------- batches
 def _batch_inputs(cases):
     """codes / chars / seq_off / pair indices of a batch whose pair k is cases[k] (all under one table)."""
-    from globalign_amd import _native
-    cmat, _, _, o = _problem(cases[0])
-    tables = _native.CostTables(cmat, o)
-    seqs = [s for c in cases for s in _problem(c)[1:3]]
-    text = "".join(seqs).encode()
-    codes = np.frombuffer(b"".join(tables.codes(s) for s in seqs), dtype=np.uint8)
-    seq_off = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.int64)
-    P = len(cases)
-    return tables, codes, np.frombuffer(text, dtype=np.uint8), seq_off, np.arange(0, 2 * P, 2), np.arange(1, 2 * P, 2)
+    return gp.batch_inputs([_problem(c) for c in cases])
 
 
 @pytest.mark.parametrize("fam", [gc.G3, gc.W2], ids=["G", "W"])
