@@ -12,8 +12,6 @@
 //     the i==0 / j==0 tails :542-581 and the final reverse :584-586): ga_strings.h.
 #include <unistd.h>
 
-#include <condition_variable>
-#include <mutex>
 #include <thread>
 #include <chrono>
 #include <cstdio>
@@ -213,19 +211,21 @@ void guard_each(ga_ctx* c, F&& dev, P&& pin) {
     GA_D(qprof), GA_D(bt_codes), GA_D(bt_items), GA_D(bt_sub), GA_D(bt_gh), GA_D(bt_gv), GA_D(bt_ticket), GA_D(bt_out);
     GA_D(bt_scratch), GA_D(bt_witems), GA_D(bt_rng), GA_D(bt_ops), GA_D(bt_walk), GA_D(bt_tb), GA_D(bt_ritems);
     GA_D(bt_rstatus), GA_D(bt_rbase), GA_D(jlut), GA_D(bs_words), GA_D(bs_tb), GA_D(bs_witems), GA_D(bs_ticket);
-    GA_P(res_pin), GA_P(prog), GA_P(pipe_pin), GA_P(chain_tab), GA_P(chain_ctl), GA_P(chain_io), GA_P(rc_ops_pin);
-    GA_P(rc_ops_prog), GA_P(up_pin);
+#define GA_PP(x) pin(c->pipe.x, #x)
+    GA_P(res_pin), GA_P(prog), pin(c->pipe.pin, "pipe_pin"), GA_PP(chain_tab), GA_PP(chain_ctl), GA_PP(chain_io);
+    GA_P(rc_ops_pin), GA_P(rc_ops_prog), GA_P(up_pin);
 #undef GA_D
 #undef GA_P
+#undef GA_PP
     for (int s = 0; s < 6; s++) {
-        auto& sl = c->pipe[s];
+        auto& sl = c->pipe.slot[s];
         const std::string pre = "pipe" + std::to_string(s) + ".";
         fillbufs(sl.fb, pre);
         dev(sl.rng, pre + "rng"), dev(sl.ops, pre + "ops"), dev(sl.result, pre + "result");
         pin(sl.tab_pin, pre + "tab_pin");
     }
 }
-static_assert(sizeof(ga_ctx::pipe) / sizeof(ga_ctx::PipeSlot) == 6, "guard_each walks six pipeline slots");
+static_assert(sizeof(Pipeline::slot) / sizeof(PipeSlot) == 6, "guard_each walks six pipeline slots");
 
 void guard_attach(ga_ctx* c) {
     GuardCfg* g = &c->guard;
@@ -661,24 +661,6 @@ double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-// Walk state between slab walks (the C ABI's ga_walk_state without the padding rules).
-struct WalkStart {
-    int64_t i, j, D, h;  // j: global column
-    int L, first;
-};
-
-// Where a walk reads its words and table and leaves its levels / result, on which stream.
-struct WalkBufs {
-    const uint8_t* tb;
-    uint32_t* rng;
-    uint32_t* ops;
-    int* result;
-    hipStream_t stream;
-    hipEvent_t ev0, ev1;
-    const int* bnd_row = nullptr;  // the boundary triples (nullptr: the context's)
-    const int* bnd_col = nullptr;
-    unsigned* ops_prog = nullptr;  // WalkArgs::ops_prog (ops then in pinned host memory)
-};
 WalkBufs ctx_walk_bufs(ga_ctx* c) {
     return WalkBufs{c->fb.tb.as<uint8_t>(), c->rng.as<uint32_t>(), c->ops.as<uint32_t>(), c->result.as<int>(), c->stream,
                     c->wev[0], c->wev[1]};
@@ -727,8 +709,8 @@ ga::WalkArgs walk_args(ga_ctx* c, int64_t ntab, const WalkStart& st, int64_t r0,
     return w;
 }
 
-int run_walk(ga_ctx* c, const uint32_t* tab, int64_t ntab, const WalkStart& st, int64_t r0 = 0, int64_t mb = -1,
-             bool vhandoff = false, bool upload_tab = true, const WalkBufs* wbp = nullptr) {
+int run_walk(ga_ctx* c, const uint32_t* tab, int64_t ntab, const WalkStart& st, int64_t r0, int64_t mb, bool vhandoff,
+             bool upload_tab, const WalkBufs* wbp) {
     const WalkBufs wb = wbp ? *wbp : ctx_walk_bufs(c);
     if (upload_tab) HIPCHK(hipMemcpyAsync(wb.rng, tab, sizeof(uint32_t) * ntab, hipMemcpyHostToDevice, wb.stream));
     ga::WalkArgs w = walk_args(c, ntab, st, r0, mb, vhandoff, wb);
@@ -768,12 +750,6 @@ void advance_walk(WalkStart& st, const gastr::Columns& col, int64_t D1) {
     st.L = col.L;
     st.D = D1;
 }
-
-// Wait for the walk; decode the levels of dispatches [st.D, D_end) into alignment columns in walk
-// order starting at (st.i, st.j) (global columns).  Returns the end state through `st` and `reason`.
-int decode_segment(ga_ctx* c, const int* res, WalkStart& st, int& reason, const char* a_chr, const char* b_chr,
-                   char* oa, char* om, char* ob, int64_t cap, int64_t& len, const WalkBufs& wb, bool synced,
-                   const uint32_t* host_ops = nullptr);
 
 int walk_segment(ga_ctx* c, WalkStart& st, int& reason, const char* a_chr, const char* b_chr, char* oa, char* om,
                  char* ob, int64_t cap, int64_t& len, const WalkBufs* wbp = nullptr) {
@@ -815,11 +791,6 @@ int decode_segment(ga_ctx* c, const int* res, WalkStart& st, int& reason, const 
     if (len > cap) return fail(GA_E_ARG, "output capacity too small");
     return GA_OK;
 }
-
-// The end of a traceback: the MT state after its dispatches, the reference's tails, reversal.
-int conclude_walk(const RngTable& snaps, const WalkStart& st, int reason, uint32_t* mt_state, const char* a_chr,
-                  const char* b_chr, char* oa, char* om, char* ob, int64_t cap, int64_t len, int64_t* out_len,
-                  int32_t* tb_status);
 
 // Whole-problem traceback: one walk from (m, n), tails, reversal (dp_array_backward's output).
 int finish_walk(ga_ctx* c, const RngTable& snaps, uint32_t* mt_state, const char* a_chr, const char* b_chr,
@@ -1303,588 +1274,6 @@ int rc_align(ga_ctx* c, uint32_t* mt_state, const char* a_chr, const char* b_chr
     return streamed_walk_finish(c, R, wb, st0, t0, mt_state, a_chr, b_chr, oa, om, ob, cap, out_len, tb_status, cost_out);
 }
 
-// ---------------------------------------------------------------- pipelined repeated alignments
-// `count` alignments of the loaded pair, each from the random state the previous one left.  Three
-// slots of boundary arrays / traceback words / hand-off edges / walk buffers (every alignment runs
-// the whole path: boundary, fill, table, walk, strings); fills alternate between two fill
-// streams, so fill k+1 starts on the CUs fill k leaves idle (C3: one fill holds 196 of 256 CUs)
-// and on those its tail frees, and walk k runs on a third stream beside them.  Walks are serial
-// (alignment k's table slice starts where alignment k-1's dispatches ended); a host thread extends
-// the one continuous tie-break stream ahead of them.
-int pipe_setup(ga_ctx* c) {
-    if (!c->wstream) HIPCHK(hipStreamCreateWithPriority(&c->wstream, hipStreamNonBlocking, c->priority));
-    for (int f = 1; f < 4; f++)
-        if (!c->fstream[f]) HIPCHK(hipStreamCreateWithPriority(&c->fstream[f], hipStreamNonBlocking, c->priority));
-    if (c->walk_cus < 0) {
-        // The walk's LDS tile torus (128 KB) needs a CU no fill workgroup occupies.  With the walk's CUs
-        // masked out of the fill streams it never waits for one to drain, and two fills may share the
-        // other CUs (GA_PIPE_WALK_CUS, default 0: unmasked streams)
-        int wc = 0;
-        if (const char* e = c->xknob("GA_PIPE_WALK_CUS")) wc = std::max(0, std::min(8, atoi(e)));
-        c->walk_cus = wc;
-        if (wc > 0) {
-            const int nc = c->num_cu, words = (nc + 31) / 32;
-            std::vector<uint32_t> fm(words, 0u), wm(words, 0u);
-            for (int cu = 0; cu < nc; cu++) {
-                auto& mk = cu >= nc - wc ? wm : fm;
-                mk[cu >> 5] |= 1u << (cu & 31);
-            }
-            HIPCHK(hipExtStreamCreateWithCUMask(&c->mwstream, (uint32_t)words, wm.data()));
-            for (int f = 0; f < 4; f++) HIPCHK(hipExtStreamCreateWithCUMask(&c->mfstream[f], (uint32_t)words, fm.data()));
-        }
-    }
-    HIPCHK(c->pipe_pin.ensure(sizeof(int) * 8 * 6));
-    const int64_t per = c->m + c->n + 1;
-    for (int s = 0; s < c->pipe_slots; s++) {
-        auto& sl = c->pipe[s];
-        for (hipEvent_t* e : {&sl.fb.ev[0], &sl.fb.ev[1], &sl.w0, &sl.w1})
-            if (!*e) HIPCHK(hipEventCreate(e));
-        if (!sl.fdone) HIPCHK(hipEventCreateWithFlags(&sl.fdone, hipEventDisableTiming));
-        HIPCHK(sl.tab_pin.ensure(sizeof(uint32_t) * per));
-        HIPCHK(sl.rng.ensure(sizeof(uint32_t) * (per + 64)));  // + the walk's entry look-ahead (SLD)
-        HIPCHK(sl.ops.ensure(c->m + c->n + 1024));
-        HIPCHK(sl.result.ensure(sizeof(int) * 16));
-        const int64_t m = c->m, na = c->n_global;
-        HIPCHK(sl.fb.ensure_boundary(m, na));
-        if (c->custom) {  // host-supplied boundary triples: the boundary pass reads them from the slot
-            HIPCHK(hipMemcpyAsync(sl.fb.bnd_row.p, c->fb.bnd_row.p, sizeof(int) * 3 * (na + 1), hipMemcpyDeviceToDevice,
-                                  c->stream));
-            HIPCHK(hipMemcpyAsync(sl.fb.bnd_col.p, c->fb.bnd_col.p, sizeof(int) * 3 * (m + 1), hipMemcpyDeviceToDevice,
-                                  c->stream));
-        }
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return GA_OK;
-}
-
-// fill of an alignment into slot `slot` on stream `st`, then its cost inputs into pinned memory, then `fdone`
-int pipe_fill(ga_ctx* c, int slot, hipStream_t st, bool row = false, gaplan::FillPlan* plan_out = nullptr) {
-    auto& sl = c->pipe[slot];
-    Band bd;  // this slot's buffers, this stream, this lane geometry
-    bd.bufs = &sl.fb;
-    bd.stream = st;
-    bd.lane_td = row ? 0 : c->pipe_lane_td;
-    bd.lane_nwc = row ? 0 : c->pipe_lane_nwc;
-    if (int r = enqueue_fill(c, GA_FILL_TRACEBACK, bd, plan_out)) return r;
-    int* pin = c->pipe_pin.host<int>() + 8 * slot;
-    HIPCHK(hipMemcpyAsync(pin, sl.fb.out_last.p, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(pin + 4, sl.fb.meta.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(pin + 5, sl.fb.GHp.as<int>() + c->col0 + c->n, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(pin + 6, sl.fb.flags.as<unsigned>() + 1, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(sl.fdone, st));
-    return GA_OK;
-}
-
-// Per slot, pinned and coherent host memory for a pipelined walk's result words (256 B) and levels: the
-// walk writes them there, so the host reads them without a hipMemcpy (which would wait for a CU, and
-// the fills hold them all).  Returns the slot stride and the area's device address.
-int pipe_io(ga_ctx* c, int S, size_t* stride, uint8_t** dev) {
-    const size_t ops_bytes = (((size_t)(c->m + c->n + 1024) + 255) / 256) * 256, io_stride = 256 + ops_bytes;
-    HIPCHK(c->chain_io.ensure(io_stride * S));
-    *stride = io_stride;
-    *dev = c->chain_io.dev<uint8_t>();
-    return GA_OK;
-}
-
-// align_many with its walks chained in one walk_chain_kernel launch.  Each walk used to
-// start after a host round trip (walk k's end seen by the host, its dispatch count read, walk k+1's
-// table slice copied and its kernel launched: 45-55 us at C2 / C5, 0.1-0.2 ms at C3), and by then a
-// queued fill workgroup could have taken the CU the walk had left (C3: a ~1 ms gap every fourth
-// walk).  Now the walks keep their CU; walk k+1 starts when walk k ends, reading the tie-break stream
-// from G_{k+1}, which the kernel sums itself, straight out of pinned host memory that the producer
-// thread fills; the host only says which fills have ended and decodes each alignment's strings.
-int align_chain(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, const char* b_chr, char* oa, char* om,
-                char* ob, int64_t cap, int64_t* out_len, int32_t* tb_status, int64_t* cost_out, double t0) {
-    const int64_t m = c->m, n = c->n, per = m + n + 1;
-    const int F = c->pipe_fills, S = c->pipe_slots;
-    if (S > ga::WALK_CHAIN_SLOTS) return fail(GA_E_ARG, "too many pipeline slots for the walk chain");
-    hipStream_t fs[4] = {c->stream, c->fstream[1], c->fstream[2], c->fstream[3]};
-    if (!c->cwstream) {
-        int lo = 0, hi = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIPCHK(hipStreamCreateWithPriority(&c->cwstream, hipStreamNonBlocking, lo));
-    }
-    hipStream_t ws = c->cwstream;
-    const int64_t need = (int64_t)count * per;
-    HIPCHK(c->chain_tab.ensure(sizeof(uint32_t) * need));
-    HIPCHK(c->chain_ctl.ensure(64));
-    size_t io_stride = 0;
-    uint8_t* io_dev = nullptr;
-    if (int r = pipe_io(c, S, &io_stride, &io_dev)) return r;
-    uint8_t* const io_host = c->chain_io.host<uint8_t>();
-    auto res_host = [&](int s) { return reinterpret_cast<int*>(io_host + io_stride * s); };
-    auto ops_host = [&](int s) { return reinterpret_cast<uint32_t*>(io_host + io_stride * s + 256); };
-    uint32_t* const chain_tab = c->chain_tab.host<uint32_t>();
-    unsigned* ctl = c->chain_ctl.host<unsigned>();
-    long long* tab_ready = reinterpret_cast<long long*>(ctl + 4);
-    std::memset(ctl, 0, 64);
-    const uint32_t* tab_dev = c->chain_tab.dev<uint32_t>();
-    unsigned* ctl_dev = c->chain_ctl.dev<unsigned>();
-
-    // the tie-break stream: a host thread extends it ahead of the walks, into pinned memory; started
-    // before the fills are enqueued (C2 / C5: the first walk waited 2.1 / 4.0 ms for its entries)
-    RngTable& R = c->many_rng;
-    R.start(mt_state);
-    R.tab.reserve((size_t)need);
-    R.step_end.reserve((size_t)need + 4);
-    R.acc.reserve((size_t)18 * need + 8);
-    std::mutex mu;
-    std::condition_variable cv;
-    int64_t ready = 0;  // entries built (under mu)
-    // walk k+1 may start the moment walk k ends, anywhere in [G_k + max(m, n), G_k + m + n]: the
-    // entries are kept two alignments' worth ahead of the last walk known to have ended
-    int64_t target = std::min<int64_t>(need, 3 * per);
-    bool quit = false;
-    double rng_ms = 0.0;
-    std::thread producer([&] {
-        for (;;) {
-            int64_t want, from;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return quit || target > ready; });
-                if (quit) return;
-                want = std::min<int64_t>(target, need);
-                from = ready;
-                if (want <= ready) {
-                    target = ready;
-                    continue;
-                }
-            }
-            const double t1 = now_ms();
-            // in pieces of half an alignment, each published as soon as it is written: the first walk
-            // waits for per entries, not for the three alignments' worth the producer starts with
-            for (int64_t to = from; to < want;) {
-                const int64_t nx = std::min(want, to + std::max<int64_t>(per / 2, 4096));
-                R.extend(nx);
-                std::memcpy(chain_tab + to, R.tab.data() + to, sizeof(uint32_t) * (nx - to));
-                __atomic_store_n(tab_ready, (long long)nx, __ATOMIC_RELEASE);
-                to = nx;
-            }
-            rng_ms += now_ms() - t1;
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                ready = want;
-            }
-            cv.notify_all();
-        }
-    });
-    auto stop = [&](int rc) {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            quit = true;
-        }
-        cv.notify_all();
-        producer.join();
-        if (rc != GA_OK) __atomic_store_n(ctl + 2, 1u, __ATOMIC_RELEASE);  // the chain exits at its next wait
-        (void)hipStreamSynchronize(ws);
-        c->guard.in_chain = false;
-        if (rc != GA_OK)
-            for (int f = 0; f < F; f++) (void)hipStreamSynchronize(fs[f]);
-        return rc;
-    };
-    int enqueued = 0, signalled = 0;
-    auto launch_all = [&]() -> int {
-        // fill 0 first (it fixes the fill geometry and so the size of every slot's traceback words), then
-        // the walks' launch, so that its workgroup has a CU before the other fills take them all, then
-        // fills 1 .. S-1; fill j goes into slot j % S on fill stream j % F (each computes its own boundary)
-        gaplan::FillPlan pl;
-        if (int r = pipe_fill(c, 0, fs[0], false, &pl)) return r;
-        enqueued++;
-        // every slot's fill buffers at their final size now: a reallocation's hipFree while the chain runs
-        // would wait for the chain, which waits for the host
-        const size_t tb_bytes = (size_t)pl.nstripes * pl.T * pl.TC * 1024;
-        const size_t hand_bytes = sizeof(int2) * (size_t)pl.nslabs * (m + 1);
-        for (int s = 1; s < S; s++) {
-            auto& sl = c->pipe[s];
-            HIPCHK(sl.fb.tb.ensure(tb_bytes));
-            HIPCHK(sl.fb.hand.ensure(hand_bytes));
-            HIPCHK(sl.fb.flags.ensure(sizeof(unsigned) * 16));
-            HIPCHK(sl.fb.out_last.ensure(sizeof(int) * 4));
-        }
-        ga::WalkChainArgs A{};
-        for (int s = 0; s < S; s++) {
-            auto& sl = c->pipe[s];
-            const WalkBufs wb{sl.fb.tb.as<uint8_t>(), nullptr, sl.ops.as<uint32_t>(), sl.result.as<int>(),
-                              ws, nullptr, nullptr, sl.fb.bnd_row.as<int>(), sl.fb.bnd_col.as<int>()};
-            A.w[s] = walk_args(c, per, WalkStart{m, n, 0, 0, 0, 1}, 0, -1, false, wb);
-            A.w[s].result = reinterpret_cast<int*>(static_cast<uint8_t*>(io_dev) + io_stride * s);
-            A.w[s].ops = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(io_dev) + io_stride * s + 256);
-        }
-        A.tab = tab_dev;
-        A.ctl = ctl_dev;
-        A.tab_ready = reinterpret_cast<const long long*>(ctl_dev + 4);
-        A.per = per;
-        A.wait_limit = 100ull * 1000 * 1000 * 60;  // 60 s of s_memrealtime (100 MHz)
-        A.count = count;
-        A.S = S;
-        HIPCHK(hipEventRecord(c->pipe[0].w0, ws));
-        c->guard.in_chain = true;  // until stop(): guard mode must not wait for the device from here on
-        ga::launch_walk_chain(ws, A);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(c->pipe[0].w1, ws));
-        for (int k = 1; k < std::min(count, S); k++) {
-            if (int r = pipe_fill(c, k, fs[k % F])) return r;
-            enqueued++;
-        }
-        return GA_OK;
-    };
-    if (int r = launch_all()) return stop(r);
-    FILE* trace = nullptr;
-    if (const char* tp = c->knob("GA_PIPE_TRACE")) trace = fopen(tp, "a");
-    const double h0 = now_ms();
-    int64_t G = 0;
-    float fill_sum = 0.f, walk_sum = 0.f;
-    int rc = GA_OK;
-    for (int k = 0; k < count && rc == GA_OK; k++) {
-        auto& sl = c->pipe[k % S];
-        // wait for walk k; meanwhile tell the chain which fills have ended (in order, enqueued ones only:
-        // a slot's event still holds the previous fill of that slot until the next is enqueued)
-        for (;;) {
-            while (signalled < enqueued && hipEventQuery(c->pipe[signalled % S].fdone) == hipSuccess)
-                __atomic_store_n(ctl, (unsigned)++signalled, __ATOMIC_RELEASE);
-            if ((int)__atomic_load_n(ctl + 1, __ATOMIC_ACQUIRE) > k) break;
-            if (__atomic_load_n(ctl + 3, __ATOMIC_ACQUIRE)) {
-                rc = fail(GA_E_TIMEOUT, "chained walk waited too long for its fill or tie-break entries");
-                break;
-            }
-            std::this_thread::sleep_for(std::chrono::microseconds(20));
-        }
-        if (rc != GA_OK) break;
-        int res[16];
-        std::memcpy(res, res_host(k % S), sizeof(res));
-        const int64_t Dk = res[0];
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            target = std::max(target, G + Dk + 2 * per + per / 8);
-        }
-        cv.notify_all();
-        const int* pin = c->pipe_pin.host<int>() + 8 * (k % S);
-        if (pin[6]) {
-            rc = fail(GA_E_TIMEOUT, "fill kernel hand-off wait timed out");
-            break;
-        }
-        cost_out[k] = (int64_t)pin[0] + pin[4] + pin[5];
-        float f = 0.f;
-        if (hipEventElapsedTime(&f, sl.fb.ev[0], sl.fb.ev[1]) == hipSuccess) fill_sum += f;
-        walk_sum += res[8] / 1.0e5f;  // the walker's own time (s_memrealtime ticks, 100 MHz)
-        if (trace)
-            fprintf(trace, "{\"k\": %d, \"chain\": 1, \"fill_ms\": %.3f, \"walk_ms\": %.3f, \"walk_done_host\": %.3f, "
-                    "\"D\": %lld, \"tile_wait_us\": %.2f, \"tile_loads\": %d, \"chain_wait_us\": %.2f, "
-                    "\"polls_fill\": %d, \"polls_tab\": %d}\n", k, f, res[8] / 1.0e5,
-                    now_ms() - h0, (long long)Dk, res[6] / 100.0, res[11], res[12] / 100.0, res[13], res[14]);
-        // fill k+S into slot k's buffers (walk k has read them)
-        if (k + S < count) {
-            if (int r = pipe_fill(c, k % S, fs[(k + S) % F])) {
-                rc = r;
-                break;
-            }
-            enqueued++;
-        }
-        // alignment k's strings, while walk k+1 and the fills run
-        const WalkBufs wb{sl.fb.tb.as<uint8_t>(), nullptr, sl.ops.as<uint32_t>(), sl.result.as<int>(),
-                          ws, nullptr, nullptr, sl.fb.bnd_row.as<int>(), sl.fb.bnd_col.as<int>()};
-        WalkStart st{m, n, 0, 0, 0, 1};
-        int reason = 0;
-        int64_t len = 0;
-        char* a_k = oa + (size_t)k * cap;
-        char* m_k = om + (size_t)k * cap;
-        char* b_k = ob + (size_t)k * cap;
-        if (int r = decode_segment(c, res, st, reason, a_chr, b_chr, a_k, m_k, b_k, cap, len, wb, true,
-                                   ops_host(k % S))) {
-            rc = r;
-            break;
-        }
-        if (int r = conclude_walk(R, st, reason, nullptr, a_chr, b_chr, a_k, m_k, b_k, cap, len, &out_len[k],
-                                  &tb_status[k])) {
-            rc = r;
-            break;
-        }
-        G += st.D;
-    }
-    if (trace) fclose(trace);
-    if (int r = stop(rc)) return r;
-    state_after(R, G, mt_state);  // the state the last alignment leaves (random.getstate() layout)
-    c->fill_ms = fill_sum / count;
-    c->walk_ms = walk_sum / count;
-    c->rng_ms = (float)(rng_ms / count);
-    c->call_ms = (float)(now_ms() - t0);
-    c->filled_tb = false;
-    return GA_OK;
-}
-
-int align_many(ga_ctx* c, int count, uint32_t* mt_state, const char* a_chr, const char* b_chr, char* oa, char* om,
-               char* ob, int64_t cap, int64_t* out_len, int32_t* tb_status, int64_t* cost_out) {
-    const double t0 = now_ms();
-    {
-        // Fill kernel and fills in flight.  A row-scan traceback fill of C3 holds 196 CUs
-        // at two waves per SIMD and is issue bound there: a second fill in flight only fills the CUs it
-        // leaves idle (10.4 ms per alignment in steady state), and co-resident fills gain nothing.  The
-        // lane-skewed traceback fill at 4 columns per lane runs 391 stripes in 98 one-wave-per-SIMD
-        // workgroups: a narrow, latency-bound fill (26 ms alone), three of which share the chip
-        // (8.65 ms per alignment; tools/exp/pipe_lane2.sh).  So one-byte words of long rows (K <= 32,
-        // an int8 profile) take lane fills; the rest three row-scan fills.  GA_PIPE_MODE=row|lane
-        // and GA_PIPE_FILLS (2..4) override.
-        const char* pm = c->knob("GA_PIPE_MODE");
-        bool lane = c->CB == 1 && c->qbytes == 1 && c->K <= 32 && c->m >= 32768 && c->n >= 4 * 4 * 64 * 64 &&
-                    c->pk.diag_req != 1 && c->pk.diag_req != 2;
-        if (pm && !strcmp(pm, "row")) lane = false;
-        if (pm && !strcmp(pm, "lane")) lane = c->qbytes == 1 && c->K <= 32;
-        c->pipe_lane_td = lane ? (c->CB == 1 ? 4 : 2) : 0;
-        c->pipe_lane_nwc = lane ? 4 : 0;
-        // Lane fills: four in flight when the process has the hardware queues for them (the fill streams
-        // and the walk stream share a priority's pool of GPU_MAX_HW_QUEUES queues; two streams on one
-        // in-order queue serialise): C3 steady state 8.34 -> 7.81 ms per alignment, walk-bound
-        // (tools/exp/pipe_queues.sh); three with HIP's default of four queues
-        const int queues = c->hw_queues;
-        // row-scan fills: three in flight (four streams with the walk's: HIP's default pool holds them);
-        // with the faster walk C5 is no longer walk-bound (1.80 -> 1.51 ms per alignment), C2 unchanged
-        int F = lane ? (queues >= 5 ? 4 : 3) : 3;
-        if (const char* e = c->knob("GA_PIPE_FILLS")) F = std::max(2, std::min(4, atoi(e)));
-        c->pipe_fills = F;
-        // slots: fill k + S reuses walk k's buffers, so the walk chain allows one alignment per
-        // (walk + fill) / S; GA_PIPE_SLOTS raises S above F + 1 (up to 6)
-        int S = F + 1;
-        if (const char* e = c->knob("GA_PIPE_SLOTS")) S = std::max(F + 1, std::min(6, atoi(e)));
-        c->pipe_slots = S;
-    }
-    if (int r = pipe_setup(c)) return r;
-    {
-        // the walks chained in one launch (align_chain) behind row-scan fills: C2 0.908 -> 0.823 ms per
-        // alignment, C5 1.522 -> 1.507.  Not behind the lane fills: C3 8.96-9.05 -> 9.47-9.55, its four
-        // narrow fills (392 workgroups for 256 CUs) running 27.4 -> 29.5 ms each beside a walk that never
-        // gives its CU back (tools/exp/chain_ab.sh).  Opt-in (GA_PIPE_CHAIN=1): the persistent chain polls
-        // host-written words, so a device-synchronising call another thread of the process makes while it
-        // runs (hipFree, hipDeviceSynchronize, a torch allocator release) would wait on it until its 60 s
-        // bound; per-launch walks have no such hazard and cost C2 / C5 ~1-10 % more per alignment.
-        const char* ch = c->knob("GA_PIPE_CHAIN");
-        const bool fits = (int64_t)count * (c->m + c->n + 1) <= ((int64_t)256 << 20);  // 1 GB of entries
-        const bool on = ch != nullptr && atoi(ch) != 0;
-        if (on && fits && c->walk_cus == 0 && !c->knob("GA_PIPE_FILL_PRIO") && !c->xknob("GA_PIPE_ROW_FIRST"))
-            return align_chain(c, count, mt_state, a_chr, b_chr, oa, om, ob, cap, out_len, tb_status, cost_out, t0);
-    }
-    const int64_t m = c->m, n = c->n, per = m + n + 1;
-    const int F = c->pipe_fills, S = c->pipe_slots;
-    hipStream_t fs[4] = {c->stream, c->fstream[1], c->fstream[2], c->fstream[3]};
-    hipStream_t ws = c->wstream;
-    if (c->walk_cus > 0) {
-        for (int f = 0; f < 4; f++) fs[f] = c->mfstream[f];
-        ws = c->mwstream;
-    } else if (const char* fp = c->knob("GA_PIPE_FILL_PRIO"); fp && !strcmp(fp, "normal")) {
-        for (int f = 0; f < 4; f++) {
-            if (!c->nfstream[f]) HIPCHK(hipStreamCreateWithPriority(&c->nfstream[f], hipStreamNonBlocking, 0));
-            fs[f] = c->nfstream[f];
-        }
-    }
-    // GA_PIPE_TRACE=<file>: per alignment, GPU times (ms from the first fill's enqueue) of fill and walk
-    // start / end and host times of the walk launches (a diagnostic of what bounds the pipeline)
-    struct PipeTrace {  // closed on every return path
-        FILE* f = nullptr;
-        hipEvent_t origin = nullptr;
-        ~PipeTrace() {
-            if (f) fclose(f);
-            if (origin) (void)hipEventDestroy(origin);
-        }
-    } tr;
-    if (const char* tp = c->knob("GA_PIPE_TRACE"))
-        if (hipEventCreate(&tr.origin) == hipSuccess && hipEventRecord(tr.origin, fs[0]) == hipSuccess)
-            tr.f = fopen(tp, "a");
-    FILE* const trace = tr.f;
-    const hipEvent_t origin = tr.origin;
-    const double h0 = now_ms();
-    double walk_launch_host = 0.0;
-    // experiment (GA_PIPE_ROW_FIRST=r): the first r fills through the row scan (shorter latency alone)
-    int row_first = 0;
-    if (const char* e = c->xknob("GA_PIPE_ROW_FIRST")) row_first = atoi(e);
-    // fill j into slot j % S on fill stream j % F; each computes its own boundary.  Every fill of the
-    // pipeline computes the same arrays (the same pair, boundary and words), so walk k takes whichever
-    // pending slot's fill ended first, not slot k % S: in the ramp the third of four fills started at
-    // once ends ~3 ms after the fourth and ~3 ms after the third walk wanted it (GA_PIPE_SLOT_ORDER=fixed
-    // keeps slot k % S)
-    const bool any_order = [c] {
-        const char* e = c->knob("GA_PIPE_SLOT_ORDER");
-        return !(e && !strcmp(e, "fixed"));
-    }();
-    size_t io_stride = 0;
-    uint8_t* io_dev = nullptr;
-    if (int r = pipe_io(c, S, &io_stride, &io_dev)) return r;
-    // slot s's walk writes its result words and levels to pinned memory (pipe_io; GA_PIPE_PINNED_IO=0:
-    // to the slot's device buffers, read back with hipMemcpy)
-    const bool pinned_io = [c] {
-        const char* e = c->knob("GA_PIPE_PINNED_IO");
-        return !(e && atoi(e) == 0);
-    }();
-    auto walk_bufs = [&](int s) {
-        auto& sl = c->pipe[s];
-        return WalkBufs{sl.fb.tb.as<uint8_t>(), sl.rng.as<uint32_t>(),
-                        pinned_io ? reinterpret_cast<uint32_t*>(io_dev + io_stride * s + 256) : sl.ops.as<uint32_t>(),
-                        pinned_io ? reinterpret_cast<int*>(io_dev + io_stride * s) : sl.result.as<int>(), ws, sl.w0,
-                        sl.w1, sl.fb.bnd_row.as<int>(), sl.fb.bnd_col.as<int>()};
-    };
-    std::vector<int> pending;  // slots holding an enqueued fill no walk has taken, in enqueue order
-    std::vector<int> walk_slot((size_t)count, -1);
-    int fills_enqueued = 0;
-    for (int k = 0; k < std::min(count, S); k++) {
-        if (int r = pipe_fill(c, k, fs[k % F], k < row_first)) return r;
-        pending.push_back(k);
-        fills_enqueued++;
-    }
-    // the tie-break table: one continuous stream, extended by a host thread ahead of the walks (its
-    // vectors are reserved up front: the walks read earlier entries while later ones are written)
-    RngTable& R = c->many_rng;
-    R.start(mt_state);
-    R.tab.reserve((size_t)count * per);
-    R.step_end.reserve((size_t)count * per + 4);
-    R.acc.reserve((size_t)18 * count * per + 8);
-    const uint32_t* tabp = R.tab.data();  // stable: the capacity is reserved
-    std::mutex mu;
-    std::condition_variable cv;
-    int64_t ready = 0;         // entries available to the walks (under mu)
-    // entries the producer builds up to (under mu): the first three alignments' worth while the first
-    // fills run (each alignment takes about (m + n) / 1.6 dispatches), then kept ahead of the walks
-    int64_t target = std::min<int64_t>((int64_t)count * per, 3 * per);
-    bool quit = false;
-    double rng_ms = 0.0;
-    std::thread producer([&] {
-        for (;;) {
-            int64_t want;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return quit || target > ready; });
-                if (quit) return;
-                want = std::min<int64_t>(target, (int64_t)count * per);
-                if (want <= ready) {
-                    target = ready;  // nothing more can be built
-                    continue;
-                }
-            }
-            const double t1 = now_ms();
-            R.extend(want);
-            rng_ms += now_ms() - t1;
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                ready = want;
-            }
-            cv.notify_all();
-        }
-    });
-    // walk k over its table slice [G, G + per), after fill k, on the walk stream
-    auto start_walk = [&](int k, int64_t G) -> int {
-        // the slot: the first pending one whose fill has ended; while all are still running, the host
-        // waits for the first to end (the oldest is not always first: in the ramp four fills share the chip)
-        size_t pick = 0;
-        for (bool found = !any_order; !found;) {
-            for (size_t q = 0; q < pending.size() && !found; q++)
-                if (hipEventQuery(c->pipe[pending[q]].fdone) == hipSuccess) {
-                    pick = q;
-                    found = true;
-                }
-            if (!found) std::this_thread::sleep_for(std::chrono::microseconds(20));
-        }
-        walk_slot[k] = pending[pick];
-        pending.erase(pending.begin() + (long)pick);
-        auto& sl = c->pipe[walk_slot[k]];
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return ready >= G + per; });
-        }
-        HIPCHK(hipStreamWaitEvent(ws, sl.fdone, 0));
-        std::memcpy(sl.tab_pin.p, tabp + G, sizeof(uint32_t) * per);
-        const WalkBufs wb = walk_bufs(walk_slot[k]);
-        return run_walk(c, sl.tab_pin.host<uint32_t>(), per, WalkStart{m, n, 0, 0, 0, 1}, 0, -1, false, true, &wb);
-    };
-    int rc = start_walk(0, 0);
-    walk_launch_host = now_ms() - h0;
-    int64_t G = 0;  // global dispatches consumed by the alignments before k
-    int64_t Dmax = 0;
-    float fill_sum = 0.f, walk_sum = 0.f;
-    for (int k = 0; k < count && rc == GA_OK; k++) {
-        auto& sl = c->pipe[walk_slot[k]];
-        const WalkBufs wb = walk_bufs(walk_slot[k]);
-        const uint8_t* io_pin = c->chain_io.host<uint8_t>() + io_stride * walk_slot[k];
-        const int* res_pin = reinterpret_cast<const int*>(io_pin);
-        const uint32_t* ops_pin = reinterpret_cast<const uint32_t*>(io_pin + 256);
-        auto step = [&]() -> int {
-            // walk k done: its dispatch count fixes where walk k+1's table slice starts
-            HIPCHK(hipEventSynchronize(sl.w1));
-            int res[16];
-            if (pinned_io) std::memcpy(res, res_pin, sizeof(res));
-            else HIPCHK(hipMemcpy(res, sl.result.p, sizeof(int) * 16, hipMemcpyDeviceToHost));
-            const int64_t Dk = res[0];
-            Dmax = std::max(Dmax, Dk);
-            if (trace) {
-                float t[4] = {0.f, 0.f, 0.f, 0.f};
-                hipEvent_t evs[4] = {sl.fb.ev[0], sl.fb.ev[1], sl.w0, sl.w1};
-                for (int q = 0; q < 4; q++) (void)hipEventElapsedTime(&t[q], origin, evs[q]);
-                // the walker's own accounting (walk_kernel result[4..11]; s_memrealtime ticks at 100 MHz)
-                fprintf(trace, "{\"k\": %d, \"fill0\": %.3f, \"fill1\": %.3f, \"walk0\": %.3f, \"walk1\": %.3f, "
-                        "\"walk_launch_host\": %.3f, \"walk_done_host\": %.3f, \"D\": %lld, \"tile_wait_us\": %.2f, "
-                        "\"walker_us\": %.2f, \"tile_loads\": %d, \"load_us_per_tile\": %.3f}\n", k, t[0], t[1], t[2],
-                        t[3], walk_launch_host, now_ms() - h0, (long long)Dk, res[6] / 100.0, res[8] / 100.0, res[11],
-                        res[11] > 0 ? res[10] / 100.0 / res[11] : 0.0);
-            }
-            {
-                // keep the producer an alignment's worth (and some) ahead of the next walk
-                std::lock_guard<std::mutex> lk(mu);
-                target = std::max(target, G + Dk + per + Dmax + Dmax / 8);
-            }
-            cv.notify_all();
-            if (k + 1 < count) {
-                if (int r = start_walk(k + 1, G + Dk)) return r;
-                walk_launch_host = now_ms() - h0;
-            }
-            // alignment k's cost (fill k finished before walk k started) and walk time, before slot k's
-            // pinned words and events are reused
-            const int* pin = c->pipe_pin.host<int>() + 8 * walk_slot[k];
-            if (pin[6]) return fail(GA_E_TIMEOUT, "fill kernel hand-off wait timed out");
-            cost_out[k] = (int64_t)pin[0] + pin[4] + pin[5];
-            float f = 0.f;
-            if (hipEventElapsedTime(&f, sl.fb.ev[0], sl.fb.ev[1]) == hipSuccess) fill_sum += f;
-            float wms = 0.f;
-            if (hipEventElapsedTime(&wms, sl.w0, sl.w1) == hipSuccess) walk_sum += wms;
-            // the next fill into walk k's slot (walk k has read it), on its stream after the fill F before
-            if (fills_enqueued < count) {
-                if (int r = pipe_fill(c, walk_slot[k], fs[fills_enqueued % F])) return r;
-                pending.push_back(walk_slot[k]);
-                fills_enqueued++;
-            }
-            // alignment k's strings, while walk k+1 and the fills run
-            WalkStart st{m, n, 0, 0, 0, 1};
-            int reason = 0;
-            int64_t len = 0;
-            char* a_k = oa + (size_t)k * cap;
-            char* m_k = om + (size_t)k * cap;
-            char* b_k = ob + (size_t)k * cap;
-            if (int r = decode_segment(c, res, st, reason, a_chr, b_chr, a_k, m_k, b_k, cap, len, wb, true,
-                                       pinned_io ? ops_pin : nullptr))
-                return r;
-            if (int r = conclude_walk(R, st, reason, nullptr, a_chr, b_chr, a_k, m_k, b_k, cap, len, &out_len[k],
-                                      &tb_status[k]))
-                return r;
-            G += st.D;
-            return GA_OK;
-        };
-        rc = step();
-    }
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        quit = true;
-    }
-    cv.notify_all();
-    producer.join();
-    if (rc != GA_OK) {
-        for (int f = 0; f < F; f++) (void)hipStreamSynchronize(fs[f]);
-        (void)hipStreamSynchronize(ws);
-        return rc;
-    }
-    state_after(R, G, mt_state);  // the state the last alignment leaves (random.getstate() layout)
-    c->fill_ms = fill_sum / count;
-    c->walk_ms = walk_sum / count;
-    c->rng_ms = (float)(rng_ms / count);
-    c->call_ms = (float)(now_ms() - t0);
-    c->filled_tb = false;  // ctx->tb does not hold the last fill's words
-    return GA_OK;
-}
-
 }  // namespace gahost
 
 // ====================================================================== C ABI
@@ -2062,23 +1451,11 @@ void ga_ctx_destroy(ga_ctx* c) {
     if (c->ev_fill) (void)hipEventDestroy(c->ev_fill);
     if (c->ev_res) (void)hipEventDestroy(c->ev_res);
     if (c->ustream) (void)hipStreamDestroy(c->ustream);
-    for (auto& sl : c->pipe)
-        for (hipEvent_t e : {sl.fb.ev[0], sl.fb.ev[1], sl.fdone, sl.w0, sl.w1})
-            if (e) (void)hipEventDestroy(e);
-    if (c->wstream) (void)hipStreamDestroy(c->wstream);
-    if (c->cwstream) (void)hipStreamDestroy(c->cwstream);
-    if (c->mwstream) (void)hipStreamDestroy(c->mwstream);
-    for (hipStream_t ms : c->mfstream)
-        if (ms) (void)hipStreamDestroy(ms);
-    for (hipStream_t ns : c->nfstream)
-        if (ns) (void)hipStreamDestroy(ns);
-    for (int f = 1; f < 4; f++)
-        if (c->fstream[f]) (void)hipStreamDestroy(c->fstream[f]);
     for (hipEvent_t e : {c->fb.ev[0], c->fb.ev[1], c->wev[0], c->wev[1], c->rev[0], c->rev[1]})
         if (e) (void)hipEventDestroy(e);
     if (c->ev_dep) (void)hipEventDestroy(c->ev_dep);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;  // the device and pinned buffers free themselves (DevBuf, PinBuf)
+    delete c;  // the device and pinned buffers free themselves (DevBuf, PinBuf), the pipeline its streams and events
 }
 
 // ga_problem_set and the other entries that run kernels and wait for them: the exported definitions, which end each
@@ -2178,39 +1555,6 @@ static int problem_align_impl(ga_ctx* c, uint32_t* mt_state, const char* a_chr, 
     const int rc = finish_walk(c, R, mt_state, a_chr, b_chr, oa, om, ob, cap, out_len, tb_status);
     c->call_ms = (float)(now_ms() - t0);
     return rc;
-}
-
-static int problem_align_many_impl(ga_ctx* c, int32_t count, uint32_t* mt_state, const char* a_chr, const char* b_chr,
-                                   char* oa, char* om, char* ob, int64_t cap, int64_t* out_len, int32_t* tb_status,
-                                   int64_t* cost_out) {
-    if (int r = check_ctx(c)) return r;
-    if (c->slab) return fail(GA_E_STATE, "slab contexts use ga_slab_fill_launch");
-    if (count < 1) return fail(GA_E_ARG, "count must be >= 1");
-    if (!mt_state || !a_chr || !b_chr || !oa || !om || !ob || !out_len || !tb_status || !cost_out)
-        return fail(GA_E_ARG, "null argument");
-    if (!c->loaded) return fail(GA_E_STATE, "no problem loaded");
-    // up to five slots of traceback words (four lane fills in flight + the walked one; GA_PIPE_SLOTS may
-    // ask for more): beyond 160 GB of them, one alignment after another
-    const bool fits = (int64_t)5 * ((c->n + 63) / 64) * 64 * c->m * c->CB <= ((int64_t)160 << 30);
-    if (count == 1 || band_rows(c) > 0 || !fits) {
-        // one alignment, or banded tracebacks (whose band fills hold every CU): one after another
-        const double t0 = now_ms();
-        float fs = 0.f, ws = 0.f, rs = 0.f;
-        for (int k = 0; k < count; k++) {
-            if (int r = ga_problem_align(c, mt_state, a_chr, b_chr, oa + (size_t)k * cap, om + (size_t)k * cap,
-                                         ob + (size_t)k * cap, cap, &out_len[k], &tb_status[k], &cost_out[k]))
-                return r;
-            fs += c->fill_ms;
-            ws += c->walk_ms;
-            rs += c->rng_ms;
-        }
-        c->fill_ms = fs / count;
-        c->walk_ms = ws / count;
-        c->rng_ms = rs / count;
-        c->call_ms = (float)(now_ms() - t0);
-        return GA_OK;
-    }
-    return align_many(c, count, mt_state, a_chr, b_chr, oa, om, ob, cap, out_len, tb_status, cost_out);
 }
 
 // ---------------------------------------------------------------- slabs
@@ -2605,7 +1949,7 @@ int ga_problem_align(ga_ctx* c, uint32_t* mt_state, const char* a_chr, const cha
 int ga_problem_align_many(ga_ctx* c, int32_t count, uint32_t* mt_state, const char* a_chr, const char* b_chr,
                           char* oa, char* om, char* ob, int64_t cap, int64_t* out_len, int32_t* tb_status,
                           int64_t* cost_out) {
-    return guard_end(c, problem_align_many_impl(c, count, mt_state, a_chr, b_chr, oa, om, ob, cap, out_len, tb_status,
+    return guard_end(c, problem_align_many(c, count, mt_state, a_chr, b_chr, oa, om, ob, cap, out_len, tb_status,
                                                 cost_out));
 }
 

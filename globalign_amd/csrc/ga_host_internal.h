@@ -1,6 +1,7 @@
-// ga_host_internal.h -- what the host engine's two translation units share (ga_host.cpp: contexts, the single-pair
-// paths, slabs; ga_batch_host.cpp: the batched calls).  Internal: not installed, and include/globalign_amd.h does not
-// mention it.  The shared helpers live in namespace gahost and are defined in ga_host.cpp.
+// ga_host_internal.h -- what the host engine's three translation units share (ga_host.cpp: contexts, the single-pair
+// paths, slabs; ga_batch_host.cpp: the batched calls; ga_pipe_host.cpp: the repeated-alignment pipeline).  Internal:
+// not installed, and include/globalign_amd.h does not mention it.  The shared helpers live in namespace gahost and,
+// but for the pipeline's, are defined in ga_host.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +14,7 @@
 #include "../../include/globalign_amd.h"
 #include "ga_device.h"
 #include "ga_guard.h"
+#include "ga_pipe.h"
 #include "ga_plan.h"
 #include "ga_rng.h"
 
@@ -146,6 +148,48 @@ struct FillBufs {
     }
 };
 
+
+// Pipelined repeated alignments (ga_problem_align_many, ga_pipe_host.cpp): what the context keeps
+// between calls.  A slot holds one alignment's boundary arrays, traceback words, walk buffers and events; fills run
+// on streams of their own, the walk on another beside them.
+struct PipeSlot {
+    FillBufs fb;  // each pipelined alignment computes its own boundary (make_dp_array) into its slot
+    DevBuf rng, ops, result;
+    hipEvent_t fdone = nullptr, w0 = nullptr, w1 = nullptr;
+    PinBuf tab_pin;  // pinned staging of the walk's table slice
+};
+struct Pipeline {
+    PipeSlot slot[gapipe::kMaxSlots];
+    hipStream_t wstream = nullptr, fstream[4] = {nullptr, nullptr, nullptr, nullptr};  // [0] unused: ctx->stream
+    // CU-masked pipeline streams (GA_PIPE_WALK_CUS > 0): the walk keeps CUs of its own, the fills the rest
+    hipStream_t mwstream = nullptr, mfstream[4] = {nullptr, nullptr, nullptr, nullptr};
+    // default-priority pipeline fill streams (GA_PIPE_FILL_PRIO=normal): four fills on their own pool of
+    // hardware queues, the walk stream keeping the greatest priority (it takes the next free CU)
+    hipStream_t nfstream[4] = {nullptr, nullptr, nullptr, nullptr};
+    int walk_cus = -1;  // CUs reserved for the walk (0: no masks; -1: not yet set up)
+    PinBuf pin;         // ("pipe_pin") pinned: per slot {out_last[4], GV(m), GH(n), abort, pad}
+    gapipe::Plan plan;  // the current call's (ga_pipe.h)
+    garng::RngTable rng;  // the calls' one continuous tie-break stream (gapipe::TableFeeder extends it)
+    // chained pipeline walks (walk_chain_kernel): the tie-break stream in pinned, coherent host memory
+    // and the control words {fills done, walks done, abort, timed out, entries written (8 B at [4])}
+    PinBuf chain_tab{true}, chain_ctl{true};
+    // the chain's stream, at the LEAST priority: HIP gives each priority its own pool of hardware
+    // queues, and no other stream of the process uses this pool, so no fill can ever be queued behind
+    // the persistent chain on an in-order queue it shares (the chain waits for those fills)
+    hipStream_t cwstream = nullptr;
+    // per slot, pinned and coherent: the walk's result words and levels, written by the chain straight
+    // into host memory (a hipMemcpy would wait for a CU, and the fills hold them all)
+    PinBuf chain_io{true};
+    ~Pipeline() {  // its streams and events (the context's device is current: ga_ctx_destroy)
+        for (auto& sl : slot)
+            for (hipEvent_t e : {sl.fb.ev[0], sl.fb.ev[1], sl.fdone, sl.w0, sl.w1})
+                if (e) (void)hipEventDestroy(e);
+        for (hipStream_t st : {wstream, cwstream, mwstream, mfstream[0], mfstream[1], mfstream[2], mfstream[3],
+                               nfstream[0], nfstream[1], nfstream[2], nfstream[3], fstream[1], fstream[2], fstream[3]})
+            if (st) (void)hipStreamDestroy(st);
+    }
+};
+
 }  // namespace gahost
 // (ga_ctx is the C ABI's type and stays global: it names these five; the .cpp files open gahost themselves)
 using gahost::DevBuf;
@@ -214,36 +258,8 @@ struct ga_ctx {
     uint32_t* in_prog_ext = nullptr;
     uint32_t* out_prog_ext = nullptr;
     RngTable walk_rng;             // tie-break table of the global problem (slab walks)
-    // pipelined repeated alignments (ga_problem_align_many): two slots of traceback words, walk
-    // buffers and events; the walk runs on its own stream beside the next fill
-    struct PipeSlot {
-        FillBufs fb;  // each pipelined alignment computes its own boundary (make_dp_array) into its slot
-        DevBuf rng, ops, result;
-        hipEvent_t fdone = nullptr, w0 = nullptr, w1 = nullptr;
-        PinBuf tab_pin;  // pinned staging of the walk's table slice
-    } pipe[6];
-    hipStream_t wstream = nullptr, fstream[4] = {nullptr, nullptr, nullptr, nullptr};  // [0] unused: ctx->stream
-    // CU-masked pipeline streams (GA_PIPE_WALK_CUS > 0): the walk keeps CUs of its own, the fills the rest
-    hipStream_t mwstream = nullptr, mfstream[4] = {nullptr, nullptr, nullptr, nullptr};
-    // default-priority pipeline fill streams (GA_PIPE_FILL_PRIO=normal): four fills on their own pool of
-    // hardware queues, the walk stream keeping the greatest priority (it takes the next free CU)
-    hipStream_t nfstream[4] = {nullptr, nullptr, nullptr, nullptr};
-    int walk_cus = -1;  // CUs reserved for the walk (0: no masks; -1: not yet set up)
-    PinBuf pipe_pin;               // pinned: per slot {out_last[4], GV(m), GH(n), abort, pad}
-    int pipe_fills = 2, pipe_slots = 3;  // fills in flight (one stream each) and slots (fills + the walked one)
-    int hw_queues = 4;                   // GPU_MAX_HW_QUEUES as the process first saw it (ga_ctx_create)
-    int pipe_lane_td = 0, pipe_lane_nwc = 0;  // the pipeline's lane-kernel fill geometry (0: the row scan)
-    RngTable many_rng;
-    // chained pipeline walks (walk_chain_kernel): the tie-break stream in pinned, coherent host memory
-    // and the control words {fills done, walks done, abort, timed out, entries written (8 B at [4])}
-    PinBuf chain_tab{true}, chain_ctl{true};
-    // the chain's stream, at the LEAST priority: HIP gives each priority its own pool of hardware
-    // queues, and no other stream of the process uses this pool, so no fill can ever be queued behind
-    // the persistent chain on an in-order queue it shares (the chain waits for those fills)
-    hipStream_t cwstream = nullptr;
-    // per slot, pinned and coherent: the walk's result words and levels, written by the chain straight
-    // into host memory (a hipMemcpy would wait for a CU, and the fills hold them all)
-    PinBuf chain_io{true};
+    int hw_queues = 4;             // GPU_MAX_HW_QUEUES as the process first saw it (ga_ctx_create)
+    gahost::Pipeline pipe;         // pipelined repeated alignments (ga_problem_align_many)
     bool walk_rng_ready = false;
     float fill_ms = 0.f, walk_ms = 0.f, rng_ms = 0.f, call_ms = 0.f;
     bool dbg_on = false;
@@ -310,7 +326,27 @@ struct Band : gaplan::Request {
     hipStream_t stream = nullptr;
 };
 
+// Walk state between slab walks (the C ABI's ga_walk_state without the padding rules).
+struct WalkStart {
+    int64_t i, j, D, h;  // j: global column
+    int L, first;
+};
+
+// Where a walk reads its words and table and leaves its levels / result, on which stream.
+struct WalkBufs {
+    const uint8_t* tb;
+    uint32_t* rng;
+    uint32_t* ops;
+    int* result;
+    hipStream_t stream;
+    hipEvent_t ev0, ev1;
+    const int* bnd_row = nullptr;  // the boundary triples (nullptr: the context's)
+    const int* bnd_col = nullptr;
+    unsigned* ops_prog = nullptr;  // WalkArgs::ops_prog (ops then in pinned host memory)
+};
+
 int check_ctx(ga_ctx* c);
+gaplan::Problem plan_problem(const ga_ctx* c);
 int guard_end(ga_ctx* c, int rc);
 std::vector<int> shifted_sub(const ga_costs* cs);
 int load_problem(ga_ctx* c, const uint8_t* a, int64_t m, const uint8_t* b_all, int64_t n_all, const ga_costs* cs,
@@ -319,5 +355,23 @@ int enqueue_fill(ga_ctx* c, int32_t flags, const Band& bd = Band(), gaplan::Fill
 int finish_fill(ga_ctx* c, int64_t* cost_out, int32_t* full_out);
 double now_ms();
 int64_t band_rows(ga_ctx* c);
+ga::WalkArgs walk_args(ga_ctx* c, int64_t ntab, const WalkStart& st, int64_t r0, int64_t mb, bool vhandoff,
+                       const WalkBufs& wb);
+int run_walk(ga_ctx* c, const uint32_t* tab, int64_t ntab, const WalkStart& st, int64_t r0 = 0, int64_t mb = -1,
+             bool vhandoff = false, bool upload_tab = true, const WalkBufs* wbp = nullptr);
+// The alignment columns of a finished walk (its result words already read): levels of dispatches
+// [st.D, res[0]) decoded in walk order starting at (st.i, st.j) (global columns); the end state through `st` and
+// `reason`.  synced: the walk is known to be complete, so its levels are read with a plain copy instead of on its
+// stream (which may already hold the next walk); host_ops: they are in pinned host memory already.
+int decode_segment(ga_ctx* c, const int* res, WalkStart& st, int& reason, const char* a_chr, const char* b_chr,
+                   char* oa, char* om, char* ob, int64_t cap, int64_t& len, const WalkBufs& wb, bool synced,
+                   const uint32_t* host_ops = nullptr);
+// The end of a traceback: the MT state after its dispatches, the reference's tails, reversal.
+int conclude_walk(const RngTable& snaps, const WalkStart& st, int reason, uint32_t* mt_state, const char* a_chr,
+                  const char* b_chr, char* oa, char* om, char* ob, int64_t cap, int64_t len, int64_t* out_len,
+                  int32_t* tb_status);
+// ga_problem_align_many without guard mode's ending (ga_pipe_host.cpp)
+int problem_align_many(ga_ctx* c, int32_t count, uint32_t* mt_state, const char* a_chr, const char* b_chr, char* oa,
+                       char* om, char* ob, int64_t cap, int64_t* out_len, int32_t* tb_status, int64_t* cost_out);
 
 }  // namespace gahost

@@ -139,3 +139,43 @@ def test_align_repeated_walk_chain(monkeypatch, chain, pinned_io, m, n, seed, co
         assert r.cost == cost
         assert (r.seq_1_aligned, r.middle_part, r.seq_2_aligned) == strings
     assert random.getstate()[1] == tuple(int(x) for x in ref[-1][2])
+
+
+def _assert_chained_oracle(m, n, seed, count, kw):
+    import globalign_amd
+    alpha = "protein" if "scoring_mat_name" in kw else "dna"
+    s1, s2 = splitmix_seq(m, seed, alpha), splitmix_seq(n, seed + 1, alpha)
+    ref = _chain_oracle(s1, s2, kw, seed, count)
+    random.seed(seed)
+    runs = globalign_amd.GlobalAligner(max_seq_len_prod=None, **kw).align_repeated(s1, s2, count)
+    assert len(runs) == count
+    for r, (cost, strings, _) in zip(runs, ref):
+        assert r.cost == cost
+        assert (r.seq_1_aligned, r.middle_part, r.seq_2_aligned) == strings
+    assert random.getstate()[1] == tuple(int(x) for x in ref[-1][2])
+
+
+@pytest.mark.parametrize("knobs,shape", [
+    (dict(GA_PIPE_SLOTS=6), 0),
+    (dict(GA_PIPE_SLOT_ORDER="fixed"), 0),
+    (dict(GA_PIPE_FILL_PRIO="normal"), 1),
+    (dict(GA_PIPE_CHAIN=1, GA_PIPE_SLOTS=6), 0),
+], ids=["slots6", "fixed-order", "fill-prio-normal", "chain-slots6"])
+def test_align_repeated_pipe_knobs(monkeypatch, knobs, shape):
+    """The pipeline's other knobs: six slots (more than fills + 1) with per-launch walks and with the chain (which has
+    six), walks that take slot k % S, fills on default-priority streams; more alignments than slots, so every slot is
+    reused.  Strings, costs and the final random state equal the chained oracle's."""
+    for k, v in knobs.items():
+        set_knob(monkeypatch, k, v)
+    _assert_chained_oracle(*_CHAIN_SHAPES[shape])
+
+
+@pytest.mark.parametrize("m,n,seed,count,band_rows", [(900, 1000, 16, 1, None), (2500, 3100, 17, 3, 512)],
+                         ids=["count1", "banded"])
+def test_align_repeated_serial_fallback(monkeypatch, m, n, seed, count, band_rows):
+    """One alignment, and banded tracebacks (GA_TB_BAND_ROWS: the band fills hold every CU): ga_problem_align_many
+    runs them one after another, with the chained oracle's results."""
+    if band_rows is not None:
+        set_knob(monkeypatch, "GA_TB_BAND_ROWS", band_rows)
+    _assert_chained_oracle(m, n, seed, count,
+                           dict(match_score=2, mismatch_score=-3, gap_open_score=-5, gap_extension_score=-1))
