@@ -1,7 +1,7 @@
-// ga_host_internal.h -- what the host engine's three translation units share (ga_host.cpp: contexts, the single-pair
-// paths, slabs; ga_batch_host.cpp: the batched calls; ga_pipe_host.cpp: the repeated-alignment pipeline).  Internal:
-// not installed, and include/globalign_amd.h does not mention it.  The shared helpers live in namespace gahost and,
-// but for the pipeline's, are defined in ga_host.cpp.
+// ga_host_internal.h -- what the host engine's four translation units share (ga_host.cpp: contexts, the fill, slabs;
+// ga_align_host.cpp: one alignment's traceback; ga_batch_host.cpp: the batched calls; ga_pipe_host.cpp: the
+// repeated-alignment pipeline).  Internal: not installed, and include/globalign_amd.h does not mention it.  The shared
+// helpers live in namespace gahost and are defined in the file named above each group.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,6 +17,7 @@
 #include "ga_pipe.h"
 #include "ga_plan.h"
 #include "ga_rng.h"
+#include "ga_walk_plan.h"
 
 namespace gahost {
 
@@ -238,6 +239,7 @@ struct ga_ctx {
     bool rc_pos_zeroed = false;  // rc_pos was cleared on the fill's stream before the fill (rc_align)
     int qrows = 1024, num_cu = 256;  // the row scan's query-profile ring (load_problem)
     gaplan::Knobs pk;          // the planner's knobs, parsed once (plan_knobs)
+    gawalk::Knobs wk;          // the traceback call's, parsed once (ga_walk_plan.h)
     // the last enqueued fill's plan (ga_plan.h): kernel, geometry, checkpoint spacing; before the first fill the
     // loaded problem's row-scan geometry
     gaplan::FillPlan plan;
@@ -345,20 +347,40 @@ struct WalkBufs {
     unsigned* ops_prog = nullptr;  // WalkArgs::ops_prog (ops then in pinned host memory)
 };
 
+// ---- ga_host.cpp
 int check_ctx(ga_ctx* c);
 gaplan::Problem plan_problem(const ga_ctx* c);
 int guard_end(ga_ctx* c, int rc);
 std::vector<int> shifted_sub(const ga_costs* cs);
 int load_problem(ga_ctx* c, const uint8_t* a, int64_t m, const uint8_t* b_all, int64_t n_all, const ga_costs* cs,
                  const int32_t* row0, const int32_t* col0, int64_t cb, int64_t ce);
+int64_t dev_avail_bytes(ga_ctx* c, int64_t held);
+size_t rc_cache_bytes(bool jump, int TD, int CB);
 int enqueue_fill(ga_ctx* c, int32_t flags, const Band& bd = Band(), gaplan::FillPlan* plan_out = nullptr);
 int finish_fill(ga_ctx* c, int64_t* cost_out, int32_t* full_out);
 double now_ms();
-int64_t band_rows(ga_ctx* c);
+
+// ---- ga_align_host.cpp
+// the start state of a whole problem's walk: at (m, n), no dispatch made yet
+inline WalkStart walk_origin(const ga_ctx* c) { return WalkStart{c->m, c->n, 0, 0, 0, 1}; }
+int64_t band_rows(ga_ctx* c);  // gawalk::band_rows of the loaded problem on this device
+WalkBufs ctx_walk_bufs(ga_ctx* c);
 ga::WalkArgs walk_args(ga_ctx* c, int64_t ntab, const WalkStart& st, int64_t r0, int64_t mb, bool vhandoff,
                        const WalkBufs& wb);
 int run_walk(ga_ctx* c, const uint32_t* tab, int64_t ntab, const WalkStart& st, int64_t r0 = 0, int64_t mb = -1,
              bool vhandoff = false, bool upload_tab = true, const WalkBufs* wbp = nullptr);
+// A launched walk's result words and levels, waited for on its stream and decoded (decode_segment).
+int walk_segment(ga_ctx* c, WalkStart& st, int& reason, const char* a_chr, const char* b_chr, char* oa, char* om,
+                 char* ob, int64_t cap, int64_t& len, const WalkBufs* wbp = nullptr);
+// The recompute walk: its score-only checkpointing fill of the loaded problem or slab, and the launch
+// of the walk + recompute workgroups from walk state `st` on the walk buffers `wb` (its table already uploaded).
+int rc_fill(ga_ctx* c);
+int rc_walk_launch(ga_ctx* c, int64_t ntab, const WalkStart& st, WalkBufs& wb);
+// ga_problem_traceback and ga_problem_align without guard mode's ending
+int problem_traceback_impl(ga_ctx* c, uint32_t* mt_state, const char* a_chr, const char* b_chr, char* oa, char* om,
+                           char* ob, int64_t cap, int64_t* out_len, int32_t* tb_status);
+int problem_align_impl(ga_ctx* c, uint32_t* mt_state, const char* a_chr, const char* b_chr, char* oa, char* om,
+                       char* ob, int64_t cap, int64_t* out_len, int32_t* tb_status, int64_t* cost_out);
 // The alignment columns of a finished walk (its result words already read): levels of dispatches
 // [st.D, res[0]) decoded in walk order starting at (st.i, st.j) (global columns); the end state through `st` and
 // `reason`.  synced: the walk is known to be complete, so its levels are read with a plain copy instead of on its

@@ -6,6 +6,8 @@
 //     limit tables of tests/limit_costs.py at the last factor the guard accepts and the first it refuses;
 //   * the fill planner (ga_plan.h): the kernel, geometry and checkpoint spacing of the shapes the project's records
 //     pin (profiles/r06, DESIGN.md 5.2 / 5.6 / 5.8.1, tests/test_gpu_rc_default_width.py), and every error return;
+//   * the traceback call's pure part (ga_walk_plan.h): its knobs' defaults and clamps, the recompute walk's eligibility,
+//     the banded traceback's rows, the recompute window's invariants and its default tables, workers per workgroup;
 //   * the guard bands' layout, scan and report (ga_guard.h) on a host model of a guarded buffer.
 // No HIP: the engine's library is tested on the GPU; this binary covers the host logic under the sanitizers.
 //
@@ -24,6 +26,7 @@
 #include "ga_guard.h"
 #include "ga_plan.h"
 #include "ga_rng.h"
+#include "ga_walk_plan.h"
 
 using namespace garng;
 
@@ -610,6 +613,213 @@ void test_guard() {
     }
 }
 
+// ---------------------------------------------------------------- the traceback call's pure part (ga_walk_plan.h)
+using KnobMap = std::map<std::string, std::string>;
+
+// the knobs of `kv` as a context would parse them: in an experiments build (xknobs) xget sees what get sees
+gawalk::Knobs walk_knobs(const KnobMap& kv, bool xknobs = false) {
+    auto get = [&kv](const char* name) -> const char* {
+        const auto it = kv.find(name);
+        return it == kv.end() ? nullptr : it->second.c_str();
+    };
+    auto none = [](const char*) -> const char* { return nullptr; };
+    return xknobs ? gawalk::Knobs::parse(get, get) : gawalk::Knobs::parse(get, none);
+}
+
+void test_walk_knobs() {
+    {
+        const gawalk::Knobs kn = walk_knobs({});
+        CHECK(kn.rc == -1 && !kn.rc_min_cells && kn.rc_every == 0 && kn.rc_loaders == 14 && kn.rc_tag_fault == 0 &&
+                  !kn.rc_wpw && kn.rc_span == 32 && kn.rc_cone == 3 && !kn.rc_win && kn.rc_servers == 64 &&
+                  kn.rc_decode_lag == 0 && !kn.rc_decode_check,
+              "GA_RC_* defaults");
+        CHECK(kn.walk_skip_corners == 1 && kn.walk_loaders == 14 && !kn.walk_nostream && !kn.tb_band_rows &&
+                  kn.tb_budget == (int64_t)64 << 30 && !kn.dev_avail,
+              "GA_WALK_* / GA_TB_* / GA_DEV_AVAIL_MB defaults");
+        CHECK(gawalk::servers(kn) == 64, "64 recompute workgroups by default");
+    }
+    // every clamp: one step outside each end, both ends, inside
+    struct Clamp { const char* name; int gawalk::Knobs::*field; bool x; int in[5], out[5]; };
+    const Clamp clamps[] = {
+        {"GA_RC_LOADERS", &gawalk::Knobs::rc_loaders, true, {11, 12, 13, 14, 15}, {12, 12, 13, 14, 14}},
+        {"GA_RC_SPAN", &gawalk::Knobs::rc_span, false, {1, 2, 5, 32, 33}, {2, 2, 5, 32, 32}},
+        {"GA_RC_CONE", &gawalk::Knobs::rc_cone, false, {0, 1, 4, 8, 9}, {1, 1, 4, 8, 8}},
+        {"GA_RC_SERVERS", &gawalk::Knobs::rc_servers, false, {0, 1, 100, 255, 256}, {1, 1, 100, 255, 255}},
+        {"GA_RC_TAG_FAULT", &gawalk::Knobs::rc_tag_fault, false, {-2, -1, 0, 1, 7}, {0, 0, 0, 1, 7}},
+        // (no clamp: the experiments build's values as given)
+        {"GA_WALK_SKIP_CORNERS", &gawalk::Knobs::walk_skip_corners, true, {-1, 0, 2, 3, 9}, {-1, 0, 2, 3, 9}},
+        {"GA_WALK_LOADERS", &gawalk::Knobs::walk_loaders, true, {0, 12, 13, 14, 20}, {0, 12, 13, 14, 20}},
+        {"GA_RC", &gawalk::Knobs::rc, false, {-1, 0, 1, 2, 7}, {-1, 0, 1, 2, 7}},
+        {"GA_RC_EVERY", &gawalk::Knobs::rc_every, false, {64, 128, 256, 4096, 1 << 20}, {64, 128, 256, 4096, 1 << 20}},
+    };
+    for (const Clamp& cl : clamps)
+        for (int k = 0; k < 5; k++) {
+            const gawalk::Knobs kn = walk_knobs({{cl.name, std::to_string(cl.in[k])}}, cl.x);
+            CHECK(kn.*cl.field == cl.out[k], "%s=%d parsed as %d, expected %d", cl.name, cl.in[k], kn.*cl.field, cl.out[k]);
+        }
+    for (const auto& [in, out] : {std::pair<int, int>{3, 4}, {4, 4}, {5, 5}, {1000, 1000}}) {
+        const gawalk::Knobs kn = walk_knobs({{"GA_RC_WIN", std::to_string(in)}});
+        CHECK(kn.rc_win && *kn.rc_win == out, "GA_RC_WIN=%d", in);
+    }
+    {
+        const gawalk::Knobs kn = walk_knobs({{"GA_RC_DECODE_LAG", "3"}, {"GA_RC_DECODE_CHECK", "0"}, {"GA_WALK_NOSTREAM", "0"},
+                                             {"GA_TB_BUDGET_MB", "100"}, {"GA_DEV_AVAIL_MB", "5"}, {"GA_TB_BAND_ROWS", "40"},
+                                             {"GA_RC_MIN_CELLS", "5000000000"}, {"GA_RC_WPW", "0"}});
+        CHECK(kn.rc_decode_lag == 1536 && kn.rc_decode_check && kn.walk_nostream, "lag in blocks of 512; flags set by presence");
+        CHECK(kn.tb_budget == (int64_t)100 << 20 && kn.dev_avail && *kn.dev_avail == (int64_t)5 << 20, "megabytes to bytes");
+        CHECK(kn.tb_band_rows && *kn.tb_band_rows == 40 && kn.rc_min_cells && *kn.rc_min_cells == 5000000000LL &&
+                  kn.rc_wpw && *kn.rc_wpw == 0,
+              "optional knobs as given");
+    }
+    {
+        // the knobs of dropped paths: invisible to a shipped build, whose xget sees nothing
+        const KnobMap kv = {{"GA_WALK_SKIP_CORNERS", "3"}, {"GA_WALK_LOADERS", "12"}, {"GA_RC_LOADERS", "12"}};
+        const gawalk::Knobs ship = walk_knobs(kv), xb = walk_knobs(kv, true);
+        CHECK(ship.walk_skip_corners == 1 && ship.walk_loaders == 14 && ship.rc_loaders == 14, "shipped build read an xknob");
+        CHECK(xb.walk_skip_corners == 3 && xb.walk_loaders == 12 && xb.rc_loaders == 12, "experiments build's xknobs");
+    }
+}
+
+void test_walk_paths() {
+    using gawalk::rc_eligible;
+    const gawalk::Knobs unset, never = walk_knobs({{"GA_RC", "0"}}), always = walk_knobs({{"GA_RC", "1"}});
+    // the shape's floor (GA_RC=1: the shape alone decides)
+    CHECK(rc_eligible(shape(256, 256), always, false) && !rc_eligible(shape(255, 256), always, false) &&
+              !rc_eligible(shape(256, 255), always, false),
+          "256 rows and columns at the least");
+    CHECK(rc_eligible(shape(256, 256, 32), always, false) && !rc_eligible(shape(256, 256, 33), always, false), "K <= 32");
+    {
+        gaplan::Problem pb = shape(256, 256);
+        pb.qbytes = 2;
+        CHECK(!rc_eligible(pb, always, false) && !rc_eligible(pb, always, true), "an int16 profile");
+    }
+    CHECK(!rc_eligible(shape(100000, 100000), never, false) && !rc_eligible(shape(100000, 100000), never, true), "GA_RC=0");
+    CHECK(!rc_eligible(shape(256, 256), unset, false), "a small problem by default");
+    // the cell thresholds: 2^26 for the single call (8191 * 8193 = 2^26 - 1), 2^32 for a slab (65535 * 65537 = 2^32 - 1)
+    CHECK(rc_eligible(shape(8192, 8192), unset, false) && !rc_eligible(shape(8191, 8193), unset, false), "2^26 cells");
+    CHECK(!rc_eligible(shape(8192, 8192), unset, true), "2^26 cells are too few for a slab");
+    CHECK(rc_eligible(shape(65536, 65536), unset, true) && !rc_eligible(shape(65535, 65537), unset, true), "2^32 cells");
+    {
+        const gawalk::Knobs kn = walk_knobs({{"GA_RC_MIN_CELLS", "1000000"}});
+        for (bool slab_call : {false, true})
+            CHECK(rc_eligible(shape(1000, 1000), kn, slab_call) && !rc_eligible(shape(1000, 999), kn, slab_call),
+                  "GA_RC_MIN_CELLS=1000000, slab call %d", (int)slab_call);
+    }
+    // the lean checkpoint store's 32-bit buffer: (m + 1 + 64) * 8 < 0x7ffffff0 holds up to m = 268435388
+    CHECK(rc_eligible(shape(268435388, 256), always, false) && !rc_eligible(shape(268435389, 256), always, false),
+          "rc_rows_fit's last row count");
+    {
+        gaplan::Problem pb = shape(65536, 65536);
+        pb.slab = true;
+        CHECK(!rc_eligible(pb, unset, false) && !rc_eligible(pb, always, false) && rc_eligible(pb, unset, true),
+              "a slab context qualifies on the slab call only");
+    }
+
+    using gawalk::band_rows;
+    const int64_t plenty = INT64_MAX / 4;
+    // forced rows round down to whole 16-row chunks, and band only where two bands fit
+    for (const auto& [rows, Bh] : {std::pair<int, int>{15, 0}, {16, 16}, {40, 32}})
+        CHECK(band_rows(1000, 1000, 1, walk_knobs({{"GA_TB_BAND_ROWS", std::to_string(rows)}}), plenty) == Bh,
+              "GA_TB_BAND_ROWS=%d", rows);
+    {
+        const gawalk::Knobs kn = walk_knobs({{"GA_TB_BAND_ROWS", "32"}});
+        CHECK(band_rows(63, 1000, 1, kn, plenty) == 0 && band_rows(64, 1000, 1, kn, 0) == 32, "forced rows: m >= 2 * Bh");
+    }
+    {
+        // 4096 x 1000 at one-byte words: 1024 bytes a row, 4 MiB in all
+        gawalk::Knobs kn;
+        kn.tb_budget = (int64_t)4 << 20;
+        CHECK(band_rows(4096, 1000, 1, kn, plenty) == 0, "words that fit the budget exactly");
+        kn.tb_budget--;  // 4095 rows fit, 4080 in whole chunks: no two such bands in 4096 rows, so no banding either
+        CHECK(band_rows(4096, 1000, 1, kn, plenty) == 0, "one byte less: a band of 4080 rows does not halve 4096");
+        kn.tb_budget = (int64_t)2 << 20;
+        CHECK(band_rows(4096, 1000, 1, kn, plenty) == 2048 && band_rows(4095, 1000, 1, kn, plenty) == 0, "half the words");
+        kn.tb_budget--;
+        CHECK(band_rows(4096, 1000, 1, kn, plenty) == 2032, "half the words less one byte: 2047 rows, 2032 in chunks");
+        CHECK(band_rows(4096, 1000, 4, kn, plenty) == 496, "4-byte words: 511 rows fit, 496 in chunks");
+        // the device's free memory below the budget (the default 64 GB here)
+        CHECK(band_rows(4096, 1000, 1, gawalk::Knobs(), 1 << 20) == 1024, "1 MiB available");
+        CHECK(band_rows(4096, 1000, 1, gawalk::Knobs(), plenty) == 0, "64 GB by default");
+        // the 64-row floor: 10 rows' worth available
+        CHECK(band_rows(4096, 1000, 1, gawalk::Knobs(), 10 * 1024) == 64 && band_rows(128, 1000, 1, gawalk::Knobs(), 10 * 1024) == 64 &&
+                  band_rows(127, 1000, 1, gawalk::Knobs(), 10 * 1024) == 0,
+              "the 64-row floor");
+    }
+
+    CHECK(gawalk::streamed(256, 256, unset) && !gawalk::streamed(255, 1000, unset) && !gawalk::streamed(1000, 255, unset) &&
+              !gawalk::streamed(1000, 1000, walk_knobs({{"GA_WALK_NOSTREAM", "1"}})),
+          "streamed levels from 256 x 256 up unless GA_WALK_NOSTREAM");
+
+    // workers per recompute workgroup: 20000-byte workers, of which (2 * 65536 - 1024) / 20000 = 6 fit
+    CHECK(gawalk::workers(false, 20000, unset) == 1, "one worker unless GA_RC_WPW");
+    for (const auto& [wpw, n] : {std::pair<int, int>{0, 1}, {4, 4}, {99, 6}})
+        CHECK(gawalk::workers(false, 20000, walk_knobs({{"GA_RC_WPW", std::to_string(wpw)}})) == n, "GA_RC_WPW=%d", wpw);
+    CHECK(gawalk::workers(false, 1000, walk_knobs({{"GA_RC_WPW", "99"}})) == 16, "16 workers at the most");
+    CHECK(gawalk::workers(true, 20000, walk_knobs({{"GA_RC_WPW", "99"}})) == 1 && gawalk::workers(true, 20000, unset) == 1,
+          "the tie-to-tie walk's one worker");
+}
+
+// The default windows (cone 3, span 32) at 1, 2, 4 and 8 columns per lane, recorded from the candidate loop as it stood
+// in ga_host.cpp's rc_walk_launch before it moved to ga_walk_plan.h (that loop compiled verbatim in a program of its own)
+const unsigned char kWindows[4][64] = {
+    {0, 1, 8, 9, 18, 10, 17, 27, 2, 16, 19, 26, 36, 11, 25, 28, 35, 45, 3, 20, 24, 34, 37, 44, 54, 12, 29, 33, 43, 46, 53, 63,
+     4, 21, 32, 38, 42, 52, 55, 62, 13, 30, 41, 47, 51, 61, 71, 5, 22, 39, 40, 50, 60, 70, 14, 31, 49, 59, 69, 79, 6, 23, 48, 58},
+    {0, 1, 8, 9, 17, 16, 25, 34, 26, 18, 24, 33, 42, 51, 10, 43, 2, 32, 35, 41, 50, 59, 68, 27, 60, 19, 40, 49, 52, 58, 67, 76,
+     85, 11, 44, 77, 3, 36, 48, 57, 66, 69, 75, 84, 93, 102, 28, 61, 94, 20, 53, 56, 65, 74, 83, 86, 92, 101, 110, 119, 12, 45,
+     78, 111},
+    {0, 1, 8, 9, 16, 33, 25, 17, 24, 41, 32, 49, 66, 58, 40, 50, 57, 74, 42, 34, 48, 65, 82, 99, 26, 91, 18, 56, 73, 83, 90, 107,
+     10, 75, 2, 64, 67, 81, 98, 115, 132, 59, 124, 51, 72, 89, 106, 116, 123, 140, 43, 108, 35, 80, 97, 100, 114, 131, 148, 165,
+     27, 92, 157, 19},
+    {0, 1, 8, 9, 16, 24, 32, 65, 57, 40, 49, 73, 41, 33, 48, 81, 25, 17, 56, 89, 64, 97, 130, 122, 72, 105, 114, 138, 106, 80, 98,
+     113, 146, 90, 82, 88, 121, 154, 74, 66, 96, 129, 162, 195, 58, 187, 50, 104, 137, 170, 179, 203, 42, 171, 34, 112, 145, 163,
+     178, 211, 26, 155, 18, 120}};
+
+void test_walk_window() {
+    for (int TD : {1, 2, 4, 8})
+        for (int cone : {1, 3, 8})
+            for (int span : {2, 3, 8, 32}) {
+                const KnobMap kv = {{"GA_RC_CONE", std::to_string(cone)}, {"GA_RC_SPAN", std::to_string(span)}};
+                const gawalk::Window w = gawalk::window(TD, walk_knobs(kv));
+                const int cols = std::min(span, 8), want = std::min(64, span * cols);
+                // the walker's own 2 x 2 blocks first: it waits on no others, so the walk always makes progress
+                CHECK(w.off[0] == 0 && w.off[1] == 1 && w.off[2] == 8 && w.off[3] == 9, "TD %d cone %d span %d: first four %d %d %d %d",
+                      TD, cone, span, w.off[0], w.off[1], w.off[2], w.off[3]);
+                CHECK(w.nwin == want, "TD %d cone %d span %d: %d window blocks, expected %d", TD, cone, span, w.nwin, want);
+                bool seen[256] = {};
+                int last = -1;
+                for (int k = 0; k < 64; k++) {
+                    const int di = w.off[k] >> 3, dj = w.off[k] & 7, dist = di - dj * TD;
+                    const int key = di + dj * TD + cone * (dist < 0 ? -dist : dist);
+                    if (k >= w.nwin) {
+                        CHECK(w.off[k] == 0, "TD %d cone %d span %d: entry %d past the window is %d", TD, cone, span, k, w.off[k]);
+                        continue;
+                    }
+                    CHECK(!seen[w.off[k]] && di < span && dj < cols, "TD %d cone %d span %d: entry %d = %d repeats or is out of range",
+                          TD, cone, span, k, w.off[k]);
+                    seen[w.off[k]] = true;
+                    if (k >= 4) {
+                        CHECK(key >= last, "TD %d cone %d span %d: key %d at entry %d after %d", TD, cone, span, key, k, last);
+                        last = key;
+                    }
+                }
+                // GA_RC_WIN caps the window, never below the four
+                KnobMap capped = kv;
+                capped["GA_RC_WIN"] = "4";
+                CHECK(gawalk::window(TD, walk_knobs(capped)).nwin == 4, "GA_RC_WIN=4");
+                capped["GA_RC_WIN"] = "10";
+                CHECK(gawalk::window(TD, walk_knobs(capped)).nwin == std::min(want, 10), "GA_RC_WIN=10");
+                capped["GA_RC_WIN"] = "1";
+                CHECK(gawalk::window(TD, walk_knobs(capped)).nwin == 4, "GA_RC_WIN=1");
+                capped["GA_RC_WIN"] = "1000";
+                CHECK(gawalk::window(TD, walk_knobs(capped)).nwin == want, "GA_RC_WIN=1000");
+            }
+    const int tds[4] = {1, 2, 4, 8};
+    for (int t = 0; t < 4; t++) {
+        const gawalk::Window w = gawalk::window(tds[t], gawalk::Knobs());
+        CHECK(w.nwin == 64 && std::memcmp(w.off, kWindows[t], 64) == 0, "the default window at %d columns per lane changed", tds[t]);
+    }
+}
+
 double ms_since(std::chrono::steady_clock::time_point t) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
 }
@@ -644,6 +854,9 @@ int main(int argc, char** argv) {
     test_checks();
     test_limit_tables();
     test_plan();
+    test_walk_knobs();
+    test_walk_paths();
+    test_walk_window();
     test_guard();
     if (failures) {
         std::fprintf(stderr, "%d check(s) failed\n", failures);

@@ -153,7 +153,7 @@ int finish_alignment(ga_ctx* c, Many& run, int k, int slot, const int* res, cons
     if (hipEventElapsedTime(&fill_ms, sl.fb.ev[0], sl.fb.ev[1]) != hipSuccess) fill_ms = 0.f;
     run.fill_sum += fill_ms;
     if (int r = refill(fill_ms)) return r;
-    WalkStart st{c->m, c->n, 0, 0, 0, 1};
+    WalkStart st = walk_origin(c);
     int reason = 0;
     int64_t len = 0;
     char *a_k = run.oa + (size_t)k * run.cap, *m_k = run.om + (size_t)k * run.cap, *b_k = run.ob + (size_t)k * run.cap;
@@ -233,7 +233,7 @@ int align_chain(ga_ctx* c, const gapipe::Knobs& kn, Many& run, const hipStream_t
         }
         ga::WalkChainArgs A{};
         for (int s = 0; s < S; s++)
-            A.w[s] = walk_args(c, per, WalkStart{m, n, 0, 0, 0, 1}, 0, -1, false, slot_walk_bufs(c, s, ws, io, true, true));
+            A.w[s] = walk_args(c, per, walk_origin(c), 0, -1, false, slot_walk_bufs(c, s, ws, io, true, true));
         A.tab = P.chain_tab.dev<uint32_t>();
         A.ctl = P.chain_ctl.dev<unsigned>();
         A.tab_ready = reinterpret_cast<const long long*>(A.ctl + 4);
@@ -356,7 +356,7 @@ int align_many(ga_ctx* c, const gapipe::Knobs& kn, Many& run) {
         HIPCHK(hipStreamWaitEvent(ws, sl.fdone, 0));
         std::memcpy(sl.tab_pin.p, feeder.tab() + G, sizeof(uint32_t) * per);
         const WalkBufs wb = slot_walk_bufs(c, walk_slot[k], ws, io, pinned_io, false);
-        return run_walk(c, sl.tab_pin.host<uint32_t>(), per, WalkStart{m, n, 0, 0, 0, 1}, 0, -1, false, true, &wb);
+        return run_walk(c, sl.tab_pin.host<uint32_t>(), per, walk_origin(c), 0, -1, false, true, &wb);
     };
     int rc = start_walk(0, 0);
     double walk_launch_host = now_ms() - h0;

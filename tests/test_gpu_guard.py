@@ -15,7 +15,7 @@ Modes: "guard" (GA_GUARD_BYTES=4096: 8x the one overrun the project has had, 4x 
 pattern too, so memory a kernel reads without anyone having written it holds hostile values, not zeros).
 
 The edge sweep of the recompute walk.  The engine takes the recompute walk from 256 x 256 cells up only
-(ga_host.cpp rc_eligible: below that, degenerate walks read cells no block recomputes), whatever GA_RC says, so
+(ga_walk_plan.h rc_eligible: below that, degenerate walks read cells no block recomputes), whatever GA_RC says, so
 the sweep's rows and columns sit on that floor: m = 256 + {1, 17, 48, 63, 64, 65, 130} (the residues mod 64 of
 1, 17, 48, 63, 64, 65, 130: one row into a block, partial 16-row chunks, a block's last row, whole blocks) and
 n = 256 and the three columns around the first multiple of the stripe width 64 TD past 256, and 17 past the

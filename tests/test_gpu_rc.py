@@ -107,6 +107,15 @@ def test_rc_worker_pools_vs_oracle(monkeypatch, env, td):
     assert kind[1] == (2 if td == "narrow" else td), kind
 
 
+@pytest.mark.parametrize("span", [2, 5])
+def test_rc_candidate_span_vs_oracle(monkeypatch, span):
+    """GA_RC_SPAN narrows the square of candidate blocks the window is ranked from: 2 leaves the walker's own 2 x 2
+    blocks (the window of GA_RC_WIN=4), 5 leaves 25 candidates, fewer than the window's 64 entries."""
+    kind = _align(monkeypatch, splitmix_seq(1000, 43, "dna"), splitmix_seq(1300, 44, "dna"), DNA, seed=span,
+                  env={"GA_LANE_COLS_PER_LANE": 4, "GA_RC_SPAN": span})
+    assert kind[1] == 4, kind
+
+
 @pytest.mark.parametrize("jump", [0, pytest.param(1, marks=needs_jump)])
 def test_rc_lost_slot_tags_repaired_vs_oracle(monkeypatch, jump):
     """Cache slot owner tags (ga::rc_slot_tag, ADVICE r4): every 3rd block a worker writes is left without its tag,
