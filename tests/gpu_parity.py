@@ -45,22 +45,14 @@ def tables(problem):
     return _native.CostTables(cmat, o), s1, s2
 
 
-def align(monkeypatch, problem, seed, knobs, ref, fill=None, walk=None):
-    """Engine.align of a problem under `knobs` against ref = (cost, strings, status, mt words), the oracle's result
-    from random.seed(seed): cost, strings, status and every MT word; fill / walk: what fill_kind() / walk_kind() must
-    report (fill: a kind, or (kind, columns per lane))."""
+def _align_on(eng, problem, seed, ref, fill, walk):
+    """One Engine.align of a problem on an open engine against ref; -> fill_kind()."""
     from globalign_amd import _native
-    for k, v in knobs.items():
-        set_knob(monkeypatch, k, v)
     tabs, s1, s2 = tables(problem)
     cost_ref, strings_ref, status_ref, mt_ref = ref
-    eng = _native.Engine(0)
-    try:
-        eng.load(tabs.codes(s1), tabs.codes(s2), tabs)
-        cost, strings, status, mt_after = eng.align(mt(seed), s1, s2)
-        kind, wkind = eng.fill_kind(), eng.walk_kind()
-    finally:
-        eng.close()
+    eng.load(tabs.codes(s1), tabs.codes(s2), tabs)
+    cost, strings, status, mt_after = eng.align(mt(seed), s1, s2)
+    kind, wkind = eng.fill_kind(), eng.walk_kind()
     if fill is not None:
         want = fill if isinstance(fill, tuple) else (fill,)
         assert kind[:len(want)] == want, (kind, want)
@@ -71,6 +63,32 @@ def align(monkeypatch, problem, seed, knobs, ref, fill=None, walk=None):
     assert tuple(strings) == strings_ref
     assert tuple(np.asarray(mt_after, dtype=np.uint32).tolist()) == mt_ref
     return kind
+
+
+def align(monkeypatch, problem, seed, knobs, ref, fill=None, walk=None):
+    """Engine.align of a problem under `knobs` against ref = (cost, strings, status, mt words), the oracle's result
+    from random.seed(seed): cost, strings, status and every MT word; fill / walk: what fill_kind() / walk_kind() must
+    report (fill: a kind, or (kind, columns per lane))."""
+    return align_cases(monkeypatch, [(problem, seed, ref)], knobs, fill, walk)[0]
+
+
+def align_cases(monkeypatch, items, knobs, fill=None, walk=None):
+    """align() of every (problem, seed, ref) of `items` on ONE engine created under `knobs` (a list of small cases
+    spends its time creating engines otherwise) -> [fill_kind()]; a failure names the item's index."""
+    from globalign_amd import _native
+    for k, v in knobs.items():
+        set_knob(monkeypatch, k, v)
+    eng = _native.Engine(0)
+    kinds = []
+    try:
+        for q, (problem, seed, ref) in enumerate(items):
+            try:
+                kinds.append(_align_on(eng, problem, seed, ref, fill, walk))
+            except AssertionError as e:
+                raise AssertionError(f"item {q} (o = {problem[3]}): {e}") from e
+    finally:
+        eng.close()
+    return kinds
 
 
 def score(monkeypatch, problem, knobs, fill, load_kw=None):
