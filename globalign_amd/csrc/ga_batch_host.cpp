@@ -82,10 +82,9 @@ struct RngRoute {
 RngRoute rng_route(const ga_ctx* c, uint32_t flags) {
     RngRoute r;
     const uint32_t which = flags & GA_BATCH_TABLES_MASK;
-    const char* dflt = c->knob("GA_BATCH_RNG");
-    r.want_device = which == GA_BATCH_TABLES_DEVICE || (which == GA_BATCH_TABLES_DEFAULT && dflt && !strcmp(dflt, "device"));
-    if (const char* e = c->knob("GA_BATCH_RNG_DEVICE_MAX_STEPS")) r.max_steps = atoll(e);
-    if (const char* e = c->knob("GA_BATCH_RNG_WORD_CAP")) r.cap_words = atoi(e);
+    r.want_device = which == GA_BATCH_TABLES_DEVICE || (which == GA_BATCH_TABLES_DEFAULT && c->bk.rng_device_default);
+    r.max_steps = c->bk.rng_max_steps;
+    r.cap_words = c->bk.rng_cap_words;
     return r;
 }
 
@@ -144,8 +143,7 @@ int tables_enqueue(ga_ctx* c, const std::vector<gabrng::Item>& jobs, int64_t tab
     const double t_tab = now_ms();
     ts.tab = std::vector<uint32_t>(host.empty() ? 0 : (size_t)tab_entries);
     if (!host.empty()) {
-        const char* nt = c->knob("GA_BATCH_RNG_THREADS");
-        const int nthreads = gabatch::rng_threads(nt ? atoi(nt) : 0, (int64_t)host.size());
+        const int nthreads = gabatch::rng_threads(c->bk.rng_threads, (int64_t)host.size());
         gabatch::build_tables(host.data(), (int64_t)host.size(), nthreads, ts.tab.data());
         // (the work list's table ranges follow each other: neighbouring host items go up in one copy)
         for (const gabatch::TableRange& rg : ts.split.ranges)
@@ -250,7 +248,7 @@ static int batch_costs_ex_impl(ga_ctx* c, const uint8_t* codes, const int64_t* s
     if (!cost_out) return fail(GA_E_ARG, "null argument");
     // the planner's routing limits
     gabatch::Limits lim;
-    if (const char* e = c->knob("GA_BATCH_MAX_CELLS")) lim.max_cells = std::max<int64_t>(0, atoll(e));
+    if (c->bk.max_cells) lim.max_cells = *c->bk.max_cells;
     lim.scratch_rows_cap = gabatch::scratch_rows_cap(batch_max_waves(c));
     gabatch::Plan plan;
     std::string why;
@@ -308,7 +306,7 @@ static int batch_align_ex_impl(ga_ctx* c, const uint8_t* codes, const int64_t* s
     for (float& x : c->batch_align_ms) x = 0.f;
     const int64_t max_waves = batch_max_waves(c);
     gabatch::AlignLimits lim;
-    if (const char* e = c->knob("GA_BATCH_ALIGN_MAX_CELLS")) lim.max_cells = std::max<int64_t>(0, atoll(e));
+    if (c->bk.align_max_cells) lim.max_cells = *c->bk.align_max_cells;
     lim.scratch_rows_cap = gabatch::scratch_rows_cap(max_waves);
     lim.tb_words_cap = gabatch::tb_slice_words_cap(max_waves);
     gabatch::AlignPlan plan;
@@ -375,8 +373,7 @@ static int batch_align_ex_impl(ga_ctx* c, const uint8_t* codes, const int64_t* s
         if (fell_back) return GA_OK;
         // the strings, on threads sized by the kernel pairs (every pair writes its own outputs); out_len < 0: see below
         const double t_dec = now_ms();
-        const char* nt = c->knob("GA_BATCH_RNG_THREADS");
-        gabatch::run_shares(nitems, gabatch::rng_threads(nt ? atoi(nt) : 0, nitems), [&](int64_t first, int64_t stride) {
+        gabatch::run_shares(nitems, gabatch::rng_threads(c->bk.rng_threads, nitems),[&](int64_t first, int64_t stride) {
             for (int64_t t = first; t < nitems; t += stride) {
                 const ga_batch_item& it = plan.kernel[(size_t)t];
                 const size_t k = (size_t)it.out;
@@ -443,9 +440,9 @@ static int batch_sample_impl(ga_ctx* c, const uint8_t* codes, const int64_t* seq
     const double t_call = now_ms();
     const int64_t max_waves = batch_max_waves(c);
     gabatch::SampleLimits lim;
-    if (const char* e = c->knob("GA_BATCH_ALIGN_MAX_CELLS")) lim.max_cells = std::max<int64_t>(0, atoll(e));
-    if (const char* e = c->knob("GA_BATCH_SAMPLE_CHUNK_WORDS")) lim.chunk_tb_words = std::max<int64_t>(1, atoll(e));
-    if (const char* e = c->knob("GA_BATCH_SAMPLE_WALK_ENTRIES")) lim.walk_entries = std::max<int64_t>(1, atoll(e));
+    if (c->bk.align_max_cells) lim.max_cells = *c->bk.align_max_cells;
+    if (c->bk.sample_chunk_words) lim.chunk_tb_words = *c->bk.sample_chunk_words;
+    if (c->bk.sample_walk_entries) lim.walk_entries = *c->bk.sample_walk_entries;
     lim.scratch_rows_cap = gabatch::scratch_rows_cap(max_waves);
     gabatch::SamplePlan plan;
     std::string why;
@@ -457,7 +454,6 @@ static int batch_sample_impl(ga_ctx* c, const uint8_t* codes, const int64_t* seq
         if (int r = check_out_capacity(seq_off, pair_a, pair_b, k, out_off, sample_off[k], sample_off[k + 1])) return r;
     if (int r = refuse_slab_single(c, plan.single, "path")) return r;
     const gabatch::WalkOut out{chars, out_a, out_mid, out_b, out_off, out_len, tb_status};
-    const char* nt = c->knob("GA_BATCH_RNG_THREADS");
     const size_t ncodes = (size_t)seq_off[nseq];
     double walk_ticks = 0, walk_steps = 0;
 
@@ -523,7 +519,7 @@ static int batch_sample_impl(ga_ctx* c, const uint8_t* codes, const int64_t* seq
                 route = rng_route(c, GA_BATCH_TABLES_HOST);
             }
             const double t_dec = now_ms();
-            gabatch::run_shares(nw, gabatch::rng_threads(nt ? atoi(nt) : 0, nw), [&](int64_t first, int64_t stride) {
+            gabatch::run_shares(nw, gabatch::rng_threads(c->bk.rng_threads, nw), [&](int64_t first, int64_t stride) {
                 for (int64_t t = first; t < nw; t += stride) {
                     const int32_t* wr = reinterpret_cast<const int32_t*>(&walked[2 * (size_t)t]);
                     gabatch::decode_walk(fitems[(size_t)wi[t].fill], wr, ops.data() + wi[t].ops_off, wi[t].out, wr[0] < 0,

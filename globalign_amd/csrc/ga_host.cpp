@@ -11,7 +11,9 @@
 //   * string assembly from the walk's per-step levels (take_* :688-753,
 //     the i==0 / j==0 tails :542-581 and the final reverse :584-586): ga_strings.h.
 // Here: the context, guard mode, load_problem, the fill, slabs and the debug ABI.  One alignment's traceback
-// (ga_problem_align, ga_problem_traceback) is ga_align_host.cpp's.
+// (ga_problem_align, ga_problem_traceback) is ga_align_host.cpp's.  The context's options (the GA_* knobs) are
+// collected, checked and parsed into typed sets by ga_opts.h and its siblings, once, in ga_ctx_create_opts: no other
+// code of the engine sees an option's name or string.
 #include <unistd.h>
 
 #include <chrono>
@@ -21,26 +23,6 @@
 #include "ga_host_internal.h"
 #include "ga_lane.h"
 #include "ga_check.h"
-
-// ------------------------------------------------------------------ context
-// The GA_* variables the shipped library reads from the environment (INTEGRATION.md lists them): the path choices
-// and budgets an operator may want to set.  Every other option -- kernel variants for tests and tuning, fault
-// injection, diagnostics -- reaches a context only through ga_ctx_create_opts, never from the environment, so a
-// stray variable cannot change a production context's kernels or inject a fault.  An experiments build
-// (make EXPERIMENTS=1) takes every GA_* variable.
-const char* const kEnvKnobs[] = {"GA_RC",           "GA_RC_MIN_CELLS", "GA_RC_BUDGET_MB",      "GA_RC_EVERY",
-                                 "GA_RC_SERVERS",   "GA_TB_BUDGET_MB", "GA_FILL_MODE",         "GA_COLS_PER_LANE",
-                                 "GA_LANE_COLS_PER_LANE", "GA_PIPE_FILLS", "GA_PIPE_CHAIN",    "GA_STREAM_PRIORITY",
-                                 "GA_HALO_SPIN_LIMIT", "GA_PIPE_TRACE"};
-bool env_knob(const std::string& name) {
-#ifdef GA_EXPERIMENTS
-    return name.compare(0, 3, "GA_") == 0;
-#else
-    for (const char* k : kEnvKnobs)
-        if (name == k) return true;
-    return false;
-#endif
-}
 
 using namespace gahost;
 using namespace garng;
@@ -390,9 +372,6 @@ int64_t dev_avail_bytes(ga_ctx* c, int64_t held) {
     return std::max<int64_t>(avail, 0);
 }
 
-#ifdef GA_EXPERIMENTS
-constexpr bool kRcJumpDefault = false;  // the tie-to-tie walk unless GA_RC_JUMP says otherwise
-#endif
 // the recompute walk's block cache: the word walk's, and (experiments build) the tie-to-tie walk's entries
 size_t rc_cache_bytes(bool jump, int TD, int CB) {
     // (+ one 64-column stripe of slack: a loader reads whole 1 KiB runs)
@@ -402,27 +381,6 @@ size_t rc_cache_bytes(bool jump, int TD, int CB) {
 
 // ---------------------------------------------------------------- the planner's inputs (ga_plan.h)
 const gaplan::LdsSizes kLdsSizes{ga::fill_lane_lds_bytes, ga::rc_worker_bytes, rc_cache_bytes};
-
-// The knobs the fill's plan depends on, as numbers: parsed here, once per context, and nowhere else.
-gaplan::Knobs plan_knobs(const ga_ctx* c) {
-    gaplan::Knobs kn;
-    if (const char* e = c->knob("GA_COLS_PER_LANE")) kn.T_req = atoi(e);  // tuning overrides
-    if (const char* e = c->knob("GA_FILL_NWC")) kn.nwc_req = atoi(e);
-    if (const char* e = c->knob("GA_FILL_MODE"))
-        kn.diag_req = !strcmp(e, "diag") ? 2 : !strcmp(e, "row") ? 1 : !strcmp(e, "lane") ? 3 : 0;
-    if (const char* e = c->knob("GA_LANE_COLS_PER_LANE")) kn.lane_T_req = atoi(e);
-    if (const char* e = c->knob("GA_DIAG_COLS_PER_LANE")) kn.diag_T_req = atoi(e);
-    if (const char* e = c->knob("GA_LANE_WG_PER_CU")) kn.lane_wg_per_cu = std::max(1, std::min(2, atoi(e)));
-    if (const char* e = c->knob("GA_LANE_QROWS")) kn.lane_qrows = atoi(e);
-    if (const char* e = c->knob("GA_RC_NARROW")) kn.rc_narrow = atoi(e) != 0;
-    if (const char* e = c->knob("GA_RC_BUDGET_MB")) kn.rc_budget = atoll(e) << 20;
-#ifdef GA_EXPERIMENTS
-    // whether the tie-to-tie walk may run (GA_RC_JUMP): the checkpoint sizing then budgets its cache
-    const char* e = c->xknob("GA_RC_JUMP");
-    kn.rc_jump = e ? atoi(e) != 0 : kRcJumpDefault;
-#endif
-    return kn;
-}
 
 // ---------------------------------------------------------------- one fill: plan, buffers, arguments, launch
 // What the four stages of enqueue_fill share: the request, its plan, and where this fill reads and writes.
@@ -471,7 +429,7 @@ int fill_buffers(ga_ctx* c, const FillJob& j) {
         // itself with that memory free.  The memsets enqueued above are harmless: the fallback's own fill
         // enqueues them again behind them on the same stream.  GA_RC_FAIL_ALLOC=1 (tests) fails the second
         // allocation after the first succeeded.
-        const bool fail_test = c->knob("GA_RC_FAIL_ALLOC") && atoi(c->knob("GA_RC_FAIL_ALLOC")) == 1;
+        const bool fail_test = c->lk.rc_fail_alloc;
         int nb = 0;
         for (auto [buf, bytes] : {std::pair<DevBuf*, size_t>{&c->colck, sizeof(int2) * (size_t)pl.nstripes * (m + 1 + ga::COLCK_PAD)},
                                   {&c->stck, sizeof(int2) * (size_t)nck * pl.nstripes * (pl.T + 1) * 64}}) {
@@ -493,41 +451,40 @@ int fill_buffers(ga_ctx* c, const FillJob& j) {
         HIPCHK(hipMemsetAsync(c->dbg.p, 0, sizeof(unsigned long long) * ga::LK_DBG_WORDS * pl.nstripes, j.st));
     }
     // the lane fill's query profile (K x (m + 4) dwords: C5 1.9 MB)
-    if (j.lane() && !c->xknob("GA_LANE_QPROF_WAVE"))  // (experiments build: the profile wave builds it, for A/B)
+    if (j.lane() && !c->lk.qprof_wave)  // (experiments build: the profile wave builds it, for A/B)
         HIPCHK(c->qprof.ensure(sizeof(uint32_t) * (size_t)c->K * (size_t)(m + 4)));
     return GA_OK;
 }
 
-// The launch-time knobs of the lane kernel (tuning, A/B runs and tests: none changes the plan).
+// The launch-time knobs of the lane kernel (gaopts::LaneKnobs; tuning, A/B runs and tests: none changes the plan).
 void fill_launch_knobs(const ga_ctx* c, const FillJob& j, ga::FillArgs& p) {
+    const gaopts::LaneKnobs& lk = c->lk;
     const bool one_round = j.lane() && j.pl.nslabs <= c->num_cu;
-    auto num = [](const char* e, int unset) { return e ? atoi(e) : unset; };
     // one round of lane workgroups (every stripe resident): the chain's lag counts, read edges late
-    p.late = num(c->knob("GA_LANE_LATE"), one_round ? 1 : 0);
+    p.late = lk.late.value_or(one_round ? 1 : 0);
     // chain neighbours on one XCD (ga_lane.hip lane_slab; experiments build only): measured no faster, since ticket
     // order already keeps 165 of C3's 195 cross-workgroup links on one XCD (r5: 188 with the map; C3 fill 9.43 ->
     // 9.46 ms, tools/exp/r5/xcd.sh).  Only for one round of workgroups that runs alone (a pipeline's fills share
     // the device; a fill that finds its workgroups not all resident falls back to ticket order after ~40 us)
-    p.xcd_map = one_round && j.bd.stream == nullptr ? num(c->xknob("GA_LANE_XCD"), 0) : 0;
+    p.xcd_map = one_round && j.bd.stream == nullptr ? lk.xcd : 0;
     // measured: C4 210 ms against 221 with the direct hand-off, 1M x 125k 52.5 against 56 (r3_c4.log)
-    p.hand_direct = num(c->knob("GA_LANE_DIRECT"), 0);
-    p.lds_floor = num(c->knob("GA_FILL_LDS_FLOOR"), -1);
-    p.lane_sub = num(c->knob("GA_LANE_SUB"), -1);
-    p.lane_tb_sub = num(c->knob("GA_LANE_TB_SUB"), -1);
-    p.asm_step = num(c->knob("GA_LANE_ASM"), 1);
-    p.io_prio = num(c->xknob("GA_LANE_IOPRIO"), 0);
-    p.hand_scope = num(c->xknob("GA_LANE_HANDSCOPE"), 0);
-    p.poll_win = std::min(std::max(num(c->knob("GA_LANE_POLLWIN"), 0), 0), 192);
-    p.out_wave = num(c->knob("GA_LANE_OUTWAVE"), 1);
+    p.hand_direct = lk.hand_direct;
+    p.lds_floor = lk.lds_floor;
+    p.lane_sub = lk.lane_sub;
+    p.lane_tb_sub = lk.lane_tb_sub;
+    p.asm_step = lk.asm_step;
+    p.io_prio = lk.io_prio;
+    p.hand_scope = lk.hand_scope;
+    p.poll_win = lk.poll_win;
+    p.out_wave = lk.out_wave;
     p.spin_limit = 1u << 26;        // ~seconds: only a broken hand-off can reach it
-    p.halo_spin_limit = 1u << 30;  // waiting on another GPU may take long (~30 s)
-    if (const char* e = c->knob("GA_HALO_SPIN_LIMIT")) p.halo_spin_limit = (unsigned)std::max(1L, atol(e));  // (tests)
+    p.halo_spin_limit = lk.halo_spin_limit.value_or(1u << 30);  // waiting on another GPU may take long (~30 s)
     // a slab with a left neighbour: every wait of its fill is, in the end, a wait for that halo
     if (c->slab && c->col0 > 0) p.spin_limit = std::max(p.spin_limit, p.halo_spin_limit);
     // the lean ramp (ga_lane.hip lean0): row 0 is the reference's boundary and uniform in the shifted domain (H' = o,
     // h2' = 2o in every column: 2o + GH(j) <= big for every j, so for the largest prefix sum, which is GH(n) only
     // when no gap cost is negative); GA_LANE_LEAN0=0 keeps the masked ramp (A/B)
-    p.lean0 = num(c->knob("GA_LANE_LEAN0"), 1) && j.lane() && !c->custom && j.bd.top == nullptr && !j.bd.band &&
+    p.lean0 = lk.lean0 && j.lane() && !c->custom && j.bd.top == nullptr && !j.bd.band &&
               2 * (int64_t)c->o + c->gh_max <= (int64_t)c->big;
 }
 
@@ -574,7 +531,7 @@ ga::FillArgs fill_args(const ga_ctx* c, const FillJob& j) {
     p.qrows = pl.qrows;
     p.cols_per_lane = pl.T;
     p.dbg = c->dbg_on ? c->dbg.as<unsigned long long>() : nullptr;
-    p.qprof = j.lane() && !c->xknob("GA_LANE_QPROF_WAVE") ? c->qprof.as<uint32_t>() : nullptr;
+    p.qprof = j.lane() && !c->lk.qprof_wave ? c->qprof.as<uint32_t>() : nullptr;
     return p;
 }
 
@@ -681,83 +638,18 @@ int ga_ctx_create(int device, ga_ctx** out) { return ga_ctx_create_opts(device, 
 
 int ga_ctx_create_opts(int device, const char* options, ga_ctx** out) {
     if (!out) return fail(GA_E_ARG, "null out");
-    // the knobs, once (ga_ctx::knobs): the environment's shipped ones, then the options ("NAME=VALUE" entries
-    // separated by ';' or newlines), checked before any device work
-    std::map<std::string, std::string> knobs;
-    for (char** e = environ; e && *e; e++)
-        if (!strncmp(*e, "GA_", 3))
-            if (const char* eq = strchr(*e, '=')) {
-                std::string name(*e, (size_t)(eq - *e));
-                if (env_knob(name)) knobs[name] = eq + 1;
-            }
-    if (options) {
-        std::string s(options), item;
-        for (size_t p = 0; p <= s.size(); p++) {
-            if (p < s.size() && s[p] != ';' && s[p] != '\n') {
-                item += s[p];
-                continue;
-            }
-            if (!item.empty()) {
-                const size_t eq = item.find('=');
-                if (eq == std::string::npos || item.compare(0, 3, "GA_") != 0)
-                    return fail(GA_E_ARG, "bad option '" + item + "' (expected GA_NAME=VALUE)");
-                knobs[item.substr(0, eq)] = item.substr(eq + 1);
-            }
-            item.clear();
-        }
-    }
-    {
-        // GA_RC_EVERY: the checkpoint spacing is a power of two (a mask and a shift per iteration)
-        const auto it = knobs.find("GA_RC_EVERY");
-        if (it != knobs.end()) {
-            const long v = atol(it->second.c_str());
-            if (v < 64 || (v & (v - 1)) != 0 || v > (1L << 20))
-                return fail(GA_E_ARG, "GA_RC_EVERY must be a power of two in [64, 2^20], not '" + it->second + "'");
-        }
-    }
-    {
-        // the tables' route: a name, an item limit the generator's int32 counters hold, a word cap
-        auto it = knobs.find("GA_BATCH_RNG");
-        if (it != knobs.end() && it->second != "host" && it->second != "device")
-            return fail(GA_E_ARG, "GA_BATCH_RNG must be host or device, not '" + it->second + "'");
-        it = knobs.find("GA_BATCH_RNG_DEVICE_MAX_STEPS");
-        if (it != knobs.end() && (atoll(it->second.c_str()) < 0 || atoll(it->second.c_str()) > (1 << 20)))
-            return fail(GA_E_ARG, "GA_BATCH_RNG_DEVICE_MAX_STEPS must be in [0, 2^20], not '" + it->second + "'");
-        it = knobs.find("GA_BATCH_RNG_WORD_CAP");
-        if (it != knobs.end() && (atoll(it->second.c_str()) < 1 || atoll(it->second.c_str()) > 1024))
-            return fail(GA_E_ARG, "GA_BATCH_RNG_WORD_CAP must be in [1, 1024], not '" + it->second + "'");
-    }
-    // guard mode: options only (none is in kEnvKnobs)
-    size_t guard_bytes = 0;
-    long guard_fill = (long)gaguard::kDefaultFill;
-    bool guard_poison = false;
-    {
-        auto whole = [](const std::string& v, long long& out) {
-            char* end = nullptr;
-            out = strtoll(v.c_str(), &end, 0);
-            return !v.empty() && end && *end == 0;
-        };
-        long long v = 0;
-        auto it = knobs.find("GA_GUARD_BYTES");
-        if (it != knobs.end()) {
-            if (!whole(it->second, v) || !gaguard::valid_guard_bytes(v))
-                return fail(GA_E_ARG, "GA_GUARD_BYTES must be 0 or a multiple of 256 up to 2^20, not '" + it->second + "'");
-            guard_bytes = (size_t)v;
-        }
-        it = knobs.find("GA_GUARD_FILL");
-        if (it != knobs.end()) {
-            if (!whole(it->second, v) || !gaguard::valid_fill(v))
-                return fail(GA_E_ARG, "GA_GUARD_FILL must be a byte value in [0, 255], not '" + it->second + "'");
-            guard_fill = (long)v;
-        }
-        it = knobs.find("GA_GUARD_POISON");
-        if (it != knobs.end()) {
-            if (it->second != "0" && it->second != "1")
-                return fail(GA_E_ARG, "GA_GUARD_POISON must be 0 or 1, not '" + it->second + "'");
-            guard_poison = it->second == "1";
-            if (guard_poison && !guard_bytes) return fail(GA_E_ARG, "GA_GUARD_POISON=1 needs GA_GUARD_BYTES");
-        }
-    }
+    // the knobs, once (ga_opts.h): the environment's shipped ones, then the options, checked before any device work
+    // (an experiments build, make EXPERIMENTS=1, takes every GA_* variable and reads the dropped paths' knobs: xget)
+#ifdef GA_EXPERIMENTS
+    constexpr bool experiments = true;
+#else
+    constexpr bool experiments = false;
+#endif
+    gaopts::Map knobs;
+    gaopts::GuardOpts guard;
+    std::string why;
+    if (int r = gaopts::collect(environ, options, experiments, knobs, why)) return fail(r, why);
+    if (int r = gaopts::check(knobs, guard, why)) return fail(r, why);
     // the planner's self-test plans with the kernels' LDS formulas as ga_plan.h restates them: they must be the kernels'
     for (int every : {64, 128, 4096})
         for (int w : {1, 2, 4, 8})
@@ -771,10 +663,23 @@ int ga_ctx_create_opts(int device, const char* options, ga_ctx** out) {
     ga_ctx* c = new ga_ctx();
     c->device = device;
     c->knobs = std::move(knobs);
-    if (guard_bytes) {
-        c->guard.G = guard_bytes;
-        c->guard.fill = (uint8_t)guard_fill;
-        c->guard.poison = guard_poison;
+    // every typed knob set, parsed here and nowhere else: `get` looks a name up, `xget` one of a path that was measured
+    // and dropped, which only an experiments build (make EXPERIMENTS=1) reads
+    const auto get = [c](const char* name) -> const char* {
+        const auto it = c->knobs.find(name);
+        return it == c->knobs.end() ? nullptr : it->second.c_str();
+    };
+    const auto xget = [&get](const char* name) -> const char* { return experiments ? get(name) : nullptr; };
+    c->pk = gaplan::Knobs::parse(get, xget);
+    c->wk = gawalk::Knobs::parse(get, xget);
+    c->lk = gaopts::LaneKnobs::parse(get, xget);
+    c->bk = gaopts::BatchKnobs::parse(get, xget);
+    c->pipek = gapipe::Knobs::parse(get, xget);
+    c->pipek.diag_req = c->pk.diag_req;
+    if (guard.bytes) {
+        c->guard.G = guard.bytes;
+        c->guard.fill = (uint8_t)guard.fill;
+        c->guard.poison = guard.poison;
         guard_attach(c);
     }
     {
@@ -791,9 +696,6 @@ int ga_ctx_create_opts(int device, const char* options, ga_ctx** out) {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
             c->num_cu = cus;
-        c->pk = plan_knobs(c);
-        c->wk = gawalk::Knobs::parse([c](const char* name) { return c->knob(name); },
-                                     [c](const char* name) { return c->xknob(name); });
     }
     // The fill runs on a stream of the greatest priority.  HIP keeps a separate pool of hardware
     // queues per priority (GPU_MAX_HW_QUEUES = 4 per pool and process), so no normal-priority
@@ -802,8 +704,7 @@ int ga_ctx_create_opts(int device, const char* options, ga_ctx** out) {
     // (DESIGN.md 7).  GA_STREAM_PRIORITY=normal restores a default-priority stream (experiments).
     {
         int lo = 0, hi = 0;
-        const char* pe = c->knob("GA_STREAM_PRIORITY");
-        const bool normal = pe && !strcmp(pe, "normal");
+        const bool normal = gaopts::stream_priority_normal(get);
         if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) lo = hi = 0;
         c->priority = normal ? 0 : hi;  // 0: the default priority (lo is the LEAST, another pool)
         if (hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, c->priority) != hipSuccess) {

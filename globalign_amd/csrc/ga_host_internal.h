@@ -14,6 +14,7 @@
 #include "../../include/globalign_amd.h"
 #include "ga_device.h"
 #include "ga_guard.h"
+#include "ga_opts.h"
 #include "ga_pipe.h"
 #include "ga_plan.h"
 #include "ga_rng.h"
@@ -201,23 +202,10 @@ using garng::RngTable;
 
 struct ga_ctx {
     // GA_* tuning / diagnostic overrides, snapshotted when the context is created (ga_ctx_create_opts): the
-    // environment's shipped knobs (kEnvKnobs) at that moment, then the caller's options.  A context's kernel choices
-    // never change under it, whatever the process does to its environment later (nullptr: unset).
-    std::map<std::string, std::string> knobs;
-    const char* knob(const char* name) const {
-        const auto it = knobs.find(name);
-        return it == knobs.end() ? nullptr : it->second.c_str();
-    }
-    // knobs of paths that were measured and dropped: read only by an experiments build
-    // (make EXPERIMENTS=1); the shipped library ignores them
-    const char* xknob(const char* name) const {
-#ifdef GA_EXPERIMENTS
-        return knob(name);
-#else
-        (void)name;
-        return nullptr;
-#endif
-    }
+    // environment's shipped knobs (gaopts::kEnvKnobs) at that moment, then the caller's options.  A context's kernel choices
+    // never change under it, whatever the process does to its environment later.  Read once, there, into the typed
+    // sets below (pk, wk, lk, bk, pipek); kept because pipek.trace points into it.
+    gaopts::Map knobs;
     int device = 0;
     int priority = 0;  // of `stream` (the greatest the device offers, see ga_ctx_create)
     hipStream_t stream = nullptr;
@@ -238,8 +226,11 @@ struct ga_ctx {
     hipEvent_t ev_fill = nullptr, ev_res = nullptr;
     bool rc_pos_zeroed = false;  // rc_pos was cleared on the fill's stream before the fill (rc_align)
     int qrows = 1024, num_cu = 256;  // the row scan's query-profile ring (load_problem)
-    gaplan::Knobs pk;          // the planner's knobs, parsed once (plan_knobs)
+    gaplan::Knobs pk;          // the planner's knobs, parsed once (ga_plan.h)
     gawalk::Knobs wk;          // the traceback call's, parsed once (ga_walk_plan.h)
+    gaopts::LaneKnobs lk;      // the lane fill's launch knobs and the batched calls', parsed once (ga_opts.h)
+    gaopts::BatchKnobs bk;
+    gapipe::Knobs pipek;       // the pipeline's, parsed once (ga_pipe.h), diag_req copied in from pk
     // the last enqueued fill's plan (ga_plan.h): kernel, geometry, checkpoint spacing; before the first fill the
     // loaded problem's row-scan geometry
     gaplan::FillPlan plan;

@@ -8,11 +8,15 @@
 //     pin (profiles/r06, DESIGN.md 5.2 / 5.6 / 5.8.1, tests/test_gpu_rc_default_width.py), and every error return;
 //   * the traceback call's pure part (ga_walk_plan.h): its knobs' defaults and clamps, the recompute walk's eligibility,
 //     the banded traceback's rows, the recompute window's invariants and its default tables, workers per workgroup;
-//   * the guard bands' layout, scan and report (ga_guard.h) on a host model of a guarded buffer.
+//   * the guard bands' layout, scan and report (ga_guard.h) on a host model of a guarded buffer;
+//   * a context's options (ga_opts.h): which of the environment's variables land in the knob map, the option string's
+//     split, every range check with its text, and the typed knob sets' defaults and clamps (gaopts::LaneKnobs,
+//     gaopts::BatchKnobs, gaplan::Knobs::parse).
 // No HIP: the engine's library is tested on the GPU; this binary covers the host logic under the sanitizers.
 //
 //   ga_host_selftest            all checks; exit status 0 when every one passes
 //   ga_host_selftest bench S    time the table for S dispatches
+//   ga_host_selftest envknobs   the GA_* names the shipped library reads from the environment, one per line
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -24,6 +28,7 @@
 #include "ga_batch.h"
 #include "ga_check.h"
 #include "ga_guard.h"
+#include "ga_opts.h"
 #include "ga_plan.h"
 #include "ga_rng.h"
 #include "ga_walk_plan.h"
@@ -617,14 +622,16 @@ void test_guard() {
 using KnobMap = std::map<std::string, std::string>;
 
 // the knobs of `kv` as a context would parse them: in an experiments build (xknobs) xget sees what get sees
-gawalk::Knobs walk_knobs(const KnobMap& kv, bool xknobs = false) {
+template <typename K>
+K parse_knobs(const KnobMap& kv, bool xknobs = false) {
     auto get = [&kv](const char* name) -> const char* {
         const auto it = kv.find(name);
         return it == kv.end() ? nullptr : it->second.c_str();
     };
     auto none = [](const char*) -> const char* { return nullptr; };
-    return xknobs ? gawalk::Knobs::parse(get, get) : gawalk::Knobs::parse(get, none);
+    return xknobs ? K::parse(get, get) : K::parse(get, none);
 }
+gawalk::Knobs walk_knobs(const KnobMap& kv, bool xknobs = false) { return parse_knobs<gawalk::Knobs>(kv, xknobs); }
 
 void test_walk_knobs() {
     {
@@ -820,6 +827,284 @@ void test_walk_window() {
     }
 }
 
+// ---------------------------------------------------------------- a context's options (ga_opts.h)
+// collect() over an environ-style array of `env` and the option string `opts` (nullptr: none)
+struct Collected {
+    int rc;
+    KnobMap kv;
+    std::string why;
+};
+Collected collect(const std::vector<std::string>& env, const char* opts, bool experiments = false) {
+    std::vector<const char*> envp;
+    for (const std::string& e : env) envp.push_back(e.c_str());
+    envp.push_back(nullptr);
+    Collected c;
+    c.rc = gaopts::collect(envp.data(), opts, experiments, c.kv, c.why);
+    return c;
+}
+
+void test_opts_collect() {
+    // what a process may have around a shipped knob: an option-only knob, a fault injector, a name without a value,
+    // a variable of somebody else's
+    const std::vector<std::string> strays = {"GA_GUARD_BYTES=100", "GA_RC_TAG_FAULT=3", "GA_NOVALUE", "PATH=/bin", "XGA_RC=1"};
+    std::vector<std::string> all = strays;
+    int nk = 0;
+    for (const char* k : gaopts::kEnvKnobs) {
+        std::vector<std::string> env = strays;
+        const std::string val = "v" + std::to_string(nk++);
+        env.insert(env.begin() + 2, std::string(k) + "=" + val);
+        all.push_back(std::string(k) + "=" + val);
+        const Collected ship = collect(env, nullptr), xb = collect(env, nullptr, true);
+        CHECK(ship.rc == GA_OK && ship.kv == (KnobMap{{k, val}}), "%s from the environment: %zu knobs", k, ship.kv.size());
+        CHECK(xb.rc == GA_OK && xb.kv == (KnobMap{{k, val}, {"GA_GUARD_BYTES", "100"}, {"GA_RC_TAG_FAULT", "3"}}),
+              "%s from the environment of an experiments build: %zu knobs", k, xb.kv.size());
+        CHECK(gaopts::env_knob(k, false) && gaopts::env_knob(k, true), "env_knob(%s)", k);
+    }
+    CHECK(nk == 14 && collect(all, nullptr).kv.size() == 14 && collect(all, nullptr, true).kv.size() == 16, "%d shipped knobs", nk);
+    struct Rule { const char* name; bool ship, xb; };
+    for (const Rule& r : {Rule{"GA_GUARD_BYTES", false, true}, Rule{"GA_RC_", false, true}, Rule{"GA_", false, true},
+                          Rule{"PATH", false, false}, Rule{"ga_rc", false, false}, Rule{"", false, false}})
+        CHECK(gaopts::env_knob(r.name, false) == r.ship && gaopts::env_knob(r.name, true) == r.xb, "env_knob's two rules on '%s'", r.name);
+    {
+        KnobMap kv;
+        std::string why;
+        CHECK(gaopts::collect(nullptr, nullptr, false, kv, why) == GA_OK && kv.empty() && why.empty(), "no environment, no options");
+        CHECK(collect({}, nullptr).rc == GA_OK && collect({"GA_RC=1"}, nullptr).kv == (KnobMap{{"GA_RC", "1"}}), "options == nullptr");
+    }
+    {
+        // options override the environment, a later option an earlier one; a value keeps its '=' and may be empty
+        const Collected c = collect({"GA_RC=0", "GA_RC_SERVERS=48", "GA_PIPE_TRACE=/tmp/a=b"}, "GA_RC=1;GA_X=a=b;GA_Y=;GA_Z=1;GA_Z=2");
+        CHECK(c.rc == GA_OK && c.kv == (KnobMap{{"GA_RC", "1"}, {"GA_RC_SERVERS", "48"}, {"GA_PIPE_TRACE", "/tmp/a=b"},
+                                                {"GA_X", "a=b"}, {"GA_Y", ""}, {"GA_Z", "2"}}),
+              "precedence and '=' in values: %zu knobs (%s)", c.kv.size(), c.why.c_str());
+        // an option may name what the environment may not
+        const Collected g = collect({"GA_GUARD_BYTES=100"}, "GA_GUARD_BYTES=0");
+        CHECK(g.rc == GA_OK && g.kv == (KnobMap{{"GA_GUARD_BYTES", "0"}}), "an option-only knob");
+    }
+    {
+        // both separators, empty items, trailing separators
+        const KnobMap want = {{"GA_A", "1"}, {"GA_B", "2"}, {"GA_C", "3"}, {"GA_D", "4"}};
+        for (const char* opts : {"GA_A=1;GA_B=2;GA_C=3;GA_D=4", "GA_A=1\nGA_B=2\nGA_C=3\nGA_D=4\n", ";;GA_A=1;\nGA_B=2\n\n;GA_C=3;;GA_D=4;\n;"}) {
+            const Collected c = collect({}, opts);
+            CHECK(c.rc == GA_OK && c.kv == want, "separators in '%s': %zu knobs (%s)", opts, c.kv.size(), c.why.c_str());
+        }
+        for (const char* opts : {"", ";", "\n", ";\n;;"}) CHECK(collect({}, opts).rc == GA_OK && collect({}, opts).kv.empty(), "empty options");
+        // (a space is no separator: it belongs to the value)
+        CHECK(collect({}, "GA_A=1 GA_B=2").kv == (KnobMap{{"GA_A", "1 GA_B=2"}}), "a space inside a value");
+    }
+    // the two malformed forms, wherever they stand
+    struct Bad { const char* opts; const char* why; };
+    for (const Bad& b : {Bad{"GA_RC", "bad option 'GA_RC' (expected GA_NAME=VALUE)"},
+                         Bad{"RC=1", "bad option 'RC=1' (expected GA_NAME=VALUE)"},
+                         Bad{"GA_RC=1;FOO=2;GA_RC_EVERY=64", "bad option 'FOO=2' (expected GA_NAME=VALUE)"},
+                         Bad{"GA_RC=1\nGA_RC_EVERY\n", "bad option 'GA_RC_EVERY' (expected GA_NAME=VALUE)"},
+                         Bad{" GA_RC=1", "bad option ' GA_RC=1' (expected GA_NAME=VALUE)"},
+                         Bad{"ga_rc=1", "bad option 'ga_rc=1' (expected GA_NAME=VALUE)"}}) {
+        const Collected c = collect({}, b.opts);
+        CHECK(c.rc == GA_E_ARG && c.why == b.why, "options '%s': %d (%s)", b.opts, c.rc, c.why.c_str());
+    }
+}
+
+void test_opts_check() {
+    struct Case { KnobMap kv; const char* why; };  // why: nullptr when the options are accepted
+    const std::string p20 = std::to_string(1 << 20), p21 = std::to_string(1 << 21);
+    const Case cases[] = {
+        {{}, nullptr},
+        {{{"GA_RC_EVERY", "63"}}, "GA_RC_EVERY must be a power of two in [64, 2^20], not '63'"},
+        {{{"GA_RC_EVERY", "64"}}, nullptr},
+        {{{"GA_RC_EVERY", "96"}}, "GA_RC_EVERY must be a power of two in [64, 2^20], not '96'"},
+        {{{"GA_RC_EVERY", p20}}, nullptr},
+        {{{"GA_RC_EVERY", p21}}, "GA_RC_EVERY must be a power of two in [64, 2^20], not '2097152'"},
+        {{{"GA_RC_EVERY", "many"}}, "GA_RC_EVERY must be a power of two in [64, 2^20], not 'many'"},
+        {{{"GA_BATCH_RNG", "host"}}, nullptr},
+        {{{"GA_BATCH_RNG", "device"}}, nullptr},
+        {{{"GA_BATCH_RNG", "gpu"}}, "GA_BATCH_RNG must be host or device, not 'gpu'"},
+        {{{"GA_BATCH_RNG_DEVICE_MAX_STEPS", "-1"}}, "GA_BATCH_RNG_DEVICE_MAX_STEPS must be in [0, 2^20], not '-1'"},
+        {{{"GA_BATCH_RNG_DEVICE_MAX_STEPS", "0"}}, nullptr},
+        {{{"GA_BATCH_RNG_DEVICE_MAX_STEPS", p20}}, nullptr},
+        {{{"GA_BATCH_RNG_DEVICE_MAX_STEPS", "1048577"}}, "GA_BATCH_RNG_DEVICE_MAX_STEPS must be in [0, 2^20], not '1048577'"},
+        {{{"GA_BATCH_RNG_WORD_CAP", "0"}}, "GA_BATCH_RNG_WORD_CAP must be in [1, 1024], not '0'"},
+        {{{"GA_BATCH_RNG_WORD_CAP", "1"}}, nullptr},
+        {{{"GA_BATCH_RNG_WORD_CAP", "1024"}}, nullptr},
+        {{{"GA_BATCH_RNG_WORD_CAP", "1025"}}, "GA_BATCH_RNG_WORD_CAP must be in [1, 1024], not '1025'"},
+        // tests/test_gpu_guard.py test_guard_options_are_checked's eight
+        {{{"GA_GUARD_BYTES", "100"}}, "GA_GUARD_BYTES must be 0 or a multiple of 256 up to 2^20, not '100'"},
+        {{{"GA_GUARD_BYTES", "4097"}}, "GA_GUARD_BYTES must be 0 or a multiple of 256 up to 2^20, not '4097'"},
+        {{{"GA_GUARD_BYTES", "-256"}}, "GA_GUARD_BYTES must be 0 or a multiple of 256 up to 2^20, not '-256'"},
+        {{{"GA_GUARD_BYTES", "1048832"}}, "GA_GUARD_BYTES must be 0 or a multiple of 256 up to 2^20, not '1048832'"},
+        {{{"GA_GUARD_BYTES", "4k"}}, "GA_GUARD_BYTES must be 0 or a multiple of 256 up to 2^20, not '4k'"},
+        {{{"GA_GUARD_BYTES", "256"}, {"GA_GUARD_FILL", "256"}}, "GA_GUARD_FILL must be a byte value in [0, 255], not '256'"},
+        {{{"GA_GUARD_POISON", "1"}}, "GA_GUARD_POISON=1 needs GA_GUARD_BYTES"},
+        {{{"GA_GUARD_BYTES", "256"}, {"GA_GUARD_POISON", "2"}}, "GA_GUARD_POISON must be 0 or 1, not '2'"},
+        // whole(): a number and nothing else
+        {{{"GA_GUARD_BYTES", ""}}, "GA_GUARD_BYTES must be 0 or a multiple of 256 up to 2^20, not ''"},
+        {{{"GA_GUARD_BYTES", "256"}, {"GA_GUARD_FILL", ""}}, "GA_GUARD_FILL must be a byte value in [0, 255], not ''"},
+        {{{"GA_GUARD_BYTES", "256"}, {"GA_GUARD_FILL", "-1"}}, "GA_GUARD_FILL must be a byte value in [0, 255], not '-1'"},
+        {{{"GA_GUARD_BYTES", "256"}, {"GA_GUARD_FILL", "0x3c "}}, "GA_GUARD_FILL must be a byte value in [0, 255], not '0x3c '"},
+        {{{"GA_GUARD_BYTES", "0"}, {"GA_GUARD_POISON", "1"}}, "GA_GUARD_POISON=1 needs GA_GUARD_BYTES"},
+        {{{"GA_GUARD_POISON", "0"}}, nullptr},
+        {{{"GA_GUARD_POISON", ""}}, "GA_GUARD_POISON must be 0 or 1, not ''"},
+        // today's order: the spacing, the tables' route, the guards
+        {{{"GA_GUARD_BYTES", "100"}, {"GA_BATCH_RNG", "gpu"}, {"GA_RC_EVERY", "96"}}, "GA_RC_EVERY must be a power of two in [64, 2^20], not '96'"},
+        {{{"GA_GUARD_BYTES", "100"}, {"GA_BATCH_RNG_WORD_CAP", "0"}, {"GA_BATCH_RNG", "gpu"}}, "GA_BATCH_RNG must be host or device, not 'gpu'"},
+        {{{"GA_GUARD_BYTES", "100"}, {"GA_BATCH_RNG_WORD_CAP", "0"}, {"GA_BATCH_RNG_DEVICE_MAX_STEPS", "-1"}},
+         "GA_BATCH_RNG_DEVICE_MAX_STEPS must be in [0, 2^20], not '-1'"},
+        {{{"GA_GUARD_BYTES", "100"}, {"GA_BATCH_RNG_WORD_CAP", "0"}}, "GA_BATCH_RNG_WORD_CAP must be in [1, 1024], not '0'"},
+        {{{"GA_GUARD_BYTES", "100"}, {"GA_GUARD_FILL", "256"}, {"GA_GUARD_POISON", "2"}},
+         "GA_GUARD_BYTES must be 0 or a multiple of 256 up to 2^20, not '100'"},
+        // names nobody reads are nobody's to refuse
+        {{{"GA_NO_SUCH_KNOB", "1"}, {"GA_RC", "many"}}, nullptr},
+    };
+    for (const Case& cs : cases) {
+        std::string desc, why;
+        for (const auto& [k, v] : cs.kv) desc += k + "=" + v + ";";
+        gaopts::GuardOpts g;
+        const int rc = gaopts::check(cs.kv, g, why);
+        if (cs.why) CHECK(rc == GA_E_ARG && why == cs.why, "options %s: %d (%s)", desc.c_str(), rc, why.c_str());
+        else CHECK(rc == GA_OK && why.empty(), "options %s refused: %d (%s)", desc.c_str(), rc, why.c_str());
+    }
+    {
+        gaopts::GuardOpts g;
+        std::string why;
+        CHECK(gaopts::check({}, g, why) == GA_OK && g.bytes == 0 && g.fill == 0xA5 && !g.poison, "guard mode is off by default");
+        CHECK(gaopts::check({{"GA_GUARD_BYTES", "1048576"}, {"GA_GUARD_FILL", "0x3c"}, {"GA_GUARD_POISON", "1"}}, g, why) == GA_OK &&
+                  g.bytes == (size_t)1 << 20 && g.fill == 0x3c && g.poison,
+              "the guard triple: %zu bytes, fill %ld, poison %d (%s)", g.bytes, g.fill, (int)g.poison, why.c_str());
+        CHECK(gaopts::check({{"GA_GUARD_BYTES", "0x100"}, {"GA_GUARD_FILL", "255"}, {"GA_GUARD_POISON", "0"}}, g, why) == GA_OK &&
+                  g.bytes == 256 && g.fill == 255 && !g.poison,
+              "guard options in hex and decimal");
+        CHECK(gaopts::check({{"GA_GUARD_BYTES", "0"}, {"GA_GUARD_FILL", "0"}}, g, why) == GA_OK && g.bytes == 0 && g.fill == 0, "guards off");
+    }
+}
+
+// one knob's values as given, and what the field holds for each
+template <typename K>
+struct IntKnob { const char* name; int K::*field; bool x; int in[5], out[5]; };
+template <typename K, size_t N>
+void check_int_knobs(const IntKnob<K> (&knobs)[N]) {
+    for (const IntKnob<K>& kb : knobs) {
+        const K unset;
+        for (int k = 0; k < 5; k++) {
+            const K kn = parse_knobs<K>({{kb.name, std::to_string(kb.in[k])}}, kb.x);
+            CHECK(kn.*kb.field == kb.out[k], "%s=%d parsed as %d, expected %d", kb.name, kb.in[k], kn.*kb.field, kb.out[k]);
+            // a dropped path's knob: the shipped build does not see it
+            if (kb.x) CHECK(parse_knobs<K>({{kb.name, std::to_string(kb.in[k])}}).*kb.field == unset.*kb.field, "shipped build read %s", kb.name);
+        }
+        CHECK(parse_knobs<K>({{kb.name, "junk"}}, kb.x).*kb.field == parse_knobs<K>({{kb.name, "0"}}, kb.x).*kb.field, "%s=junk is 0", kb.name);
+    }
+}
+
+void test_lane_knobs() {
+    using gaopts::LaneKnobs;
+    for (bool x : {false, true}) {
+        const LaneKnobs kn = parse_knobs<LaneKnobs>({}, x);
+        CHECK(!kn.late && kn.xcd == 0 && kn.hand_direct == 0 && kn.lds_floor == -1 && kn.lane_sub == -1 && kn.lane_tb_sub == -1 &&
+                  kn.asm_step == 1 && kn.io_prio == 0 && kn.hand_scope == 0 && kn.poll_win == 0 && kn.out_wave == 1 &&
+                  !kn.halo_spin_limit && kn.lean0 == 1 && !kn.rc_fail_alloc && !kn.qprof_wave,
+              "GA_LANE_* defaults");
+    }
+    const IntKnob<LaneKnobs> knobs[] = {
+        {"GA_LANE_XCD", &LaneKnobs::xcd, true, {-1, 0, 1, 2, 9}, {-1, 0, 1, 2, 9}},
+        {"GA_LANE_DIRECT", &LaneKnobs::hand_direct, false, {-1, 0, 1, 2, 9}, {-1, 0, 1, 2, 9}},
+        {"GA_FILL_LDS_FLOOR", &LaneKnobs::lds_floor, false, {-1, 0, 1, 40000, 163840}, {-1, 0, 1, 40000, 163840}},
+        {"GA_LANE_SUB", &LaneKnobs::lane_sub, false, {-1, 0, 1, 2, 9}, {-1, 0, 1, 2, 9}},
+        {"GA_LANE_TB_SUB", &LaneKnobs::lane_tb_sub, false, {-1, 0, 1, 2, 9}, {-1, 0, 1, 2, 9}},
+        {"GA_LANE_ASM", &LaneKnobs::asm_step, false, {-1, 0, 1, 2, 9}, {-1, 0, 1, 2, 9}},
+        {"GA_LANE_IOPRIO", &LaneKnobs::io_prio, true, {-1, 0, 1, 2, 3}, {-1, 0, 1, 2, 3}},
+        {"GA_LANE_HANDSCOPE", &LaneKnobs::hand_scope, true, {-1, 0, 1, 2, 3}, {-1, 0, 1, 2, 3}},
+        {"GA_LANE_POLLWIN", &LaneKnobs::poll_win, false, {-1, 0, 64, 192, 193}, {0, 0, 64, 192, 192}},
+        {"GA_LANE_OUTWAVE", &LaneKnobs::out_wave, false, {-1, 0, 1, 2, 9}, {-1, 0, 1, 2, 9}},
+        {"GA_LANE_LEAN0", &LaneKnobs::lean0, false, {-1, 0, 1, 2, 9}, {-1, 0, 1, 2, 9}},
+    };
+    check_int_knobs(knobs);
+    for (const auto& [in, out] : {std::pair<const char*, int>{"0", 0}, {"1", 1}, {"-3", -3}, {"junk", 0}}) {
+        const LaneKnobs kn = parse_knobs<LaneKnobs>({{"GA_LANE_LATE", in}});
+        CHECK(kn.late && *kn.late == out, "GA_LANE_LATE=%s", in);
+    }
+    for (const auto& [in, out] : {std::pair<const char*, unsigned>{"-5", 1u}, {"0", 1u}, {"1", 1u}, {"1000", 1000u}, {"1073741824", 1u << 30}}) {
+        const LaneKnobs kn = parse_knobs<LaneKnobs>({{"GA_HALO_SPIN_LIMIT", in}});
+        CHECK(kn.halo_spin_limit && *kn.halo_spin_limit == out, "GA_HALO_SPIN_LIMIT=%s", in);
+    }
+    for (const auto& [in, out] : {std::pair<const char*, bool>{"0", false}, {"1", true}, {"2", false}, {"-1", false}, {"yes", false}})
+        CHECK(parse_knobs<LaneKnobs>({{"GA_RC_FAIL_ALLOC", in}}).rc_fail_alloc == out, "GA_RC_FAIL_ALLOC=%s", in);
+    // set by presence, and an experiments build's alone
+    CHECK(parse_knobs<LaneKnobs>({{"GA_LANE_QPROF_WAVE", "0"}}, true).qprof_wave && !parse_knobs<LaneKnobs>({{"GA_LANE_QPROF_WAVE", "1"}}).qprof_wave,
+          "GA_LANE_QPROF_WAVE");
+    auto get_of = [](const KnobMap& kv) {
+        return [kv](const char* name) -> const char* {
+            const auto it = kv.find(name);
+            return it == kv.end() ? nullptr : it->second.c_str();
+        };
+    };
+    CHECK(!gaopts::stream_priority_normal(get_of({})) && gaopts::stream_priority_normal(get_of({{"GA_STREAM_PRIORITY", "normal"}})) &&
+              !gaopts::stream_priority_normal(get_of({{"GA_STREAM_PRIORITY", "high"}})) &&
+              !gaopts::stream_priority_normal(get_of({{"GA_STREAM_PRIORITY", ""}})),
+          "GA_STREAM_PRIORITY=normal and nothing else");
+}
+
+void test_batch_knobs() {
+    using gaopts::BatchKnobs;
+    for (bool x : {false, true}) {  // (no knob of a dropped path among them: both builds read the same)
+        const BatchKnobs kn = parse_knobs<BatchKnobs>({}, x);
+        CHECK(!kn.rng_device_default && kn.rng_max_steps == 1024 && kn.rng_cap_words == 48 && kn.rng_threads == 0 && !kn.max_cells &&
+                  !kn.align_max_cells && !kn.sample_chunk_words && !kn.sample_walk_entries,
+              "GA_BATCH_* defaults");
+    }
+    const IntKnob<BatchKnobs> knobs[] = {
+        {"GA_BATCH_RNG_WORD_CAP", &BatchKnobs::rng_cap_words, false, {1, 2, 48, 1000, 1024}, {1, 2, 48, 1000, 1024}},
+        {"GA_BATCH_RNG_THREADS", &BatchKnobs::rng_threads, false, {-2, 0, 1, 8, 500}, {-2, 0, 1, 8, 500}},
+    };
+    check_int_knobs(knobs);
+    CHECK(parse_knobs<BatchKnobs>({{"GA_BATCH_RNG", "device"}}).rng_device_default && !parse_knobs<BatchKnobs>({{"GA_BATCH_RNG", "host"}}).rng_device_default,
+          "GA_BATCH_RNG");
+    for (int64_t v : {(int64_t)0, (int64_t)1, (int64_t)1024, (int64_t)1 << 20})
+        CHECK(parse_knobs<BatchKnobs>({{"GA_BATCH_RNG_DEVICE_MAX_STEPS", std::to_string(v)}}).rng_max_steps == v,
+              "GA_BATCH_RNG_DEVICE_MAX_STEPS=%lld", (long long)v);
+    struct Floor { const char* name; std::optional<int64_t> BatchKnobs::*field; int64_t floor; };
+    for (const Floor& f : {Floor{"GA_BATCH_MAX_CELLS", &BatchKnobs::max_cells, 0}, Floor{"GA_BATCH_ALIGN_MAX_CELLS", &BatchKnobs::align_max_cells, 0},
+                           Floor{"GA_BATCH_SAMPLE_CHUNK_WORDS", &BatchKnobs::sample_chunk_words, 1},
+                           Floor{"GA_BATCH_SAMPLE_WALK_ENTRIES", &BatchKnobs::sample_walk_entries, 1}})
+        for (int64_t v : {(int64_t)-7, (int64_t)-1, (int64_t)0, (int64_t)1, (int64_t)2, (int64_t)5000000000LL}) {
+            const BatchKnobs kn = parse_knobs<BatchKnobs>({{f.name, std::to_string(v)}});
+            const std::optional<int64_t>& got = kn.*f.field;
+            CHECK(got && *got == std::max(v, f.floor), "%s=%lld", f.name, (long long)v);
+            // each name fills its own field and no other
+            int set = 0;
+            for (const auto* o : {&kn.max_cells, &kn.align_max_cells, &kn.sample_chunk_words, &kn.sample_walk_entries}) set += o->has_value();
+            CHECK(set == 1, "%s set %d fields", f.name, set);
+        }
+}
+
+void test_plan_knobs() {
+    using gaplan::Knobs;
+    for (bool x : {false, true}) {
+        const Knobs kn = parse_knobs<Knobs>({}, x), unset;
+        CHECK(kn.T_req == 0 && kn.nwc_req == 0 && kn.diag_req == 0 && kn.lane_T_req == 0 && kn.diag_T_req == 0 && kn.lane_wg_per_cu == 1 &&
+                  kn.lane_qrows == 4096 && kn.rc_narrow && kn.rc_budget == (int64_t)96 << 30 && kn.rc_jump == gaplan::kRcJumpDefault &&
+                  kn.dev_avail == unset.dev_avail,
+              "the planner's defaults");
+    }
+    const IntKnob<Knobs> knobs[] = {
+        {"GA_COLS_PER_LANE", &Knobs::T_req, false, {-1, 0, 1, 4, 8}, {-1, 0, 1, 4, 8}},
+        {"GA_FILL_NWC", &Knobs::nwc_req, false, {-1, 0, 4, 8, 16}, {-1, 0, 4, 8, 16}},
+        {"GA_LANE_COLS_PER_LANE", &Knobs::lane_T_req, false, {-1, 0, 1, 4, 8}, {-1, 0, 1, 4, 8}},
+        {"GA_DIAG_COLS_PER_LANE", &Knobs::diag_T_req, false, {-1, 0, 1, 4, 8}, {-1, 0, 1, 4, 8}},
+        {"GA_LANE_WG_PER_CU", &Knobs::lane_wg_per_cu, false, {-1, 0, 1, 2, 3}, {1, 1, 1, 2, 2}},
+        {"GA_LANE_QROWS", &Knobs::lane_qrows, false, {0, 64, 1024, 4096, 8192}, {0, 64, 1024, 4096, 8192}},
+    };
+    check_int_knobs(knobs);
+    for (const auto& [in, out] : {std::pair<const char*, int>{"row", 1}, {"diag", 2}, {"lane", 3}, {"auto", 0}, {"", 0}, {"Row", 0}})
+        CHECK(parse_knobs<Knobs>({{"GA_FILL_MODE", in}}).diag_req == out, "GA_FILL_MODE=%s", in);
+    for (const auto& [in, out] : {std::pair<const char*, bool>{"0", false}, {"1", true}, {"2", true}, {"junk", false}})
+        CHECK(parse_knobs<Knobs>({{"GA_RC_NARROW", in}}).rc_narrow == out, "GA_RC_NARROW=%s", in);
+    for (int64_t mb : {(int64_t)0, (int64_t)1, (int64_t)98304, (int64_t)300000})
+        CHECK(parse_knobs<Knobs>({{"GA_RC_BUDGET_MB", std::to_string(mb)}}).rc_budget == mb << 20, "GA_RC_BUDGET_MB=%lld", (long long)mb);
+    // the tie-to-tie walk is an experiments build's to ask for
+    CHECK(!parse_knobs<Knobs>({{"GA_RC_JUMP", "1"}}).rc_jump && parse_knobs<Knobs>({{"GA_RC_JUMP", "1"}}, true).rc_jump &&
+              !parse_knobs<Knobs>({{"GA_RC_JUMP", "0"}}, true).rc_jump,
+          "GA_RC_JUMP");
+}
+
 double ms_since(std::chrono::steady_clock::time_point t) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
 }
@@ -844,6 +1129,10 @@ int main(int argc, char** argv) {
         std::printf("twists alone (%lld): %.3f ms (%u)\n", (long long)tw, ms_since(t0), g.mt[5]);
         return 0;
     }
+    if (argc >= 2 && std::string(argv[1]) == "envknobs") {
+        for (const char* k : gaopts::kEnvKnobs) std::printf("%s\n", k);
+        return 0;
+    }
     for (uint64_t seed = 1; seed <= 12; seed++) {
         const int64_t steps = seed <= 6 ? (int64_t)(seed * seed * 37) : (int64_t)(seed * 2111);
         test_table(seed, steps);
@@ -858,6 +1147,11 @@ int main(int argc, char** argv) {
     test_walk_paths();
     test_walk_window();
     test_guard();
+    test_opts_collect();
+    test_opts_check();
+    test_lane_knobs();
+    test_batch_knobs();
+    test_plan_knobs();
     if (failures) {
         std::fprintf(stderr, "%d check(s) failed\n", failures);
         return 1;

@@ -23,8 +23,9 @@ constexpr int kChainSlots = 6;  // ga::WALK_CHAIN_SLOTS (ga_pipe_host.cpp assert
 
 enum Mode { kAuto = 0, kRow = 1, kLane = 2 };
 
-// The pipeline's knobs, parsed here and nowhere else: `get` looks a shipped knob up, `xget` one of a path that was
-// measured and dropped (ga_ctx::knob / ga_ctx::xknob: the shipped build's sees nothing); nullptr for an unset name.
+// The pipeline's knobs, parsed here and nowhere else, once per context (ga_ctx::pipek): `get` looks a shipped knob up,
+// `xget` one of a path that was measured and dropped (ga_ctx_create_opts' two look-ups: the shipped build's xget sees
+// nothing); nullptr for an unset name.
 struct Knobs {
     int mode = kAuto;                // GA_PIPE_MODE=row|lane
     std::optional<int> fills;        // GA_PIPE_FILLS (2..4)
@@ -34,7 +35,7 @@ struct Knobs {
     bool fill_prio_normal = false;   // ... to "normal": the fills on default-priority streams
     bool fixed_order = false;        // GA_PIPE_SLOT_ORDER=fixed: walk k takes slot k % S
     bool pinned_io = true;           // GA_PIPE_PINNED_IO=0: walk results and levels in device memory
-    const char* trace = nullptr;     // GA_PIPE_TRACE=<file> (the caller's string)
+    const char* trace = nullptr;     // GA_PIPE_TRACE=<file> (the caller's string: ga_ctx::knobs keeps it alive)
     int walk_cus = 0;                // (experiments) GA_PIPE_WALK_CUS, 0..8
     std::optional<int> row_first;    // (experiments) GA_PIPE_ROW_FIRST
     int diag_req = 0;                // gaplan::Knobs::diag_req (GA_FILL_MODE), which the caller copies in

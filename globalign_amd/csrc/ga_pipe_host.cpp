@@ -427,9 +427,7 @@ int problem_align_many(ga_ctx* c, int32_t count, uint32_t* mt_state, const char*
     if (!mt_state || !a_chr || !b_chr || !oa || !om || !ob || !out_len || !tb_status || !cost_out)
         return fail(GA_E_ARG, "null argument");
     if (!c->loaded) return fail(GA_E_STATE, "no problem loaded");
-    gapipe::Knobs kn = gapipe::Knobs::parse([c](const char* name) { return c->knob(name); },
-                                            [c](const char* name) { return c->xknob(name); });
-    kn.diag_req = c->pk.diag_req;
+    const gapipe::Knobs& kn = c->pipek;
     c->pipe.plan = gapipe::plan(plan_problem(c), kn, c->hw_queues, count, count == 1 ? 0 : band_rows(c));
     if (c->pipe.plan.serial) {
         const double t0 = now_ms();

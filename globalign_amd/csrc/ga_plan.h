@@ -6,6 +6,8 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 
@@ -44,7 +46,10 @@ struct Request {
     int lane_td = 0, lane_nwc = 0;
 };
 
-// The knobs the choice reads, as numbers (ga_host.cpp plan_knobs parses them once per context).
+constexpr bool kRcJumpDefault = false;  // the tie-to-tie walk unless GA_RC_JUMP says otherwise
+
+// The knobs the choice reads, as numbers: parsed here and nowhere else, once per context (ga_ctx::pk), as
+// gawalk::Knobs is: `get` looks a shipped knob up, `xget` one of a path that was measured and dropped.
 struct Knobs {
     int T_req = 0, nwc_req = 0;  // GA_COLS_PER_LANE, GA_FILL_NWC (0: automatic)
     int diag_req = 0;            // GA_FILL_MODE: 0 automatic, 1 row scan, 2 anti-diagonal, 3 lane-skewed
@@ -58,6 +63,24 @@ struct Knobs {
     int64_t rc_budget = (int64_t)96 << 30;  // GA_RC_BUDGET_MB, in bytes
     bool rc_jump = false;        // the tie-to-tie walk is requested (experiments build): its cache is budgeted
     int64_t dev_avail = INT64_MAX / 4;  // device memory the recompute fill's checkpoints may take (dev_avail_bytes)
+    template <typename Get, typename XGet>
+    static Knobs parse(Get&& get, XGet&& xget) {
+        Knobs kn;
+        if (const char* e = get("GA_COLS_PER_LANE")) kn.T_req = atoi(e);  // tuning overrides
+        if (const char* e = get("GA_FILL_NWC")) kn.nwc_req = atoi(e);
+        if (const char* e = get("GA_FILL_MODE"))
+            kn.diag_req = !strcmp(e, "diag") ? 2 : !strcmp(e, "row") ? 1 : !strcmp(e, "lane") ? 3 : 0;
+        if (const char* e = get("GA_LANE_COLS_PER_LANE")) kn.lane_T_req = atoi(e);
+        if (const char* e = get("GA_DIAG_COLS_PER_LANE")) kn.diag_T_req = atoi(e);
+        if (const char* e = get("GA_LANE_WG_PER_CU")) kn.lane_wg_per_cu = std::max(1, std::min(2, atoi(e)));
+        if (const char* e = get("GA_LANE_QROWS")) kn.lane_qrows = atoi(e);
+        if (const char* e = get("GA_RC_NARROW")) kn.rc_narrow = atoi(e) != 0;
+        if (const char* e = get("GA_RC_BUDGET_MB")) kn.rc_budget = atoll(e) << 20;
+        // whether the tie-to-tie walk may run (GA_RC_JUMP): the checkpoint sizing then budgets its cache
+        const char* e = xget("GA_RC_JUMP");
+        kn.rc_jump = e ? atoi(e) != 0 : kRcJumpDefault;
+        return kn;
+    }
 };
 
 // The kernels' LDS formulas and the walk's cache size: defined beside the kernels (ga_lane.hip, ga_rcwalk.hip) and

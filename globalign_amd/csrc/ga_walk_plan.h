@@ -21,7 +21,7 @@ namespace gawalk {
 constexpr int kSpanI = 32, kSpanS = 8, kWindow = 64;
 
 // The knobs of the traceback call, parsed here and nowhere else, once per context (ga_ctx::wk): `get` looks a shipped
-// knob up, `xget` one of a path that was measured and dropped (ga_ctx::knob / ga_ctx::xknob: the shipped build's sees
+// knob up, `xget` one of a path that was measured and dropped (ga_ctx_create_opts' two look-ups: the shipped build's xget sees
 // nothing); nullptr for an unset name.
 struct Knobs {
     int rc = -1;                            // GA_RC: 0 never, 1 whenever the shape allows (tests), else large problems

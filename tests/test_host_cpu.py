@@ -96,6 +96,22 @@ def test_lane_asm_header_matches_generator(tmp_path):
     assert out.read_bytes() == open(f"{ROOT}/globalign_amd/csrc/ga_lane_asm.h", "rb").read()
 
 
+def test_env_knobs_are_documented():
+    """Every GA_* variable the shipped library reads from the environment (gaopts::kEnvKnobs, which the host
+    self-test prints) is listed in INTEGRATION.md."""
+    import os
+    import subprocess
+    csrc = os.path.join(ROOT, "globalign_amd", "csrc")
+    r = subprocess.run(["make", "-s", "-C", csrc, "selftest"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    names = subprocess.run([os.path.join(ROOT, "globalign_amd", "_lib", "ga_host_selftest"), "envknobs"],
+                           capture_output=True, text=True, timeout=60, check=True).stdout.split()
+    assert len(names) == len(set(names)) >= 14 and all(n.startswith("GA_") for n in names)
+    doc = open(f"{ROOT}/INTEGRATION.md").read()
+    missing = [n for n in names if not re.search(rf"\b{n}\b", doc)]
+    assert not missing, missing
+
+
 def test_engine_cache_keeps_one_knob_set(monkeypatch):
     """default_engine / device_engines keep one context per (device(s), thread): a GA_* change drops the contexts
     made under the old set (they held their device buffers for the life of the process)."""
