@@ -233,6 +233,11 @@ int banded_align(ga_ctx* c, int64_t Bh, uint32_t* mt_state, const char* a_chr, c
         int64_t seg = 0;
         if (int r = walk_segment(c, st, reason, a_chr, b_chr, oa + len, om + len, ob + len, cap - len, seg)) return r;
         if (int r = check_fill_abort(c)) return r;
+        // the walk tests local row 0 first: a move that lands on a band's top row AND on local column 0 comes back
+        // as a hand-over (6), but the walk has reached the left edge -- what it reports anywhere else in a band
+        // (jend).  Handing it on would start the next band's walk at column 0, on the degenerate path.  (Only the
+        // whole-problem call bands its traceback, col0 == 0: column 0 is the matrix edge, reason 2.)
+        if (reason == 6 && st.j == 0) reason = 2;
         len += seg;
         walk_ms += c->walk_ms;
         float f = 0.f;

@@ -1,6 +1,7 @@
 """What the GPU parity tests under explicit cost tables share (tests/test_gpu_general_costs.py,
-tests/test_gpu_limits.py): one engine call of a problem against the oracle's result for it.  A problem is a tuple
-(costing dict, seq_1, seq_2, gap open cost); the callers keep their own case lists and cached references."""
+tests/test_gpu_limits.py, tests/test_gpu_tie_classes.py, tests/test_gpu_path_geometry.py): one engine call of a
+problem against the oracle's result for it.  A problem is a tuple (costing dict, seq_1, seq_2, gap open cost); the
+callers keep their own case lists and cached references."""
 import random
 
 import numpy as np
