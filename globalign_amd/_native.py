@@ -46,6 +46,7 @@ EXPORTS = [
     "ga_last_error", "ga_device_count", "ga_ctx_create", "ga_ctx_create_opts", "ga_ctx_destroy", "ga_build_flags", "ga_problem_set", "ga_problem_fill", "ga_batch_costs", "ga_batch_costs_ex", "ga_batch_align", "ga_batch_align_timings", "ga_debug_seed_state",
     "ga_batch_align_ex", "ga_batch_align_info", "ga_debug_pair_tables",
     "ga_batch_sample", "ga_batch_sample_info", "ga_batch_sample_timings",
+    "ga_batch_count", "ga_batch_count_info", "ga_batch_count_timings",
     "ga_problem_set_cells",
     "ga_problem_traceback", "ga_problem_align", "ga_problem_align_many", "ga_problem_set_slab", "ga_slab_buffers", "ga_slab_bind_halos",
     "ga_slab_link", "ga_slab_link_export", "ga_slab_link_import", "ga_enable_peer_access",
@@ -120,6 +121,10 @@ def load_library():
                                       pi64, pi64, p32, pi64, C.c_uint32]
         L.ga_batch_sample_info.argtypes = [vp, pi64]
         L.ga_batch_sample_timings.argtypes = [vp, C.POINTER(C.c_float)]
+        L.ga_batch_count.argtypes = [vp, vp, pi64, i64, p32, p32, p32, i64, C.POINTER(GaCosts), pi64,
+                                     C.POINTER(C.c_double)]
+        L.ga_batch_count_info.argtypes = [vp, pi64]
+        L.ga_batch_count_timings.argtypes = [vp, C.POINTER(C.c_float)]
         L.ga_debug_pair_tables.argtypes = [vp, vp, p32, i64, i32, pu32, p32]
         L.ga_batch_align_timings.argtypes = [vp, C.POINTER(C.c_float)]
         L.ga_debug_seed_state.argtypes = [C.c_uint64, pu32]
@@ -383,6 +388,33 @@ class Engine:
             raise ValueError(f"rng_tables must be None, 'host' or 'device', not {rng_tables!r}")
         b = batch_arrays(codes, seq_off, pair_a, pair_b, pair_max_cost, chars, seeds, sample_off)
         return self._batch_strings(self._L.ga_batch_sample, b, tables, (b.sample_off.ctypes.data_as(_P64),), rng_tables)
+
+    def batch_count(self, codes, seq_off, pair_a, pair_b, tables, pair_max_cost=None):
+        """The number of co-optimal alignments of many pairs in one call (ga_batch_count): batch_costs's arguments.
+        -> (costs int64, counts float64), in pair order.  Afterwards no problem counts as loaded."""
+        b = batch_arrays(codes, seq_off, pair_a, pair_b, pair_max_cost)
+        costs, counts = np.zeros(b.P, dtype=np.int64), np.zeros(b.P, dtype=np.float64)
+        _check(self._L.ga_batch_count(*self._batch_head(b, tables), costs.ctypes.data_as(_P64),
+                                      counts.ctypes.data_as(C.POINTER(C.c_double))))
+        self.m = self.n = 0
+        return costs, counts
+
+    def batch_count_info(self):
+        """{kernel_pairs, single_fill_pairs, fill_chunks, fill_launches, count_launches, hbm_edge_pairs} of the last
+        batch_count (ga_batch_count_info): the pairs batch_words_kernel filled and batch_count_kernel counted, those
+        counted from a single-pair fill, the fill chunks, the fill and count launches, and the pairs whose edge column
+        went through HBM."""
+        out = (C.c_int64 * 8)()
+        _check(self._L.ga_batch_count_info(self._h, out))
+        return dict(zip(("kernel_pairs", "single_fill_pairs", "fill_chunks", "fill_launches", "count_launches",
+                         "hbm_edge_pairs"), (int(x) for x in out)))
+
+    def batch_count_timings(self):
+        """{words_ms, count_ms, single_fill_ms, single_count_ms, call_ms} of the last batch_count, summed over its
+        launches."""
+        out = (C.c_float * 8)()
+        _check(self._L.ga_batch_count_timings(self._h, out))
+        return dict(words_ms=out[0], count_ms=out[1], single_fill_ms=out[2], single_count_ms=out[3], call_ms=out[4])
 
     def _batch_head(self, b, tables):
         """The arguments every batched entry begins with."""

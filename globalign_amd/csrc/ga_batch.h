@@ -1,7 +1,8 @@
 // ga_batch.h -- host-side planning of a batch of score-only alignments (ga_batch_costs) and of a batch of alignments
 // with strings (ga_batch_align, at the end); no HIP: built into the engine, into the kernels' translation unit for the
-// work-item layout, and into the planner self-tests, ga_batch_selftest.cpp, ga_batch_align_selftest.cpp and
-// ga_batch_sample_selftest.cpp (ga_batch_sample's planner, after ga_batch_align's), under AddressSanitizer / UBSan.
+// work-item layout, and into the planner self-tests, ga_batch_selftest.cpp, ga_batch_align_selftest.cpp,
+// ga_batch_sample_selftest.cpp (ga_batch_sample's planner, after ga_batch_align's) and ga_batch_count_selftest.cpp
+// (ga_batch_count's, after that), under AddressSanitizer / UBSan.
 //
 // A batch is a list of sequences (codes concatenated, seq_off[s] .. seq_off[s + 1]) and a list of pairs of sequence
 // indices.  The planner checks every pair as check_problem (ga_check.h) checks a single problem -- with that pair's
@@ -313,6 +314,28 @@ inline void plan_walk_launches(const ga_batch_item* items, int64_t count, const 
     if (wl.count > 0) launches.push_back(wl);
 }
 
+// The kernel pairs cut into fill chunks, in work-list order: a chunk takes pairs while their traceback words stay
+// within `cap` u32 words (every pair's own words are within it: the routing's rule); pair t's slice is appended to
+// `words`, and close(chunk) is called for every chunk as it ends.
+template <typename Close>
+inline void plan_fill_chunks(const std::vector<ga_batch_item>& kernel, int CB, int64_t cap,
+                             std::vector<ga_batch_words_item>& words, Close close) {
+    FillChunk ch;
+    for (int64_t t = 0; t < (int64_t)kernel.size(); t++) {
+        const ga_batch_item& it = kernel[(size_t)t];
+        const int64_t w = tb_slice_words(it.m, it.T, it.nstripes, CB);
+        if (ch.count > 0 && ch.tb_words + w > cap) {
+            close(ch);
+            ch = FillChunk();
+            ch.first = t;
+        }
+        words.push_back(ga_batch_words_item{ch.tb_words, w});
+        ch.tb_words += w;
+        ch.count++;
+    }
+    if (ch.count > 0) close(ch);
+}
+
 // plan_batch_align's checks, error order, stripe geometry and routing, a pair's traceback words measured against a
 // fill chunk's cap instead of a wave's share (lim.tb_words_cap is set from lim.chunk_tb_words here).  Pair k has the
 // samples sample_off[k] .. sample_off[k + 1].  A walk launch takes items while their table entries stay within
@@ -345,20 +368,59 @@ inline int plan_batch_sample(const uint8_t* codes, const int64_t* seq_off, int64
         ch.launch_count = (int64_t)out.launches.size() - ch.launch_first;
         out.chunks.push_back(ch);
     };
-    FillChunk ch;
-    for (int64_t t = 0; t < (int64_t)out.kernel.size(); t++) {
-        const ga_batch_item& it = out.kernel[(size_t)t];
-        const int64_t w = tb_slice_words(it.m, it.T, it.nstripes, out.CB);  // <= al.tb_words_cap: the routing's rule
-        if (ch.count > 0 && ch.tb_words + w > al.tb_words_cap) {
-            close_chunk(ch);
-            ch = FillChunk();
-            ch.first = t;
-        }
-        out.words.push_back(ga_batch_words_item{ch.tb_words, w});
-        ch.tb_words += w;
-        ch.count++;
-    }
-    if (ch.count > 0) close_chunk(ch);
+    plan_fill_chunks(out.kernel, out.CB, al.tb_words_cap, out.words, close_chunk);
+    return GA_OK;
+}
+
+// ------------------------------------------------------------------ co-optimal alignment counts (ga_batch_count)
+// batch_words_kernel fills a chunk's pairs as for ga_batch_sample; batch_count_kernel, a later launch on the same
+// stream, then counts every pair's co-optimal alignments from its words, one wave per pair (ga_batch.hip, DESIGN.md
+// 5.13).  A stripe hands the next one two doubles a row, N(i, edge, 0) and N(i, edge, 1): through the wave's LDS share
+// while m fits (kLdsEdgeRows rows), else through a ping-pong pair of HBM slices of the wave's own.
+constexpr int64_t kCountEdgeBytes = 16;  // two doubles a row
+
+// The most rows a wave's count scratch slice may have with `waves` resident waves (two ping-pong slices each).
+inline int64_t count_rows_cap(int64_t waves) {
+    return kScratchBytesCap / (std::max<int64_t>(waves, 1) * 2 * kCountEdgeBytes);
+}
+
+struct CountLimits : AlignLimits {
+    int64_t chunk_tb_words = kTbScratchBytesCap / 4;  // as SampleLimits's
+    int64_t count_rows_cap = 0;                       // most rows of HBM count edge a wave may be given
+};
+
+struct CountPlan : Plan {
+    int CB = 1;
+    std::vector<ga_batch_words_item> words;  // parallel to `kernel`; tb_off counts from the chunk's start
+    std::vector<FillChunk> chunks;           // (launch_first / launch_count unused: a chunk has one count launch)
+    int64_t count_rows = 0;                  // rows per wave and ping-pong slice of the count's HBM edge (0: none)
+};
+
+// plan_batch_sample's fill side: plan_batch_align's checks, error order, stripe geometry and routing with a pair's
+// words measured against a fill chunk's cap, and the same chunks.  Also to `single` goes a pair whose count edge needs
+// HBM rows beyond lim.count_rows_cap.  The caller decides what becomes of `single` (a pair with a one-letter sequence
+// has no count; the others are filled by the single-pair fill).
+inline int plan_batch_count(const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                            const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                            const CountLimits& lim, CountPlan& out, std::string& err) {
+    out = CountPlan();
+    const int CB = cs ? tb_word_bytes(cs->gap_open) : 0;  // (0: plan_batch_routed refuses every pair)
+    const int64_t cap = std::max<int64_t>(lim.chunk_tb_words, 0);
+    Plan base;
+    const int r = plan_batch_routed(
+        codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim,
+        [&](int64_t m, int64_t n, int T, int nstripes) {
+            return std::min(m, n) < 2 || CB == 0 || tb_slice_words(m, T, nstripes, CB) > cap ||
+                   (needs_scratch(m, n) && m > lim.count_rows_cap);
+        },
+        base, err);
+    if (r) return r;
+    static_cast<Plan&>(out) = std::move(base);
+    out.CB = std::max(CB, 1);
+    out.words.reserve(out.kernel.size());
+    for (const ga_batch_item& it : out.kernel)
+        if (needs_scratch(it.m, it.n)) out.count_rows = std::max<int64_t>(out.count_rows, it.m);
+    plan_fill_chunks(out.kernel, out.CB, cap, out.words, [&](const FillChunk& ch) { out.chunks.push_back(ch); });
     return GA_OK;
 }
 

@@ -1,5 +1,5 @@
-// ga_batch_host.cpp -- the batch engine behind ga_batch_costs, ga_batch_align, ga_batch_sample and
-// ga_debug_pair_tables (DESIGN.md 5.10 - 5.12): staging and launches of the batch kernels, the one table stage and the
+// ga_batch_host.cpp -- the batch engine behind ga_batch_costs, ga_batch_align, ga_batch_sample, ga_batch_count and
+// ga_debug_pair_tables (DESIGN.md 5.10 - 5.13): staging and launches of the batch kernels, the one table stage and the
 // one decode of the calls with strings.  It reaches the rest of the engine through ga_host_internal.h.
 #include <cstring>
 
@@ -631,6 +631,175 @@ static int batch_sample_impl(ga_ctx* c, const uint8_t* codes, const int64_t* seq
     return GA_OK;
 }
 
+// ga_batch_count: every pair filled as ga_batch_sample fills it, then counted by batch_count_kernel
+// from the words the fill left, one wave per pair.  No table stage, no RNG and no decode.
+static int batch_count_impl(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                            const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                            int64_t* cost_out, double* count_out) {
+    if (int r = check_ctx(c)) return r;
+    for (int64_t& x : c->batch_count_info) x = 0;
+    for (float& x : c->batch_count_ms) x = 0.f;
+    if (npairs == 0) return GA_OK;  // an empty batch: no launch
+    if (!cost_out || !count_out) return fail(GA_E_ARG, "null argument");
+    const double t_call = now_ms();
+    const int64_t max_waves = batch_max_waves(c);
+    const int W = gabatch::kWavesPerGroup;
+    gabatch::CountLimits lim;
+    if (c->bk.align_max_cells) lim.max_cells = *c->bk.align_max_cells;
+    if (c->bk.sample_chunk_words) lim.chunk_tb_words = *c->bk.sample_chunk_words;
+    lim.scratch_rows_cap = gabatch::scratch_rows_cap(max_waves);
+    lim.count_rows_cap = gabatch::count_rows_cap(max_waves);
+    gabatch::CountPlan plan;
+    std::string why;
+    if (int r = gabatch::plan_batch_count(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim, plan, why))
+        return fail(r, why);
+    auto len_of = [&](int64_t s) { return seq_off[s + 1] - seq_off[s]; };
+    // What left the kernel route is counted from a single-pair fill with stored words or not at all: the lowest pair
+    // that cannot be is refused before anything is launched.
+    {
+        int64_t bad = -1, avail = -1;
+        const char* reason = nullptr;
+        for (const int64_t k : plan.single) {
+            if (bad >= 0 && k > bad) continue;
+            const int64_t m = len_of(pair_a[k]), n = len_of(pair_b[k]);
+            const char* r = nullptr;
+            if (std::min(m, n) < 2) {
+                r = "count needs sequences of at least two letters";
+            } else {
+                // (forced rows, tests, do not ask the device what it has free: band_rows, ga_align_host.cpp)
+                if (avail < 0) avail = c->wk.tb_band_rows ? 0 : dev_avail_bytes(c, (int64_t)c->fb.tb.cap);
+                if (gawalk::band_rows(m, n, plan.CB, c->wk, avail) != 0)
+                    r = "traceback words exceed the budget, and counting has no banded route";
+                else if (gabatch::needs_scratch(m, n) && m > gabatch::count_rows_cap(W))
+                    r = "edge column exceeds the count scratch";
+            }
+            if (r) bad = k, reason = r;
+        }
+        if (bad >= 0) return fail(GA_E_ARG, "pair " + std::to_string(bad) + ": " + reason);
+    }
+    if (int r = refuse_slab_single(c, plan.single, "fill")) return r;
+    HIPCHK(c->bc_out.ensure(sizeof(double) * npairs));
+    HIPCHK(c->bc_ticket.ensure(sizeof(unsigned)));
+
+    // The count launch over `nitems` pairs whose work list and slices are on the device at items_dev / words_dev and
+    // whose words lie in tb (tb_words u32s, `layout`, `tc`), behind the fill on the context's stream and between the
+    // events c->wev; edge_rows: the HBM edge rows a wave needs (0: none).
+    auto enqueue_count = [&](const ga_batch_item* items_dev, const ga_batch_words_item* words_dev, int nitems,
+                             const uint32_t* tb, int64_t tb_words, int CB, int layout, int tc, int waves,
+                             int64_t edge_rows) -> int {
+        if (edge_rows > 0) HIPCHK(c->bc_scratch.ensure(sizeof(double2) * 2 * (size_t)edge_rows * waves));
+        // the count's ticket starts at zero for every launch
+        HIPCHK(hipMemsetAsync(c->bc_ticket.p, 0, sizeof(unsigned), c->stream));
+        HIPCHK(hipEventRecord(c->wev[0], c->stream));
+        const ga::CountArgs q{cs->gap_open, items_dev, words_dev, nitems, c->bc_ticket.as<unsigned>(),
+                              c->bc_out.as<double>(), (long long)npairs, tb, (long long)tb_words, tc,
+                              edge_rows > 0 ? c->bc_scratch.as<double2>() : nullptr, (long long)edge_rows};
+        ga::launch_batch_count(c->stream, q, CB, layout, waves);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->wev[1], c->stream));
+        c->batch_count_info[4]++;
+        return GA_OK;
+    };
+    auto take_count = [&](double got, int64_t k) -> int {
+        if (!(got >= 1.0))
+            return fail(GA_E_STATE, "pair " + std::to_string(k) + ": work item does not fit the count launch");
+        count_out[k] = got;
+        return GA_OK;
+    };
+
+    // the kernel pairs, fill chunk by fill chunk
+    for (const gabatch::FillChunk& ch : plan.chunks) {
+        const std::vector<ga_batch_item> items(plan.kernel.begin() + ch.first, plan.kernel.begin() + ch.first + ch.count);
+        BatchStage bs;
+        if (int r = stage_batch(c, codes, seq_off, nseq, npairs, cs, items, plan.scratch_rows, bs)) return r;
+        HIPCHK(c->bs_words.ensure(sizeof(ga_batch_words_item) * items.size()));
+        if (c->bs_tb.ensure(sizeof(uint32_t) * (size_t)ch.tb_words) != hipSuccess) {
+            (void)hipStreamSynchronize(c->stream);  // the staged uploads read this call's buffers
+            return fail(GA_E_NOMEM, "no device memory for the batch's traceback words");
+        }
+        HIPCHK(hipMemcpyAsync(c->bs_words.p, plan.words.data() + ch.first, sizeof(ga_batch_words_item) * items.size(),
+                              hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipEventRecord(c->fb.ev[0], c->stream));
+        const ga::WordsArgs q{bs.args, c->bs_words.as<ga_batch_words_item>(), c->bs_tb.as<uint32_t>(),
+                              (long long)ch.tb_words};
+        ga::launch_batch_words(c->stream, q, plan.qbytes, plan.CB, bs.waves);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->fb.ev[1], c->stream));
+        c->batch_count_info[3]++;
+        if (int r = enqueue_count(c->bt_items.as<ga_batch_item>(), c->bs_words.as<ga_batch_words_item>(), (int)items.size(),
+                                  c->bs_tb.as<uint32_t>(), ch.tb_words, plan.CB, gabatch::LAYOUT_BATCH, 0, bs.waves,
+                                  plan.count_rows))
+            return r;
+        std::vector<long long> got((size_t)npairs);
+        std::vector<double> cnt((size_t)npairs);
+        HIPCHK(hipMemcpyAsync(got.data(), c->bt_out.p, sizeof(long long) * npairs, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(cnt.data(), c->bc_out.p, sizeof(double) * npairs, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        float count_ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&c->fill_ms, c->fb.ev[0], c->fb.ev[1]));
+        HIPCHK(hipEventElapsedTime(&count_ms, c->wev[0], c->wev[1]));
+        c->batch_count_ms[0] += c->fill_ms;
+        c->batch_count_ms[1] += count_ms;
+        if (int r = take_batch_costs(got, items.data(), items.size(), cost_out)) return r;
+        for (const ga_batch_item& it : items) {
+            if (int r = take_count(cnt[(size_t)it.out], it.out)) return r;
+            c->batch_count_info[5] += gabatch::needs_scratch(it.m, it.n);
+        }
+        c->batch_count_info[0] += (int64_t)items.size();
+        c->batch_count_info[2]++;
+    }
+
+    // A pair that left the kernel route for its size: one single-pair fill with stored words, as ga_batch_sample's
+    // large route, then one wave counts c->fb.tb in that fill's layout.  They go through the context's problem slot,
+    // so no problem is loaded afterwards.
+    for (const int64_t k : plan.single) {
+        const int64_t sa = pair_a[k], sb = pair_b[k];
+        const int64_t m = len_of(sa), n = len_of(sb);
+        c->rc_used = false;
+        auto fill = [&](int64_t, int64_t) -> int {
+            if (band_rows(c) != 0) return fail(GA_E_ARG, "traceback words exceed the budget, and counting has no banded route");
+            if (int r = enqueue_fill(c, GA_FILL_TRACEBACK)) return r;
+            if (int r = finish_fill(c, &cost_out[k], nullptr)) return r;
+            c->batch_count_ms[2] += c->fill_ms;
+            c->batch_count_info[3]++;
+            const gaplan::FillPlan& pl = c->plan;
+            const int64_t tb_words = (int64_t)pl.nstripes * pl.T * pl.TC * 256;
+            if ((int64_t)pl.TC * (16 / c->CB) < m || tb_words < gabatch::stripe_words(n, pl.TC))
+                return fail(GA_E_STATE, "the fill's words do not cover the pair");
+            ga_batch_item it{0, (int32_t)m, 0, (int32_t)n, 0, (int32_t)k, 0, 0};
+            gabatch::stripe_geometry(n, it.T, it.nstripes);
+            const ga_batch_words_item ws{0, tb_words};
+            HIPCHK(c->bt_items.ensure(sizeof(ga_batch_item)));
+            HIPCHK(c->bs_words.ensure(sizeof(ga_batch_words_item)));
+            HIPCHK(hipMemcpyAsync(c->bt_items.p, &it, sizeof(it), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->bs_words.p, &ws, sizeof(ws), hipMemcpyHostToDevice, c->stream));
+            const bool hbm = gabatch::needs_scratch(m, n);
+            if (int r = enqueue_count(c->bt_items.as<ga_batch_item>(), c->bs_words.as<ga_batch_words_item>(), 1,
+                                      c->fb.tb.as<uint32_t>(), tb_words, c->CB, gabatch::LAYOUT_STRIPE, pl.TC, W,
+                                      hbm ? m : 0))
+                return r;
+            double got = 0.0;
+            HIPCHK(hipMemcpyAsync(&got, c->bc_out.as<double>() + k, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));  // (the uploads' sources live until here)
+            float count_ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&count_ms, c->wev[0], c->wev[1]));
+            c->batch_count_ms[3] += count_ms;
+            c->batch_count_info[1]++;
+            c->batch_count_info[5] += hbm;
+            // (batch_single_pair names the pair itself)
+            if (!(got >= 1.0)) return fail(GA_E_STATE, "work item does not fit the count launch");
+            count_out[k] = got;
+            return GA_OK;
+        };
+        if (int r = batch_single_pair(c, codes, seq_off, pair_a, pair_b, pair_max_cost, cs, k, fill)) return r;
+        c->filled_tb = false;
+    }
+    c->batch_count_ms[4] = (float)(now_ms() - t_call);
+    return GA_OK;
+}
+
+int ga_batch_count_info(ga_ctx* c, int64_t* out8) { return copy_figures(c, &ga_ctx::batch_count_info, out8); }
+int ga_batch_count_timings(ga_ctx* c, float* out8) { return copy_figures(c, &ga_ctx::batch_count_ms, out8); }
 int ga_batch_sample_info(ga_ctx* c, int64_t* out8) { return copy_figures(c, &ga_ctx::batch_sample_info, out8); }
 int ga_batch_sample_timings(ga_ctx* c, float* out8) { return copy_figures(c, &ga_ctx::batch_sample_ms, out8); }
 int ga_batch_align_timings(ga_ctx* c, float* out6) { return copy_figures(c, &ga_ctx::batch_align_ms, out6); }
@@ -722,6 +891,13 @@ int ga_batch_sample(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int
     return guard_end(c, batch_sample_impl(c, codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, sample_off,
                                           seeds, chars, out_a, out_mid, out_b, out_off, out_len, tb_status, cost_out,
                                           flags));
+}
+
+int ga_batch_count(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                   const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                   int64_t* cost_out, double* count_out) {
+    return guard_end(c, batch_count_impl(c, codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, cost_out,
+                                         count_out));
 }
 
 int ga_debug_pair_tables(ga_ctx* c, const uint64_t* seeds, const int32_t* steps, int64_t nitems, int32_t route,

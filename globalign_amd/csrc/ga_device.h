@@ -280,6 +280,23 @@ struct WalksArgs {
 // layout: gabatch::LAYOUT_BATCH (batch_words_kernel's words) or LAYOUT_STRIPE (a single-pair fill's, ga_batch_layout.h)
 void launch_batch_words(hipStream_t s, const WordsArgs& q, int qbytes, int CB, int waves);
 void launch_batch_walks(hipStream_t s, const WalksArgs& q, int CB, int layout, int waves);
+// the number of co-optimal alignments of every pair (ga_batch_count): batch_count_kernel, a later
+// launch on the stream that filled the words, one wave per pair (ga_batch_count.hip)
+struct CountArgs {
+    int o;                               // the gap-open cost (the words' rank test)
+    const ga_batch_item* items;          // the chunk's work list, as the fill had it
+    const ga_batch_words_item* words;    // parallel to items
+    int nitems;
+    unsigned* ticket;                    // the count launch's own ticket word, zeroed by the host
+    double* count_out;                   // [npairs], indexed by ga_batch_item::out; -1.0: the item does not fit
+    long long npairs;
+    const uint32_t* tb;                  // the words, written by an earlier launch and only read here
+    long long tb_words;
+    int tc;                              // LAYOUT_STRIPE: 16-byte words per lane of the fill that wrote tb
+    double2* scratch;                    // [waves][2][scratch_rows] edge columns in HBM (nullptr: no pair needs them)
+    long long scratch_rows;
+};
+void launch_batch_count(hipStream_t s, const CountArgs& q, int CB, int layout, int waves);
 // the device-routed items' tie-break tables, one wave per item (batch_rng_kernel, ga_batch_rng.hip)
 struct RngArgs {
     const gabrng::Item* items;   // seed, steps and tab_off of each item

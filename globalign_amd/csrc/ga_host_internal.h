@@ -279,6 +279,11 @@ struct ga_ctx {
     DevBuf bs_words, bs_tb, bs_witems, bs_ticket;
     int64_t batch_sample_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     float batch_sample_ms[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    // ga_batch_count fills as ga_batch_sample does and adds the counts, the count launch's own ticket
+    // word and the waves' HBM edge columns of doubles; ga_batch_count_info's and _timings's figures of its last call
+    DevBuf bc_out, bc_ticket, bc_scratch;
+    int64_t batch_count_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    float batch_count_ms[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int walk_jump_diag[3] = {0, 0, 0};  // the tie-to-tie walk's trips, region re-checks, ties (result[12..14])
     DevBuf jlut;           // the jump workers' LUT for gap open jlut_o (ga::jump_lut_build)
     int jlut_o = -1;

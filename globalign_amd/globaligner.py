@@ -26,7 +26,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _native
-from .results import AlignmentResults, BatchAlignments, BatchSamples, BatchScores, final_cost_to_score
+from .results import AlignmentResults, BatchAlignments, BatchCounts, BatchSamples, BatchScores, final_cost_to_score
 from .scoring import MAX_SEQ_LEN_PROD, get_max_val, validate_and_transform_args
 
 __version__ = "0.1.0"
@@ -197,6 +197,28 @@ class GlobalAligner:
         return BatchSamples(strings[0], strings[1], strings[2], costs, b.scores(costs),
                             [flat[x:y].copy() for x, y in cut], b.scoring_mat, b.costing_mat,
                             b.gap_open_score, b.gap_open_cost)
+
+    def count_alignments(self, seqs_1, seqs_2):
+        """The number of co-optimal alignments of seqs_1[k] with seqs_2[k] for every k: how many different
+        (seq_1_aligned, middle_part, seq_2_aligned) results ``align`` can return for the pair over all outcomes of the
+        reference's random tie-breaks -- what ``sample_alignments`` draws from, so ``len(distinct(k))`` of any sample
+        run is at most ``counts[k]``.  The counts come from one fill of the pair and a path count over its traceback
+        words on the GPU; the process-global ``random`` state is not touched.  Validation is align_pairs's.  A pair
+        with a one-letter sequence has no count (the reference's traceback is not a path walk there) and raises
+        ValueError for the lowest such pair, as does a pair whose traceback words do not fit the device's budget.
+        -> BatchCounts."""
+        _, b, _ = self._strings_batch("count_alignments", seqs_1, seqs_2, "host", lambda P: None)
+        if b is None:
+            e = self._empty_batch((0,))
+            return BatchCounts(np.zeros(0, dtype=np.float64), np.zeros(0, dtype=bool), e.costs, e.scores, *e[2:])
+        lens = np.diff(b.seq_off)
+        short = np.flatnonzero(np.minimum(lens[b.pair_a], lens[b.pair_b]) < 2)
+        if short.size:
+            raise ValueError(f"pair {int(short[0])}: count_alignments needs sequences of at least two letters")
+        eng = _native.default_engine(self.device)
+        costs, counts = eng.batch_count(b.codes, b.seq_off, b.pair_a, b.pair_b, b.tables, b.pair_max_cost)
+        return BatchCounts(counts, counts < 2.0 ** 53, costs, b.scores(costs), b.scoring_mat, b.costing_mat,
+                           b.gap_open_score, b.gap_open_cost)
 
     def _strings_batch(self, method, seqs_1, seqs_2, tables, seeds_of):
         """The front half of align_pairs and sample_alignments (`method`: the name in the messages): the checks in their

@@ -182,3 +182,24 @@ class BatchSamples(NamedTuple):
         for key in zip(self.seq_1_aligned[k], self.middle_part[k], self.seq_2_aligned[k]):
             counts[key] = counts.get(key, 0) + 1
         return list(counts.items())
+
+
+class BatchCounts(NamedTuple):
+    """The number of co-optimal alignments of every pair (GlobalAligner.count_alignments): how many different
+    alignments the traceback can return for the pair over all tie-breaks.  counts: numpy float64, shape (P,) -- the
+    counts grow exponentially with the lengths, so they are doubles: the exact integer where exact[k] (counts[k] <
+    2**53: every partial sum is a positive integer no larger than the total), the recurrence's double sum above, +inf
+    past the double range; exact: numpy bool, shape (P,); the pair's cost and score in numpy int64 arrays; and the
+    settings, as BatchScores reports them."""
+    counts: "numpy.ndarray"
+    exact: "numpy.ndarray"
+    costs: "numpy.ndarray"
+    scores: "numpy.ndarray"
+    scoring_mat: dict
+    costing_mat: dict
+    gap_open_score: int
+    gap_open_cost: int
+
+    def count(self, k):
+        """Pair k's count: a Python int when it is exact, else the float."""
+        return int(self.counts[k]) if self.exact[k] else float(self.counts[k])

@@ -210,6 +210,32 @@ int ga_batch_sample_info(ga_ctx* ctx, int64_t* out8);
  * did not hide), host string decode ms, whole call wall ms, the walks' ns per dispatch (average of what each wave
  * timed), single-pair fills ms, 0} of the last ga_batch_sample, summed over its launches. */
 int ga_batch_sample_timings(ga_ctx* ctx, float* out8);
+/* The number of co-optimal alignments of every pair: how many different
+ * alignments the traceback can return for pair k over all tie-breaks, the
+ * paths from (m, n) of the DAG its walk moves on.
+ * count_out[k] receives it as a double -- the exact integer below 2^53, the
+ * recurrence's double sum above, +inf past the double range, never NaN -- and
+ * cost_out[k] pair k's cost.  codes .. costs are ga_batch_sample's, with the
+ * same checks and errors ("pair <k>: ..."); no seeds, no tables, no strings.
+ * Kernel pairs are filled chunk by chunk by batch_words_kernel as for
+ * ga_batch_sample (GA_BATCH_ALIGN_MAX_CELLS, GA_BATCH_SAMPLE_CHUNK_WORDS) and
+ * counted by batch_count_kernel, one wave per pair, in a later launch on the
+ * same stream.  A pair that leaves the kernel route for its size is filled by
+ * the single-pair fill with stored traceback words and counted by one wave of
+ * the same kernel.  Refused with GA_E_ARG, before any launch and for the lowest
+ * such pair: a pair with a one-letter sequence (the reference's traceback is
+ * no path walk there) and a pair whose words exceed the traceback budget
+ * (GA_TB_BUDGET_MB): there is no banded or recompute route for counting. */
+int ga_batch_count(ga_ctx* ctx, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                   const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* costs,
+                   int64_t* cost_out, double* count_out);
+/* out8 = {pairs counted on the kernel route, pairs counted from a single-pair fill, fill chunks, fill launches
+ * (batch_words_kernel's and single-pair fills), count launches, pairs whose edge column went through HBM, 0, 0} of
+ * the last ga_batch_count. */
+int ga_batch_count_info(ga_ctx* ctx, int64_t* out8);
+/* out8 = {batch_words_kernel ms, batch_count_kernel ms over those pairs, single-pair fills ms, batch_count_kernel ms
+ * over their pairs, whole call wall ms, 0, 0, 0} of the last ga_batch_count, summed over its launches. */
+int ga_batch_count_timings(ga_ctx* ctx, float* out8);
 /* The tie-break tables alone, with no alignment: item t's steps[t] entries under seeds[t], concatenated in
  * tab_out, by route 1 (host) or 2 (device; an item over GA_BATCH_RNG_DEVICE_MAX_STEPS is built on the host, as
  * in the real call).  status_out[t]: 0 complete, 1 the word cap was reached (entries past the stop are

@@ -24,6 +24,10 @@ JSON line per workload with pairs, cells, ms (median of 5 calls after 2 warm-ups
                                                 of random.seed(s) + align over 32 of the seeds (S3) --, in alternating
                                                 rounds of one process: median, least and most of 5 after 2 warm-ups,
                                                 with the engine's own parts of the last call
+    python tools/batch_bench.py --count         B1 and S3's 10k x 10k pair through count_alignments:
+                                                median, least and most of 5 after 2 warm-ups, with the count launch's
+                                                kernel ms beside the fill's for the same batch (medians over the timed
+                                                calls of the same run), the count's ns per cell, and the counts' range
 
 Workloads (SplitMix64 sequences of tests.conftest, lengths from a seeded random.Random):
   B1  4096 DNA pairs, lengths 200-400         B2  1024 BLOSUM62 pairs, lengths 100-600
@@ -258,6 +262,38 @@ def sample_workloads():
     run("S3", [(splitmix_seq(10000, 1, "dna"), splitmix_seq(10000, 2, "dna"))], 256, old_samples=32)
 
 
+def count_workloads():
+    def run(name, pairs):
+        al = GlobalAligner(max_seq_len_prod=None, **DNA)
+        a, b = [p[0] for p in pairs], [p[1] for p in pairs]
+        eng, parts, last = _native.default_engine(0), [], {}
+
+        def call():
+            last["res"] = al.count_alignments(a, b)
+            parts.append(eng.batch_count_timings())
+
+        for _ in range(WARMUP):
+            call()
+        ms = []
+        for _ in range(REPEATS):
+            t0 = time.perf_counter()
+            call()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        parts, res = parts[-REPEATS:], last["res"]
+        cells = sum(len(x) * len(y) for x, y in pairs)
+        med = {k: round(statistics.median(x[k] for x in parts), 4) for k in parts[0]}
+        count_ms, fill_ms = med["count_ms"] + med["single_count_ms"], med["words_ms"] + med["single_fill_ms"]
+        print(json.dumps(dict(workload=name, pairs=len(pairs), cells=cells, ms=round(statistics.median(ms), 4),
+                              ms_min=round(min(ms), 4), ms_max=round(max(ms), 4), **med,
+                              count_over_fill=round(count_ms / fill_ms, 3), count_ns_per_cell=round(count_ms * 1e6 / cells, 4),
+                              fill_ns_per_cell=round(fill_ms * 1e6 / cells, 4), info=eng.batch_count_info(),
+                              counts_min=float(res.counts.min()), counts_max=float(res.counts.max()),
+                              exact=int(res.exact.sum()))), flush=True)
+
+    run("B1-count", pairs_of(4096, 200, 400, "dna", 1))
+    run("S3-count", [(splitmix_seq(10000, 1, "dna"), splitmix_seq(10000, 2, "dna"))])
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--loop", type=int, default=0, metavar="K")
@@ -267,8 +303,11 @@ def main():
     ap.add_argument("--align-loop", type=int, default=0, metavar="K")
     ap.add_argument("--align-crossover", action="store_true")
     ap.add_argument("--sample", action="store_true")
+    ap.add_argument("--count", action="store_true")
     args = ap.parse_args()
-    if args.sample:
+    if args.count:
+        count_workloads()
+    elif args.sample:
         sample_workloads()
     elif args.loop:
         loop(args.loop)
