@@ -47,6 +47,7 @@ EXPORTS = [
     "ga_batch_align_ex", "ga_batch_align_info", "ga_debug_pair_tables",
     "ga_batch_sample", "ga_batch_sample_info", "ga_batch_sample_timings",
     "ga_batch_count", "ga_batch_count_info", "ga_batch_count_timings",
+    "ga_batch_rank", "ga_batch_rank_info", "ga_batch_rank_timings",
     "ga_problem_set_cells",
     "ga_problem_traceback", "ga_problem_align", "ga_problem_align_many", "ga_problem_set_slab", "ga_slab_buffers", "ga_slab_bind_halos",
     "ga_slab_link", "ga_slab_link_export", "ga_slab_link_import", "ga_enable_peer_access",
@@ -125,6 +126,10 @@ def load_library():
                                      C.POINTER(C.c_double)]
         L.ga_batch_count_info.argtypes = [vp, pi64]
         L.ga_batch_count_timings.argtypes = [vp, C.POINTER(C.c_float)]
+        L.ga_batch_rank.argtypes = [vp, vp, pi64, i64, p32, p32, p32, i64, C.POINTER(GaCosts), pi64, vp, vp, vp, vp, vp,
+                                    pi64, pi64, p32, pi64, C.POINTER(C.c_uint64)]
+        L.ga_batch_rank_info.argtypes = [vp, pi64]
+        L.ga_batch_rank_timings.argtypes = [vp, C.POINTER(C.c_float)]
         L.ga_debug_pair_tables.argtypes = [vp, vp, p32, i64, i32, pu32, p32]
         L.ga_batch_align_timings.argtypes = [vp, C.POINTER(C.c_float)]
         L.ga_debug_seed_state.argtypes = [C.c_uint64, pu32]
@@ -415,6 +420,41 @@ class Engine:
         out = (C.c_float * 8)()
         _check(self._L.ga_batch_count_timings(self._h, out))
         return dict(words_ms=out[0], count_ms=out[1], single_fill_ms=out[2], single_count_ms=out[3], call_ms=out[4])
+
+    def batch_rank(self, codes, seq_off, pair_a, pair_b, tables, rank_off, ranks, chars, pair_max_cost=None):
+        """Co-optimal alignments of many pairs by rank (ga_batch_rank): batch_costs's arguments, rank_off (int64, P + 1
+        entries from 0: pair k has the slots rank_off[k] .. rank_off[k + 1], possibly none), ranks (uint64, one per slot)
+        and chars as batch_align takes them.
+        -> (costs int64 per pair, counts uint64 per pair: min(count, 2**64 - 1), status int32 per slot: 0, or 1 for a
+        rank that is not below the pair's count, lengths int64 per slot, offsets int64 (slots + 1), (seq_1_aligned,
+        middle, seq_2_aligned) uint8 buffers): slot f's strings are the lengths[f] bytes at offsets[f] of each buffer.
+        Afterwards no problem counts as loaded."""
+        b = batch_arrays(codes, seq_off, pair_a, pair_b, pair_max_cost, chars, ranks, rank_off)
+        offsets, bufs, costs, lengths, status = batch_outputs(b)
+        counts = np.zeros(b.P, dtype=np.uint64)
+        _check(self._L.ga_batch_rank(*self._batch_head(b, tables), b.sample_off.ctypes.data_as(_P64), b.seeds.ctypes.data,
+                                     b.chars.ctypes.data, bufs[0].ctypes.data, bufs[1].ctypes.data, bufs[2].ctypes.data,
+                                     offsets.ctypes.data_as(_P64), lengths.ctypes.data_as(_P64),
+                                     status.ctypes.data_as(_P32), costs.ctypes.data_as(_P64),
+                                     counts.ctypes.data_as(C.POINTER(C.c_uint64))))
+        self.m = self.n = 0
+        return costs, counts, status[:b.S], lengths[:b.S], offsets, bufs
+
+    def batch_rank_info(self):
+        """{kernel_pairs, single_fill_pairs, fill_chunks, fill_launches, table_launches, walk_launches, slots_walked,
+        saturated_pairs} of the last batch_rank (ga_batch_rank_info)."""
+        out = (C.c_int64 * 8)()
+        _check(self._L.ga_batch_rank_info(self._h, out))
+        return dict(zip(("kernel_pairs", "single_fill_pairs", "fill_chunks", "fill_launches", "table_launches",
+                         "walk_launches", "slots_walked", "saturated_pairs"), (int(x) for x in out)))
+
+    def batch_rank_timings(self):
+        """{words_ms, table_ms, walks_ms, decode_ms, call_ms, walk_ns_per_step, single_fill_ms, single_table_ms} of the
+        last batch_rank, summed over its launches."""
+        out = (C.c_float * 8)()
+        _check(self._L.ga_batch_rank_timings(self._h, out))
+        return dict(zip(("words_ms", "table_ms", "walks_ms", "decode_ms", "call_ms", "walk_ns_per_step", "single_fill_ms",
+                         "single_table_ms"), (float(x) for x in out)))
 
     def _batch_head(self, b, tables):
         """The arguments every batched entry begins with."""

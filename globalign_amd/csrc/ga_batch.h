@@ -1,8 +1,9 @@
 // ga_batch.h -- host-side planning of a batch of score-only alignments (ga_batch_costs) and of a batch of alignments
 // with strings (ga_batch_align, at the end); no HIP: built into the engine, into the kernels' translation unit for the
 // work-item layout, and into the planner self-tests, ga_batch_selftest.cpp, ga_batch_align_selftest.cpp,
-// ga_batch_sample_selftest.cpp (ga_batch_sample's planner, after ga_batch_align's) and ga_batch_count_selftest.cpp
-// (ga_batch_count's, after that), under AddressSanitizer / UBSan.
+// ga_batch_sample_selftest.cpp (ga_batch_sample's planner, after ga_batch_align's), ga_batch_count_selftest.cpp
+// (ga_batch_count's, after that) and ga_batch_rank_selftest.cpp (ga_batch_rank's, at the end), under AddressSanitizer /
+// UBSan.
 //
 // A batch is a list of sequences (codes concatenated, seq_off[s] .. seq_off[s + 1]) and a list of pairs of sequence
 // indices.  The planner checks every pair as check_problem (ga_check.h) checks a single problem -- with that pair's
@@ -15,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "ga_batch_rank.h"
 #include "ga_check.h"
 
 // One pair as the kernel takes it (a wave reads it with one uniform 32-byte load).
@@ -421,6 +423,145 @@ inline int plan_batch_count(const uint8_t* codes, const int64_t* seq_off, int64_
     for (const ga_batch_item& it : out.kernel)
         if (needs_scratch(it.m, it.n)) out.count_rows = std::max<int64_t>(out.count_rows, it.m);
     plan_fill_chunks(out.kernel, out.CB, cap, out.words, [&](const FillChunk& ch) { out.chunks.push_back(ch); });
+    return GA_OK;
+}
+
+}  // namespace gabatch
+
+// ------------------------------------------------------------------ co-optimal alignments by rank (ga_batch_rank)
+// batch_words_kernel fills a chunk's pairs as for ga_batch_count; batch_rank_table_kernel, a later launch on the same
+// stream, runs the count recurrence in saturating u64 and keeps every interior cell's three counts in the pair's slice
+// of the chunk's tables (ga_batch_rank.h has the layout); batch_rank_walk_kernel then walks a pair once per requested
+// rank, one lane per walk (ga_batch_rank.hip).
+
+// One walk item: up to 64 consecutive slots of one pair, lane l walking slot `out` + l.
+struct ga_batch_rank_item {
+    int64_t ops_off;  // the item's level words in the walk launch's: slot l at ops_off + l * ceil((m + n) / 16)
+    int32_t fill;     // the pair's index in its chunk's work list
+    int32_t out;      // the first slot's flat index (pair order, then rank order): its rank, and where its strings go
+    int32_t nslots;   // 1 .. 64
+    int32_t res;      // the first slot's place among the walk launch's results
+};
+
+namespace gabatch {
+
+// The tables of one fill chunk, all its pairs (GA_BATCH_RANK_TABLE_BYTES overrides): the words' cap.
+constexpr int64_t kRankTableBytesCap = kTbScratchBytesCap;
+
+struct RankLimits : CountLimits {
+    int64_t chunk_table_bytes = kRankTableBytesCap;
+    int64_t walk_entries = kWalkTableEntriesCap;  // steps (m + n a slot) of one walk launch, as SampleLimits's
+};
+
+// Walk items [first, first + count) of RankPlan::walk share one launch: `slots` results, ops_words level words.
+struct RankLaunch {
+    int64_t first = 0, count = 0;
+    int64_t slots = 0, steps = 0, ops_words = 0;
+};
+
+struct RankPlan : Plan {
+    int CB = 1;
+    std::vector<ga_batch_words_item> words;  // parallel to `kernel`; tb_off counts from the chunk's start
+    std::vector<int64_t> table_off;          // parallel to `kernel`: the pair's table in its chunk's, in u64 entries
+    std::vector<int64_t> chunk_table;        // parallel to `chunks`: u64 entries of the chunk's tables
+    std::vector<FillChunk> chunks;           // launch_first / launch_count index `launches`
+    std::vector<ga_batch_rank_item> walk;    // chunk by chunk, pair by pair in work-list order, 64 slots at a time
+    std::vector<RankLaunch> launches;
+    int64_t count_rows = 0;                  // as CountPlan's
+};
+
+// bytes of the count table of a pair of n columns (its stripe geometry is the fill's)
+inline int64_t rank_table_bytes(int64_t m, int64_t n) {
+    int T = 1, nstripes = 1;
+    stripe_geometry(n, T, nstripes);
+    return rank_table_entries(m, T, nstripes) * 8;
+}
+
+// plan_walk_launches' shape for rank items: the slots rank_off[items[t].out] .. rank_off[items[t].out + 1] of pair
+// items[t] in groups of 64, appended to `walk`, cut into launches of at most walk_entries steps (m + n a slot; a
+// single item above that gets a launch of its own), appended to `launches`.
+inline void plan_rank_launches(const ga_batch_item* items, int64_t count, const int64_t* rank_off, int64_t walk_entries,
+                               std::vector<ga_batch_rank_item>& walk, std::vector<RankLaunch>& launches) {
+    const int64_t walk_cap = std::max<int64_t>(walk_entries, 1);
+    RankLaunch wl;
+    wl.first = (int64_t)walk.size();
+    for (int64_t t = 0; t < count; t++) {
+        const int64_t steps = (int64_t)items[t].m + items[t].n, wps = (steps + 15) / 16;
+        const int64_t last = rank_off[items[t].out + 1];
+        for (int64_t f = rank_off[items[t].out]; f < last; f += 64) {
+            const int64_t ns = std::min<int64_t>(64, last - f);
+            if (wl.count > 0 && wl.steps + ns * steps > walk_cap) {
+                launches.push_back(wl);
+                wl = RankLaunch();
+                wl.first = (int64_t)walk.size();
+            }
+            walk.push_back(ga_batch_rank_item{wl.ops_words, (int32_t)t, (int32_t)f, (int32_t)ns, (int32_t)wl.slots});
+            wl.count++;
+            wl.slots += ns;
+            wl.steps += ns * steps;
+            wl.ops_words += ns * wps;
+        }
+    }
+    if (wl.count > 0) launches.push_back(wl);
+}
+
+// plan_batch_count's checks, error order, stripe geometry and routing.  Pair k has the ranks rank_off[k] ..
+// rank_off[k + 1] (none is legal: the pair is filled and counted).  A pair of two letters a side whose own table
+// exceeds lim.chunk_table_bytes is refused, the lowest such pair first.  A chunk closes when either its words would
+// exceed lim.chunk_tb_words or its tables lim.chunk_table_bytes; a pair never appears in two chunks, and a chunk's walk
+// items follow plan_rank_launches.
+inline int plan_batch_rank(const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                           const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                           const int64_t* rank_off, const RankLimits& lim, RankPlan& out, std::string& err) {
+    out = RankPlan();
+    auto fail = [&](int code, const std::string& msg) {
+        err = msg;
+        return code;
+    };
+    CountPlan base;
+    if (int r = plan_batch_count(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim, base, err)) return r;
+    if (npairs == 0) return GA_OK;
+    if (!rank_off) return fail(GA_E_ARG, "null argument");
+    if (rank_off[0] != 0) return fail(GA_E_ARG, "rank_off must start at 0");
+    for (int64_t k = 0; k < npairs; k++)
+        if (rank_off[k + 1] < rank_off[k]) return fail(GA_E_ARG, "rank_off must not decrease");
+    if (rank_off[npairs] > (int64_t)INT32_MAX) return fail(GA_E_RANGE, "a batch holds at most 2^31 - 1 ranks");
+    const int64_t table_cap = std::max<int64_t>(lim.chunk_table_bytes, 0);
+    for (int64_t k = 0; k < npairs; k++) {
+        const int64_t m = seq_off[pair_a[k] + 1] - seq_off[pair_a[k]], n = seq_off[pair_b[k] + 1] - seq_off[pair_b[k]];
+        if (std::min(m, n) >= 2 && rank_table_bytes(m, n) > table_cap)
+            return fail(GA_E_ARG, "pair " + std::to_string(k) + ": count table exceeds the rank table budget");
+    }
+    static_cast<Plan&>(out) = std::move(static_cast<Plan&>(base));
+    out.CB = base.CB;
+    out.count_rows = base.count_rows;
+    const int64_t words_cap = std::max<int64_t>(lim.chunk_tb_words, 0);
+    FillChunk ch;
+    int64_t table = 0;
+    auto close_chunk = [&]() {
+        ch.launch_first = (int64_t)out.launches.size();
+        plan_rank_launches(out.kernel.data() + ch.first, ch.count, rank_off, lim.walk_entries, out.walk, out.launches);
+        ch.launch_count = (int64_t)out.launches.size() - ch.launch_first;
+        out.chunks.push_back(ch);
+        out.chunk_table.push_back(table);
+    };
+    for (int64_t t = 0; t < (int64_t)out.kernel.size(); t++) {
+        const ga_batch_item& it = out.kernel[(size_t)t];
+        const int64_t w = tb_slice_words(it.m, it.T, it.nstripes, out.CB);
+        const int64_t e = rank_table_entries(it.m, it.T, it.nstripes);
+        if (ch.count > 0 && (ch.tb_words + w > words_cap || (table + e) * 8 > table_cap)) {
+            close_chunk();
+            ch = FillChunk();
+            ch.first = t;
+            table = 0;
+        }
+        out.words.push_back(ga_batch_words_item{ch.tb_words, w});
+        out.table_off.push_back(table);
+        ch.tb_words += w;
+        table += e;
+        ch.count++;
+    }
+    if (ch.count > 0) close_chunk();
     return GA_OK;
 }
 

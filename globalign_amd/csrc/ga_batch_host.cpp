@@ -1,5 +1,5 @@
-// ga_batch_host.cpp -- the batch engine behind ga_batch_costs, ga_batch_align, ga_batch_sample, ga_batch_count and
-// ga_debug_pair_tables: staging and launches of the batch kernels, the one table stage and the
+// ga_batch_host.cpp -- the batch engine behind ga_batch_costs, ga_batch_align, ga_batch_sample, ga_batch_count,
+// ga_batch_rank and ga_debug_pair_tables: staging and launches of the batch kernels, the one table stage and the
 // one decode of the calls with strings.  It reaches the rest of the engine through ga_host_internal.h.
 #include <cstring>
 
@@ -798,6 +798,284 @@ static int batch_count_impl(ga_ctx* c, const uint8_t* codes, const int64_t* seq_
     return GA_OK;
 }
 
+// ga_batch_rank: every pair filled as ga_batch_count fills it; batch_rank_table_kernel then keeps the
+// saturating u64 path counts of every cell in the pair's table, and batch_rank_walk_kernel walks the pair once per
+// requested rank, one lane per walk, reading the counts only at ties.  No table stage and no RNG; the strings come
+// from the walks' levels through decode_walk, as ga_batch_sample's.
+static int batch_rank_impl(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                           const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                           const int64_t* rank_off, const uint64_t* ranks, const char* chars, char* out_a, char* out_mid,
+                           char* out_b, const int64_t* out_off, int64_t* out_len, int32_t* rank_status, int64_t* cost_out,
+                           uint64_t* count_out) {
+    if (int r = check_ctx(c)) return r;
+    for (int64_t& x : c->batch_rank_info) x = 0;
+    for (float& x : c->batch_rank_ms) x = 0.f;
+    if (npairs == 0) return GA_OK;  // an empty batch: no launch
+    if (!rank_off || !cost_out || !count_out) return fail(GA_E_ARG, "null argument");
+    const double t_call = now_ms();
+    const int64_t max_waves = batch_max_waves(c);
+    const int W = gabatch::kWavesPerGroup;
+    gabatch::RankLimits lim;
+    if (c->bk.align_max_cells) lim.max_cells = *c->bk.align_max_cells;
+    if (c->bk.sample_chunk_words) lim.chunk_tb_words = *c->bk.sample_chunk_words;
+    if (c->bk.sample_walk_entries) lim.walk_entries = *c->bk.sample_walk_entries;
+    if (c->bk.rank_table_bytes) lim.chunk_table_bytes = *c->bk.rank_table_bytes;
+    lim.scratch_rows_cap = gabatch::scratch_rows_cap(max_waves);
+    lim.count_rows_cap = gabatch::count_rows_cap(max_waves);
+    gabatch::RankPlan plan;
+    std::string why;
+    if (int r = gabatch::plan_batch_rank(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, rank_off, lim, plan,
+                                         why))
+        return fail(r, why);
+    const int64_t nslots = rank_off[npairs];
+    if (nslots > 0 && (!ranks || !chars || !out_a || !out_mid || !out_b || !out_off || !out_len || !rank_status))
+        return fail(GA_E_ARG, "null argument");
+    auto len_of = [&](int64_t s) { return seq_off[s + 1] - seq_off[s]; };
+    // What left the kernel route is ranked from a single-pair fill with stored words or not at all: the lowest pair
+    // that cannot be is refused before anything is launched (ga_batch_count's rule and reasons).
+    {
+        int64_t bad = -1, avail = -1;
+        const char* reason = nullptr;
+        for (const int64_t k : plan.single) {
+            if (bad >= 0 && k > bad) continue;
+            const int64_t m = len_of(pair_a[k]), n = len_of(pair_b[k]);
+            const char* r = nullptr;
+            if (std::min(m, n) < 2) {
+                r = "ranks need sequences of at least two letters";
+            } else {
+                if (avail < 0) avail = c->wk.tb_band_rows ? 0 : dev_avail_bytes(c, (int64_t)c->fb.tb.cap);
+                if (gawalk::band_rows(m, n, plan.CB, c->wk, avail) != 0)
+                    r = "traceback words exceed the budget, and ranking has no banded route";
+                else if (gabatch::needs_scratch(m, n) && m > gabatch::count_rows_cap(W))
+                    r = "edge column exceeds the count scratch";
+            }
+            if (r) bad = k, reason = r;
+        }
+        if (bad >= 0) return fail(GA_E_ARG, "pair " + std::to_string(bad) + ": " + reason);
+    }
+    for (int64_t k = 0; k < npairs; k++)
+        if (int r = check_out_capacity(seq_off, pair_a, pair_b, k, out_off, rank_off[k], rank_off[k + 1])) return r;
+    if (int r = refuse_slab_single(c, plan.single, "fill")) return r;
+    const gabatch::WalkOut out{chars, out_a, out_mid, out_b, out_off, out_len, rank_status};
+    HIPCHK(c->br_out.ensure(sizeof(uint64_t) * npairs));
+    HIPCHK(c->br_ticket.ensure(sizeof(unsigned)));
+    HIPCHK(c->br_ranks.ensure(sizeof(uint64_t) * std::max<int64_t>(nslots, 1)));
+    if (nslots > 0)
+        HIPCHK(hipMemcpyAsync(c->br_ranks.p, ranks, sizeof(uint64_t) * nslots, hipMemcpyHostToDevice, c->stream));
+    double walk_ticks = 0, walk_steps = 0;
+
+    // The pairs of one fill: their work list, slices and tables' places on the device, their words in tb (tb_words
+    // u32s, `layout`, `tc`), their tables in br_table (table_entries u64s).
+    struct Filled {
+        const std::vector<ga_batch_item>& items;
+        const ga_batch_item* items_dev;
+        const ga_batch_words_item* words_dev;
+        const int64_t* toff_dev;
+        const uint32_t* tb;
+        int64_t tb_words;
+        int CB, layout, tc;
+        int64_t table_entries;
+    };
+    // The table launch behind the fill on the context's stream, between the events c->wev; edge_rows: the HBM edge
+    // rows a wave needs (0: none).
+    auto enqueue_table = [&](const Filled& f, int waves, int64_t edge_rows) -> int {
+        if (edge_rows > 0) HIPCHK(c->bc_scratch.ensure(sizeof(ulonglong2) * 2 * (size_t)edge_rows * waves));
+        // the ticket starts at zero for every launch
+        HIPCHK(hipMemsetAsync(c->br_ticket.p, 0, sizeof(unsigned), c->stream));
+        HIPCHK(hipEventRecord(c->wev[0], c->stream));
+        const ga::RankTableArgs q{cs->gap_open, f.items_dev, f.words_dev, f.toff_dev, (int)f.items.size(),
+                                  c->br_ticket.as<unsigned>(), c->br_out.as<unsigned long long>(), (long long)npairs, f.tb,
+                                  (long long)f.tb_words, f.tc, c->br_table.as<unsigned long long>(),
+                                  (long long)f.table_entries, edge_rows > 0 ? c->bc_scratch.as<ulonglong2>() : nullptr,
+                                  (long long)edge_rows};
+        ga::launch_batch_rank_table(c->stream, q, f.CB, f.layout, waves);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->wev[1], c->stream));
+        c->batch_rank_info[4]++;
+        return GA_OK;
+    };
+    // pair: the pair the message names, or -1 where batch_single_pair names it itself
+    auto take_count = [&](uint64_t got, int64_t k, int64_t pair) -> int {
+        if (got == 0)
+            return fail(GA_E_STATE, (pair >= 0 ? "pair " + std::to_string(pair) + ": " : std::string()) +
+                                        "work item does not fit the table launch");
+        count_out[k] = got;
+        c->batch_rank_info[7] += got == gabatch::kRankCap;
+        return GA_OK;
+    };
+    // The walk launches `launches` over `witems` (both counted from 0 here) of the filled pairs, each behind what is on
+    // the stream; then the copies back and the strings.
+    auto run_walks = [&](const Filled& f, const ga_batch_rank_item* witems, const gabatch::RankLaunch* launches,
+                         int64_t nlaunch) -> int {
+        for (int64_t L = 0; L < nlaunch; L++) {
+            const gabatch::RankLaunch& wl = launches[L];
+            const ga_batch_rank_item* wi = witems + wl.first;
+            const int64_t nw = wl.count;
+            HIPCHK(c->br_items.ensure(sizeof(ga_batch_rank_item) * nw));
+            HIPCHK(c->bt_walk.ensure(sizeof(int4) * 2 * wl.slots));
+            HIPCHK(c->bt_ops.ensure(sizeof(uint32_t) * wl.ops_words));
+            HIPCHK(hipMemcpyAsync(c->br_items.p, wi, sizeof(ga_batch_rank_item) * nw, hipMemcpyHostToDevice, c->stream));
+            // a slot no item reports to keeps status -1; the ticket starts at zero for every launch
+            HIPCHK(hipMemsetAsync(c->bt_walk.p, 0xff, sizeof(int4) * 2 * wl.slots, c->stream));
+            HIPCHK(hipMemsetAsync(c->br_ticket.p, 0, sizeof(unsigned), c->stream));
+            const int waves = (int)((std::min<int64_t>(max_waves, nw) + W - 1) / W * W);
+            std::vector<int4> walked((size_t)wl.slots * 2);
+            std::vector<uint32_t> ops((size_t)wl.ops_words);
+            HIPCHK(hipEventRecord(c->rev[0], c->stream));
+            const ga::RankWalkArgs q{cs->gap_open, f.items_dev, f.words_dev, f.toff_dev, (int)f.items.size(),
+                                     c->br_items.as<ga_batch_rank_item>(), (int)nw, c->br_ticket.as<unsigned>(),
+                                     c->br_ranks.as<unsigned long long>(), (long long)nslots, c->bt_ops.as<uint32_t>(),
+                                     (long long)wl.ops_words, c->bt_walk.as<int4>(), (long long)wl.slots, f.tb,
+                                     (long long)f.tb_words, f.tc, c->br_table.as<unsigned long long>(),
+                                     (long long)f.table_entries};
+            ga::launch_batch_rank_walk(c->stream, q, f.CB, f.layout, waves);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(c->rev[1], c->stream));
+            c->batch_rank_info[5]++;
+            HIPCHK(hipMemcpyAsync(walked.data(), c->bt_walk.p, sizeof(int4) * 2 * wl.slots, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(ops.data(), c->bt_ops.p, sizeof(uint32_t) * ops.size(), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            float walk_ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&walk_ms, c->rev[0], c->rev[1]));
+            c->batch_rank_ms[2] += walk_ms;
+            const double t_dec = now_ms();
+            gabatch::run_shares(nw, gabatch::rng_threads(c->bk.rng_threads, nw), [&](int64_t first, int64_t stride) {
+                for (int64_t t = first; t < nw; t += stride) {
+                    const ga_batch_item& it = f.items[(size_t)wi[t].fill];
+                    const int64_t wps = ((int64_t)it.m + it.n + 15) / 16;
+                    for (int64_t l = 0; l < wi[t].nslots; l++) {
+                        const int32_t* wr = reinterpret_cast<const int32_t*>(&walked[2 * (size_t)(wi[t].res + l)]);
+                        const int64_t slot = wi[t].out + l;
+                        if (wr[4] == gabatch::kRankOutOfRange) {
+                            rank_status[slot] = 1;
+                            out_len[slot] = 0;
+                        } else {
+                            gabatch::decode_walk(it, wr, ops.data() + wi[t].ops_off + l * wps, slot,
+                                                 wr[4] != gabatch::kRankOk, out);
+                        }
+                    }
+                }
+            });
+            c->batch_rank_ms[3] += (float)(now_ms() - t_dec);
+            for (int64_t t = 0; t < nw; t++) {
+                // (batch_single_pair names the pair of a large-route walk itself)
+                const int64_t k = f.layout == gabatch::LAYOUT_BATCH ? f.items[(size_t)wi[t].fill].out : -1;
+                for (int64_t l = 0; l < wi[t].nslots; l++) {
+                    if (int r = check_decoded(out_len[wi[t].out + l], k, "walk item does not fit the walk launch")) return r;
+                    walk_steps += walked[2 * (size_t)(wi[t].res + l)].x;
+                }
+                walk_ticks += walked[2 * (size_t)wi[t].res + 1].y;
+            }
+            c->batch_rank_info[6] += wl.slots;
+        }
+        return GA_OK;
+    };
+    for (hipEvent_t& e : c->rev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+
+    // the kernel pairs, fill chunk by fill chunk
+    for (size_t ci = 0; ci < plan.chunks.size(); ci++) {
+        const gabatch::FillChunk& ch = plan.chunks[ci];
+        const std::vector<ga_batch_item> items(plan.kernel.begin() + ch.first, plan.kernel.begin() + ch.first + ch.count);
+        BatchStage bs;
+        if (int r = stage_batch(c, codes, seq_off, nseq, npairs, cs, items, plan.scratch_rows, bs)) return r;
+        HIPCHK(c->bs_words.ensure(sizeof(ga_batch_words_item) * items.size()));
+        HIPCHK(c->br_toff.ensure(sizeof(int64_t) * items.size()));
+        if (c->bs_tb.ensure(sizeof(uint32_t) * (size_t)ch.tb_words) != hipSuccess ||
+            c->br_table.ensure(sizeof(uint64_t) * (size_t)plan.chunk_table[ci]) != hipSuccess) {
+            (void)hipStreamSynchronize(c->stream);  // the staged uploads read this call's buffers
+            return fail(GA_E_NOMEM, "no device memory for the batch's traceback words and count tables");
+        }
+        HIPCHK(hipMemcpyAsync(c->bs_words.p, plan.words.data() + ch.first, sizeof(ga_batch_words_item) * items.size(),
+                              hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->br_toff.p, plan.table_off.data() + ch.first, sizeof(int64_t) * items.size(),
+                              hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipEventRecord(c->fb.ev[0], c->stream));
+        const ga::WordsArgs q{bs.args, c->bs_words.as<ga_batch_words_item>(), c->bs_tb.as<uint32_t>(),
+                              (long long)ch.tb_words};
+        ga::launch_batch_words(c->stream, q, plan.qbytes, plan.CB, bs.waves);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->fb.ev[1], c->stream));
+        c->batch_rank_info[3]++;
+        const Filled f{items, c->bt_items.as<ga_batch_item>(), c->bs_words.as<ga_batch_words_item>(),
+                       c->br_toff.as<int64_t>(), c->bs_tb.as<uint32_t>(), ch.tb_words, plan.CB, gabatch::LAYOUT_BATCH, 0,
+                       plan.chunk_table[ci]};
+        if (int r = enqueue_table(f, bs.waves, plan.count_rows)) return r;
+        std::vector<long long> got((size_t)npairs);
+        std::vector<uint64_t> cnt((size_t)npairs);
+        HIPCHK(hipMemcpyAsync(got.data(), c->bt_out.p, sizeof(long long) * npairs, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(cnt.data(), c->br_out.p, sizeof(uint64_t) * npairs, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        float table_ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&c->fill_ms, c->fb.ev[0], c->fb.ev[1]));
+        HIPCHK(hipEventElapsedTime(&table_ms, c->wev[0], c->wev[1]));
+        c->batch_rank_ms[0] += c->fill_ms;
+        c->batch_rank_ms[1] += table_ms;
+        if (int r = take_batch_costs(got, items.data(), items.size(), cost_out)) return r;
+        for (const ga_batch_item& it : items)
+            if (int r = take_count(cnt[(size_t)it.out], it.out, it.out)) return r;
+        c->batch_rank_info[0] += (int64_t)items.size();
+        c->batch_rank_info[2]++;
+        if (int r = run_walks(f, plan.walk.data(), plan.launches.data() + ch.launch_first, ch.launch_count)) return r;
+    }
+
+    // A pair that left the kernel route for its size: one single-pair fill with stored words, as ga_batch_count's
+    // large route, then one wave makes its table from c->fb.tb in that fill's layout and its slots walk it.  They go
+    // through the context's problem slot, so no problem is loaded afterwards.
+    for (const int64_t k : plan.single) {
+        const int64_t sa = pair_a[k], sb = pair_b[k];
+        const int64_t m = len_of(sa), n = len_of(sb);
+        c->rc_used = false;
+        auto fill = [&](int64_t, int64_t) -> int {
+            if (band_rows(c) != 0) return fail(GA_E_ARG, "traceback words exceed the budget, and ranking has no banded route");
+            if (int r = enqueue_fill(c, GA_FILL_TRACEBACK)) return r;
+            if (int r = finish_fill(c, &cost_out[k], nullptr)) return r;
+            c->batch_rank_ms[6] += c->fill_ms;
+            c->batch_rank_info[3]++;
+            const gaplan::FillPlan& pl = c->plan;
+            const int64_t tb_words = (int64_t)pl.nstripes * pl.T * pl.TC * 256;
+            if ((int64_t)pl.TC * (16 / c->CB) < m || tb_words < gabatch::stripe_words(n, pl.TC))
+                return fail(GA_E_STATE, "the fill's words do not cover the pair");
+            ga_batch_item it{(int32_t)seq_off[sa], (int32_t)m, (int32_t)seq_off[sb], (int32_t)n, 0, (int32_t)k, 0, 0};
+            gabatch::stripe_geometry(n, it.T, it.nstripes);
+            const std::vector<ga_batch_item> items(1, it);
+            const ga_batch_words_item ws{0, tb_words};
+            const int64_t toff = 0, entries = gabatch::rank_table_entries(m, it.T, it.nstripes);
+            std::vector<ga_batch_rank_item> walk;
+            std::vector<gabatch::RankLaunch> launches;
+            gabatch::plan_rank_launches(items.data(), 1, rank_off, lim.walk_entries, walk, launches);
+            HIPCHK(c->bt_items.ensure(sizeof(ga_batch_item)));
+            HIPCHK(c->bs_words.ensure(sizeof(ga_batch_words_item)));
+            HIPCHK(c->br_toff.ensure(sizeof(int64_t)));
+            if (c->br_table.ensure(sizeof(uint64_t) * (size_t)entries) != hipSuccess)
+                return fail(GA_E_NOMEM, "no device memory for the pair's count table");
+            HIPCHK(hipMemcpyAsync(c->bt_items.p, &it, sizeof(it), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->bs_words.p, &ws, sizeof(ws), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->br_toff.p, &toff, sizeof(toff), hipMemcpyHostToDevice, c->stream));
+            const Filled f{items, c->bt_items.as<ga_batch_item>(), c->bs_words.as<ga_batch_words_item>(),
+                           c->br_toff.as<int64_t>(), c->fb.tb.as<uint32_t>(), tb_words, c->CB, gabatch::LAYOUT_STRIPE, pl.TC,
+                           entries};
+            if (int r = enqueue_table(f, W, gabatch::needs_scratch(m, n) ? m : 0)) return r;
+            uint64_t got = 0;
+            HIPCHK(hipMemcpyAsync(&got, c->br_out.as<uint64_t>() + k, sizeof(got), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));  // (the uploads' sources live until here)
+            float table_ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&table_ms, c->wev[0], c->wev[1]));
+            c->batch_rank_ms[7] += table_ms;
+            c->batch_rank_info[1]++;
+            if (int r = take_count(got, k, -1)) return r;
+            return run_walks(f, walk.data(), launches.data(), (int64_t)launches.size());
+        };
+        if (int r = batch_single_pair(c, codes, seq_off, pair_a, pair_b, pair_max_cost, cs, k, fill)) return r;
+        c->filled_tb = false;
+    }
+    c->batch_rank_ms[4] = (float)(now_ms() - t_call);
+    c->batch_rank_ms[5] = (float)(10.0 * walk_ticks / std::max(walk_steps, 1.0));  // (a tick is 10 ns)
+    return GA_OK;
+}
+
+int ga_batch_rank_info(ga_ctx* c, int64_t* out8) { return copy_figures(c, &ga_ctx::batch_rank_info, out8); }
+int ga_batch_rank_timings(ga_ctx* c, float* out8) { return copy_figures(c, &ga_ctx::batch_rank_ms, out8); }
 int ga_batch_count_info(ga_ctx* c, int64_t* out8) { return copy_figures(c, &ga_ctx::batch_count_info, out8); }
 int ga_batch_count_timings(ga_ctx* c, float* out8) { return copy_figures(c, &ga_ctx::batch_count_ms, out8); }
 int ga_batch_sample_info(ga_ctx* c, int64_t* out8) { return copy_figures(c, &ga_ctx::batch_sample_info, out8); }
@@ -898,6 +1176,15 @@ int ga_batch_count(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int6
                    int64_t* cost_out, double* count_out) {
     return guard_end(c, batch_count_impl(c, codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, cost_out,
                                          count_out));
+}
+
+int ga_batch_rank(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                  const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                  const int64_t* rank_off, const uint64_t* ranks, const char* chars, char* out_a, char* out_mid,
+                  char* out_b, const int64_t* out_off, int64_t* out_len, int32_t* rank_status, int64_t* cost_out,
+                  uint64_t* count_out) {
+    return guard_end(c, batch_rank_impl(c, codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, rank_off, ranks,
+                                        chars, out_a, out_mid, out_b, out_off, out_len, rank_status, cost_out, count_out));
 }
 
 int ga_debug_pair_tables(ga_ctx* c, const uint64_t* seeds, const int32_t* steps, int64_t nitems, int32_t route,

@@ -8,6 +8,7 @@ struct ga_batch_item;  // ga_batch.h
 struct ga_batch_walk_item;
 struct ga_batch_words_item;
 struct ga_batch_sample_item;
+struct ga_batch_rank_item;
 namespace gabrng {
 struct Item;  // ga_batch_rng.h
 }
@@ -297,6 +298,51 @@ struct CountArgs {
     long long scratch_rows;
 };
 void launch_batch_count(hipStream_t s, const CountArgs& q, int CB, int layout, int waves);
+// co-optimal alignments by rank (ga_batch_rank; ga_batch_rank.hip): batch_rank_table_kernel keeps every
+// interior cell's three saturating u64 path counts in the pair's table (gabatch::rank_table_index, ga_batch_rank.h),
+// one wave per pair; batch_rank_walk_kernel, a later launch, walks a pair once per requested rank, one lane per walk
+struct RankTableArgs {
+    int o;                               // the gap-open cost (the words' rank test)
+    const ga_batch_item* items;          // the chunk's work list, as the fill had it
+    const ga_batch_words_item* words;    // parallel to items
+    const int64_t* table_off;            // parallel to items: the pair's table in `table`, in u64 entries
+    int nitems;
+    unsigned* ticket;                    // the table launch's own ticket word, zeroed by the host
+    unsigned long long* count_out;       // [npairs] min(count, 2^64 - 1), indexed by ga_batch_item::out; 0: the item
+                                         // does not fit
+    long long npairs;
+    const uint32_t* tb;                  // the words, written by an earlier launch and only read here
+    long long tb_words;
+    int tc;                              // LAYOUT_STRIPE: 16-byte words per lane of the fill that wrote tb
+    unsigned long long* table;           // the chunk's count tables
+    long long table_entries;
+    ulonglong2* scratch;                 // [waves][2][scratch_rows] edge columns in HBM (nullptr: no pair needs them)
+    long long scratch_rows;
+};
+struct RankWalkArgs {
+    int o;
+    const ga_batch_item* items;          // the chunk's work list, as the fill had it
+    const ga_batch_words_item* words;    // parallel to items
+    const int64_t* table_off;            // parallel to items
+    int nfill;
+    const ga_batch_rank_item* witems;    // this launch's walk items: up to 64 slots of a pair each
+    int nwalk;
+    unsigned* ticket;                    // the walks' own ticket word, zeroed by the host
+    const unsigned long long* ranks;     // the call's ranks, slot f at ranks[f]
+    long long nranks;
+    uint32_t* ops;                       // the chosen levels, item t's slot l at witems[t].ops_off + l * ceil((m + n) / 16)
+    long long ops_words;
+    int4* walk_out;                      // [nslots][2] {dispatches, i, j, reason}, {status (gabatch::kRankOk, ...), the
+                                         // item's walk ticks in its first slot, 0, 0}, slot l of item t at witems[t].res + l
+    long long nslots;
+    const uint32_t* tb;                  // the words and the tables, written by earlier launches and only read here
+    long long tb_words;
+    int tc;
+    const unsigned long long* table;
+    long long table_entries;
+};
+void launch_batch_rank_table(hipStream_t s, const RankTableArgs& q, int CB, int layout, int waves);
+void launch_batch_rank_walk(hipStream_t s, const RankWalkArgs& q, int CB, int layout, int waves);
 // the device-routed items' tie-break tables, one wave per item (batch_rng_kernel, ga_batch_rng.hip)
 struct RngArgs {
     const gabrng::Item* items;   // seed, steps and tab_off of each item

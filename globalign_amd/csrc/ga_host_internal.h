@@ -284,6 +284,13 @@ struct ga_ctx {
     DevBuf bc_out, bc_ticket, bc_scratch;
     int64_t batch_count_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     float batch_count_ms[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    // ga_batch_rank fills as ga_batch_count does and adds the chunk's count tables and the pairs'
+    // places in them, the u64 counts, the call's ranks, a walk launch's items and the two launches' ticket word (the
+    // edge columns go through bc_scratch, the walks' results and level words through bt_walk and bt_ops);
+    // ga_batch_rank_info's and _timings's figures of its last call
+    DevBuf br_table, br_toff, br_out, br_ranks, br_items, br_ticket;
+    int64_t batch_rank_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    float batch_rank_ms[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int walk_jump_diag[3] = {0, 0, 0};  // the tie-to-tie walk's trips, region re-checks, ties (result[12..14])
     DevBuf jlut;           // the jump workers' LUT for gap open jlut_o (ga::jump_lut_build)
     int jlut_o = -1;

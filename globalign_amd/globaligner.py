@@ -26,7 +26,8 @@ from pathlib import Path
 import numpy as np
 
 from . import _native
-from .results import AlignmentResults, BatchAlignments, BatchCounts, BatchSamples, BatchScores, final_cost_to_score
+from .results import (AlignmentResults, BatchAlignments, BatchCounts, BatchRanked, BatchSamples, BatchScores,
+                      final_cost_to_score)
 from .scoring import MAX_SEQ_LEN_PROD, get_max_val, validate_and_transform_args
 
 __version__ = "0.1.0"
@@ -220,6 +221,91 @@ class GlobalAligner:
         return BatchCounts(counts, counts < 2.0 ** 53, costs, b.scores(costs), b.scoring_mat, b.costing_mat,
                            b.gap_open_score, b.gap_open_cost)
 
+    def alignments_by_rank(self, seqs_1, seqs_2, ranks):
+        """The co-optimal alignments of seqs_1[k] with seqs_2[k] that ``ranks[k]`` names, for every k.  The reference
+        breaks traceback ties with random.choice, so a pair has a family of co-optimal alignments (``count_alignments``
+        says how many).  They are ordered by the levels the traceback emits, from the alignment's last column
+        backwards: at the first column where two of them differ, a column of both letters comes before a gap in seq_1,
+        and that before a gap in seq_2; the forced tail after the first row or column adds nothing.  Rank r is the
+        r-th alignment of that order, from 0.  ``ranks`` holds one sequence of ints per pair (it may be empty: the pair
+        is only counted), each in [0, 2**64 - 1).  The GPU fills the pair once, keeps the number of paths below every
+        state of the traceback, and walks down from the last cell entering, at every tie, the branch whose path count
+        contains the rank; no random number is drawn and the process-global ``random`` state is not touched.
+        ``counts[k]`` is min(the pair's count, 2**64 - 1): the counts saturate there, and every rank below counts[k] is
+        exact all the same.  Validation is count_alignments's; a rank that is not below its pair's count raises
+        ValueError for the lowest pair and slot.
+        -> BatchRanked."""
+        return self._ranked("alignments_by_rank", seqs_1, seqs_2, ranks)
+
+    def _ranked(self, method, seqs_1, seqs_2, ranks):
+        """alignments_by_rank under the name `method` (the name in the messages)."""
+        _, b, _ = self._strings_batch(method, seqs_1, seqs_2, "host", lambda P: None)
+        per_pair = _rank_lists(ranks, 0 if b is None else len(b.pair_a))
+        if b is None:
+            e = self._empty_batch((0,))
+            return BatchRanked([], [], [], e.costs, e.scores, [], np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=bool),
+                               *e[2:])
+        lens = np.diff(b.seq_off)
+        short = np.flatnonzero(np.minimum(lens[b.pair_a], lens[b.pair_b]) < 2)
+        if short.size:
+            raise ValueError(f"pair {int(short[0])}: {method} needs sequences of at least two letters")
+        rank_off = np.concatenate([[0], np.cumsum([len(r) for r in per_pair])]).astype(np.int64)
+        flat = np.concatenate(per_pair) if per_pair else np.zeros(0, dtype=np.uint64)
+        eng = _native.default_engine(self.device)
+        costs, counts, status, lengths, offsets, bufs = eng.batch_rank(b.codes, b.seq_off, b.pair_a, b.pair_b, b.tables,
+                                                                       rank_off, flat,
+                                                                       np.frombuffer(b.text, dtype=np.uint8),
+                                                                       b.pair_max_cost)
+        failed = np.flatnonzero(status != 0)
+        if failed.size:
+            k = int(np.searchsorted(rank_off, failed[0], side="right")) - 1
+            raise ValueError(f"pair {k}: rank {int(flat[failed[0]])} is not below the pair's count {int(counts[k])}")
+        cut = list(zip(rank_off[:-1].tolist(), rank_off[1:].tolist()))
+        strings = [[flat_strings[x:y] for x, y in cut] for flat_strings in _cut_strings(bufs, offsets, lengths)]
+        return BatchRanked(strings[0], strings[1], strings[2], costs, b.scores(costs), per_pair, counts,
+                           counts == np.uint64(2 ** 64 - 1), b.scoring_mat, b.costing_mat, b.gap_open_score,
+                           b.gap_open_cost)
+
+    def enumerate_alignments(self, seqs_1, seqs_2, limit=1024):
+        """The first min(count, limit) co-optimal alignments of every pair in rank order (alignments_by_rank has the
+        order): the pair's whole family where ``complete(k)`` says so.  ``limit`` is an int >= 1.  Two
+        alignments_by_rank calls: one without ranks for the counts, one for the ranks 0 .. min(counts[k], limit) - 1, so
+        the pairs are filled and their count tables made twice -- that keeps the engine to one mode.
+        -> BatchRanked."""
+        if not isinstance(limit, numbers.Integral) or isinstance(limit, bool):
+            raise TypeError("limit must be an int")
+        if int(limit) < 1:
+            raise ValueError("limit must be at least 1")
+        seqs_1, seqs_2 = list(seqs_1), list(seqs_2)
+        counted = self._ranked("enumerate_alignments", seqs_1, seqs_2, [()] * min(len(seqs_1), len(seqs_2)))
+        return self._ranked("enumerate_alignments", seqs_1, seqs_2,
+                            [range(min(int(c), int(limit))) for c in counted.counts])
+
+    def sample_alignments_uniform(self, seqs_1, seqs_2, samples, seed=0):
+        """Co-optimal alignments of every pair drawn uniformly from the pair's family: every one of its counts[k]
+        alignments is as likely as any other, unlike ``sample_alignments``, whose random.choice per traceback step draws
+        an alignment through many ties far less often than one through few.  ``samples`` is an int S >= 1 (every pair
+        gets S) or one int >= 1 per pair; ``seed`` an int.  The ranks are drawn by ``rng = random.Random(seed)``, pair by
+        pair and sample by sample, as ``rng.randrange(counts[k])``, and handed to one alignments_by_rank call (a call
+        without ranks ahead of it gets the counts): the result is reproducible, and the process-global ``random`` state
+        is not touched.  A pair whose count is saturated (2**64 - 1 or more alignments) raises ValueError, the lowest
+        such pair first: a u64 rank cannot index its family.
+        -> BatchRanked."""
+        seqs_1, seqs_2 = list(seqs_1), list(seqs_2)
+        if not isinstance(seed, numbers.Integral):
+            raise TypeError("seed must be an int")
+        P = min(len(seqs_1), len(seqs_2))
+        # (unequal lists are the first call's to refuse)
+        per_pair = _sample_seeds(samples, 0, P)[0] if len(seqs_1) == len(seqs_2) else None
+        counted = self._ranked("sample_alignments_uniform", seqs_1, seqs_2, [()] * P)
+        full = np.flatnonzero(counted.saturated)
+        if full.size:
+            raise ValueError(f"pair {int(full[0])}: the count is saturated (2**64 - 1 or more co-optimal alignments), "
+                             "a uniform rank cannot be drawn")
+        rng = random.Random(int(seed))
+        ranks = [[rng.randrange(int(counted.counts[k])) for _ in range(per_pair[k])] for k in range(P)]
+        return self._ranked("sample_alignments_uniform", seqs_1, seqs_2, ranks)
+
     def _strings_batch(self, method, seqs_1, seqs_2, tables, seeds_of):
         """The front half of align_pairs and sample_alignments (`method`: the name in the messages): the checks in their
         order, the seeds by seeds_of(P), and the batch.  -> (seeds, the _prepare_batch namespace or None for no pairs,
@@ -399,6 +485,34 @@ def _pair_seeds(seeds, P):
     if isinstance(seeds, numbers.Integral):
         return np.uint64(values[0]) + np.arange(P, dtype=np.uint64)
     return np.array(values, dtype=np.uint64)
+
+
+def _rank_lists(ranks, P):
+    """alignments_by_rank's ranks as a list of P uint64 arrays: one sequence of ints per pair (it may be empty), every
+    rank in [0, 2**64 - 1)."""
+    if isinstance(ranks, (str, bytes, numbers.Integral)):
+        raise TypeError("ranks must be a sequence with one sequence of ints per pair")
+    try:
+        per_pair = list(ranks)
+    except TypeError:
+        raise TypeError("ranks must be a sequence with one sequence of ints per pair") from None
+    if len(per_pair) != P:
+        raise ValueError(f"ranks must have one entry per pair, got {len(per_pair)} for {P} pairs")
+    out = []
+    for k, own in enumerate(per_pair):
+        if isinstance(own, (numbers.Integral, str, bytes)):
+            raise TypeError("ranks must be a sequence with one sequence of ints per pair")
+        try:
+            own = list(own)
+        except TypeError:
+            raise TypeError("ranks must be a sequence with one sequence of ints per pair") from None
+        if not all(isinstance(v, numbers.Integral) for v in own):
+            raise TypeError(f"pair {k}: ranks must be ints")
+        own = [int(v) for v in own]
+        if any(v < 0 or v >= 2 ** 64 - 1 for v in own):
+            raise ValueError(f"pair {k}: every rank must be in [0, 2**64 - 1)")
+        out.append(np.array(own, dtype=np.uint64))
+    return out
 
 
 def _sample_seeds(samples, seeds, P):

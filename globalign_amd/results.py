@@ -203,3 +203,38 @@ class BatchCounts(NamedTuple):
     def count(self, k):
         """Pair k's count: a Python int when it is exact, else the float."""
         return int(self.counts[k]) if self.exact[k] else float(self.counts[k])
+
+
+class BatchRanked(NamedTuple):
+    """Co-optimal alignments of every pair by rank (GlobalAligner.alignments_by_rank, enumerate_alignments,
+    sample_alignments_uniform): per pair a list with one string per requested rank, for each of the three lines; the
+    pair's cost and score in numpy int64 arrays of shape (P,); per pair the uint64 array of the ranks asked for; counts:
+    numpy uint64, shape (P,), min(the pair's number of co-optimal alignments, 2**64 - 1) -- every rank below it is exact
+    whatever the true count; saturated: numpy bool, counts == 2**64 - 1; and the settings, as BatchAlignments reports
+    them."""
+    seq_1_aligned: list
+    middle_part: list
+    seq_2_aligned: list
+    costs: "numpy.ndarray"
+    scores: "numpy.ndarray"
+    ranks: list
+    counts: "numpy.ndarray"
+    saturated: "numpy.ndarray"
+    scoring_mat: dict
+    costing_mat: dict
+    gap_open_score: int
+    gap_open_cost: int
+
+    def result(self, k, t):
+        """Entry t of pair k (the alignment of rank ranks[k][t]) as an AlignmentResults (output=None), with the batch's
+        matrices."""
+        return AlignmentResults(self.seq_1_aligned[k][t], self.middle_part[k][t], self.seq_2_aligned[k][t],
+                                int(self.costs[k]), int(self.scores[k]), self.scoring_mat, self.costing_mat,
+                                self.gap_open_score, self.gap_open_cost, None)
+
+    def complete(self, k):
+        """Whether pair k's entries are the pair's whole family of co-optimal alignments, in rank order: its count is not
+        saturated and ranks[k] is exactly 0 .. counts[k] - 1."""
+        n = int(self.counts[k])
+        r = self.ranks[k]
+        return not bool(self.saturated[k]) and len(r) == n and all(int(x) == q for q, x in enumerate(r))

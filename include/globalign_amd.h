@@ -236,6 +236,48 @@ int ga_batch_count_info(ga_ctx* ctx, int64_t* out8);
 /* out8 = {batch_words_kernel ms, batch_count_kernel ms over those pairs, single-pair fills ms, batch_count_kernel ms
  * over their pairs, whole call wall ms, 0, 0, 0} of the last ga_batch_count, summed over its launches. */
 int ga_batch_count_timings(ga_ctx* ctx, float* out8);
+/* Co-optimal alignments by rank.  The alignments the traceback
+ * can return for pair k are ordered by their level sequence as the traceback
+ * emits it, from the alignment's last column backwards, lexicographically with
+ * diagonal < gap in seq_1 < gap in seq_2; rank r names the r-th of them, from 0.
+ * Pair k has the slots rank_off[k] .. rank_off[k + 1] (npairs + 1 entries from
+ * 0, at most 2^31 - 1 slots; a pair without slots is legal: it is filled and
+ * counted, nothing is walked) and slot f asks for rank ranks[f].  Its strings go
+ * to out_a / out_mid / out_b at out_off[f] (slots + 1 entries, m + n characters
+ * a slot at least), out_len[f] bytes each; rank_status[f] receives 0, or 1 for
+ * a rank that is not below the pair's count: such a slot draws no walk and has
+ * out_len[f] = 0.  count_out[k] receives min(count, 2^64 - 1) -- the counts are
+ * u64 that saturate; every rank below that value is exact, whatever the true
+ * count -- and cost_out[k] pair k's cost.  codes .. costs and chars are
+ * ga_batch_sample's, with ga_batch_count's checks, errors ("pair <k>: ...") and
+ * refusals.  No seeds, no tables, no random numbers.
+ * Kernel pairs are filled chunk by chunk by batch_words_kernel as for
+ * ga_batch_count; batch_rank_table_kernel, one wave per pair, keeps the three
+ * path counts of every cell in the pair's table, 24 (m + 63) 64 T bytes a stripe
+ * of 64 T columns, and batch_rank_walk_kernel walks a pair once per slot, one
+ * lane per walk, 64 slots of a pair to a wave; both are later launches on the
+ * same stream.  A chunk closes when its words would exceed
+ * GA_BATCH_SAMPLE_CHUNK_WORDS or its tables GA_BATCH_RANK_TABLE_BYTES (option,
+ * default 2^33: 8 GiB); a pair whose own table exceeds that is refused with
+ * GA_E_ARG before any launch, the lowest such pair first.  A chunk's walks are
+ * cut into launches of at most GA_BATCH_SAMPLE_WALK_ENTRIES steps (m + n a
+ * slot).  A pair that leaves the kernel route for its size is filled by the
+ * single-pair fill with stored traceback words; one wave makes its table and
+ * the same walk kernel walks it. */
+int ga_batch_rank(ga_ctx* ctx, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                  const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* costs,
+                  const int64_t* rank_off, const uint64_t* ranks, const char* chars, char* out_a, char* out_mid,
+                  char* out_b, const int64_t* out_off, int64_t* out_len, int32_t* rank_status, int64_t* cost_out,
+                  uint64_t* count_out);
+/* out8 = {pairs on the kernel route, pairs filled by the single-pair fill, fill chunks, fill launches
+ * (batch_words_kernel's and single-pair fills), table launches, walk launches, slots walked, pairs with a saturated
+ * count} of the last ga_batch_rank. */
+int ga_batch_rank_info(ga_ctx* ctx, int64_t* out8);
+/* out8 = {batch_words_kernel ms, batch_rank_table_kernel ms over those pairs, batch_rank_walk_kernel ms, host string
+ * decode ms, whole call wall ms, the walks' ns per step (what each wave timed over the steps of its 64 lanes),
+ * single-pair fills ms, batch_rank_table_kernel ms over their pairs} of the last ga_batch_rank, summed over its
+ * launches. */
+int ga_batch_rank_timings(ga_ctx* ctx, float* out8);
 /* The tie-break tables alone, with no alignment: item t's steps[t] entries under seeds[t], concatenated in
  * tab_out, by route 1 (host) or 2 (device; an item over GA_BATCH_RNG_DEVICE_MAX_STEPS is built on the host, as
  * in the real call).  status_out[t]: 0 complete, 1 the word cap was reached (entries past the stop are

@@ -28,6 +28,12 @@ JSON line per workload with pairs, cells, ms (median of 5 calls after 2 warm-ups
                                                 median, least and most of 5 after 2 warm-ups, with the count launch's
                                                 kernel ms beside the fill's for the same batch (medians over the timed
                                                 calls of the same run), the count's ns per cell, and the counts' range
+    python tools/batch_bench.py --rank          B1 with 16 ranks a pair and S3's 10k x 10k pair with 64 ranks through
+                                                alignments_by_rank, the ranks drawn below the counts a
+                                                first call returns: median, least and most of 5 after 2 warm-ups, with
+                                                the table and walk launches' kernel ms, and count_alignments's count
+                                                launch on the same batch in the same run; B1 once more with the tables'
+                                                cap raised so that it takes one chunk
 
 Workloads (SplitMix64 sequences of tests.conftest, lengths from a seeded random.Random):
   B1  4096 DNA pairs, lengths 200-400         B2  1024 BLOSUM62 pairs, lengths 100-600
@@ -294,6 +300,56 @@ def count_workloads():
     run("S3-count", [(splitmix_seq(10000, 1, "dna"), splitmix_seq(10000, 2, "dna"))])
 
 
+def rank_workloads():
+    def run(name, pairs, nranks, options=None):
+        for k, v in (options or {}).items():
+            _native.OPTIONS[k] = str(v)
+        al = GlobalAligner(max_seq_len_prod=None, **DNA)
+        a, b = [p[0] for p in pairs], [p[1] for p in pairs]
+        eng, parts, cparts, last = _native.default_engine(0), [], [], {}
+        counts = al.alignments_by_rank(a, b, [()] * len(pairs)).counts
+        rng = random.Random(1)
+        ranks = [[rng.randrange(int(c)) for _ in range(nranks)] for c in counts]
+
+        def call():
+            last["res"] = al.alignments_by_rank(a, b, ranks)
+            parts.append(eng.batch_rank_timings())
+
+        def count():
+            al.count_alignments(a, b)
+            cparts.append(eng.batch_count_timings())
+
+        for _ in range(WARMUP):
+            call()
+            count()
+        ms = []
+        for _ in range(REPEATS):
+            t0 = time.perf_counter()
+            call()
+            ms.append((time.perf_counter() - t0) * 1e3)
+            count()
+        parts, cparts, res = parts[-REPEATS:], cparts[-REPEATS:], last["res"]
+        cells = sum(len(x) * len(y) for x, y in pairs)
+        steps = sum(nranks * (len(x) + len(y)) for x, y in pairs)
+        med = {k: round(statistics.median(x[k] for x in parts), 4) for k in parts[0]}
+        cmed = {"count_" + k: round(statistics.median(x[k] for x in cparts), 4) for k in cparts[0]}
+        table_ms = med["table_ms"] + med["single_table_ms"]
+        count_ms = cmed["count_count_ms"] + cmed["count_single_count_ms"]
+        print(json.dumps(dict(workload=name, pairs=len(pairs), ranks=nranks * len(pairs), cells=cells,
+                              ms=round(statistics.median(ms), 4), ms_min=round(min(ms), 4), ms_max=round(max(ms), 4), **med,
+                              **cmed, table_over_count=round(table_ms / count_ms, 3),
+                              table_ns_per_cell=round(table_ms * 1e6 / cells, 4),
+                              walk_ms_per_mstep=round(med["walks_ms"] / steps * 1e6, 4), info=eng.batch_rank_info(),
+                              saturated=int(res.saturated.sum()), options=options or {})), flush=True)
+        for k in options or {}:
+            del _native.OPTIONS[k]
+
+    b1 = pairs_of(4096, 200, 400, "dna", 1)
+    run("B1-rank", b1, 16)
+    run("B1-rank-one-chunk", b1, 16, options={"GA_BATCH_RANK_TABLE_BYTES": 16 << 30})
+    run("S3-rank", [(splitmix_seq(10000, 1, "dna"), splitmix_seq(10000, 2, "dna"))], 64)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--loop", type=int, default=0, metavar="K")
@@ -304,8 +360,11 @@ def main():
     ap.add_argument("--align-crossover", action="store_true")
     ap.add_argument("--sample", action="store_true")
     ap.add_argument("--count", action="store_true")
+    ap.add_argument("--rank", action="store_true")
     args = ap.parse_args()
-    if args.count:
+    if args.rank:
+        rank_workloads()
+    elif args.count:
         count_workloads()
     elif args.sample:
         sample_workloads()
