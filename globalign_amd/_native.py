@@ -19,6 +19,7 @@ GA_FILL_TRACEBACK = 1
 GA_FILL_FULL = 2
 GA_E_NOMEM = -6
 GA_E_GUARD = -7
+GA_E_COUNT = -8
 GA_TB_OK = 0
 GA_TB_INDEX_ERROR = 1
 
@@ -48,6 +49,7 @@ EXPORTS = [
     "ga_batch_sample", "ga_batch_sample_info", "ga_batch_sample_timings",
     "ga_batch_count", "ga_batch_count_info", "ga_batch_count_timings",
     "ga_batch_rank", "ga_batch_rank_info", "ga_batch_rank_timings",
+    "ga_batch_support", "ga_batch_support_info", "ga_batch_support_timings",
     "ga_problem_set_cells",
     "ga_problem_traceback", "ga_problem_align", "ga_problem_align_many", "ga_problem_set_slab", "ga_slab_buffers", "ga_slab_bind_halos",
     "ga_slab_link", "ga_slab_link_export", "ga_slab_link_import", "ga_enable_peer_access",
@@ -130,6 +132,10 @@ def load_library():
                                     pi64, pi64, p32, pi64, C.POINTER(C.c_uint64)]
         L.ga_batch_rank_info.argtypes = [vp, pi64]
         L.ga_batch_rank_timings.argtypes = [vp, C.POINTER(C.c_float)]
+        L.ga_batch_support.argtypes = [vp, vp, pi64, i64, p32, p32, p32, i64, C.POINTER(GaCosts), pi64,
+                                       C.POINTER(C.c_double), pi64, C.POINTER(C.c_double)]
+        L.ga_batch_support_info.argtypes = [vp, pi64]
+        L.ga_batch_support_timings.argtypes = [vp, C.POINTER(C.c_float)]
         L.ga_debug_pair_tables.argtypes = [vp, vp, p32, i64, i32, pu32, p32]
         L.ga_batch_align_timings.argtypes = [vp, C.POINTER(C.c_float)]
         L.ga_debug_seed_state.argtypes = [C.c_uint64, pu32]
@@ -170,7 +176,7 @@ def load_library():
 def _check(rc):
     if rc != 0:
         msg = _lib.ga_last_error().decode(errors="replace")
-        if rc == -1:
+        if rc == -1 or rc == GA_E_COUNT:
             raise ValueError(msg)
         if rc == GA_E_NOMEM:
             raise MemoryError(f"globalign_amd engine: {msg}")
@@ -455,6 +461,40 @@ class Engine:
         _check(self._L.ga_batch_rank_timings(self._h, out))
         return dict(zip(("words_ms", "table_ms", "walks_ms", "decode_ms", "call_ms", "walk_ns_per_step", "single_fill_ms",
                          "single_table_ms"), (float(x) for x in out)))
+
+    def batch_support(self, codes, seq_off, pair_a, pair_b, tables, pair_max_cost=None):
+        """Match support of many pairs in one call (ga_batch_support): batch_costs's arguments.
+        -> (costs int64, counts float64, offsets int64 (P + 1), supports float64): pair k's (m, n) matrix is
+        supports[offsets[k]:offsets[k + 1]], row-major.  A pair whose count is not finite raises ValueError.
+        Afterwards no problem counts as loaded."""
+        b = batch_arrays(codes, seq_off, pair_a, pair_b, pair_max_cost)
+        lens = np.diff(b.seq_off)
+        cells = lens[b.pair_a] * lens[b.pair_b] if b.P else np.zeros(0, dtype=np.int64)
+        offsets = np.concatenate([[0], np.cumsum(cells)]).astype(np.int64)
+        costs, counts = np.zeros(b.P, dtype=np.int64), np.zeros(b.P, dtype=np.float64)
+        supports = np.zeros(max(int(offsets[-1]), 1), dtype=np.float64)
+        pd = C.POINTER(C.c_double)
+        _check(self._L.ga_batch_support(*self._batch_head(b, tables), offsets.ctypes.data_as(_P64),
+                                        supports.ctypes.data_as(pd), costs.ctypes.data_as(_P64),
+                                        counts.ctypes.data_as(pd)))
+        self.m = self.n = 0
+        return costs, counts, offsets, supports
+
+    def batch_support_info(self):
+        """{kernel_pairs, single_fill_pairs, fill_chunks, fill_launches, support_launches, hbm_edge_pairs} of the last
+        batch_support (ga_batch_support_info); a support launch is the N-table, flow and gather kernels of one fill."""
+        out = (C.c_int64 * 8)()
+        _check(self._L.ga_batch_support_info(self._h, out))
+        return dict(zip(("kernel_pairs", "single_fill_pairs", "fill_chunks", "fill_launches", "support_launches",
+                         "hbm_edge_pairs"), (int(x) for x in out)))
+
+    def batch_support_timings(self):
+        """{words_ms, table_ms, flow_ms, gather_ms, single_fill_ms, single_table_ms, single_flow_ms, single_gather_ms} of
+        the last batch_support, summed over its launches."""
+        out = (C.c_float * 8)()
+        _check(self._L.ga_batch_support_timings(self._h, out))
+        return dict(zip(("words_ms", "table_ms", "flow_ms", "gather_ms", "single_fill_ms", "single_table_ms",
+                         "single_flow_ms", "single_gather_ms"), (float(x) for x in out)))
 
     def _batch_head(self, b, tables):
         """The arguments every batched entry begins with."""

@@ -2,8 +2,8 @@
 // with strings (ga_batch_align, at the end); no HIP: built into the engine, into the kernels' translation unit for the
 // work-item layout, and into the planner self-tests, ga_batch_selftest.cpp, ga_batch_align_selftest.cpp,
 // ga_batch_sample_selftest.cpp (ga_batch_sample's planner, after ga_batch_align's), ga_batch_count_selftest.cpp
-// (ga_batch_count's, after that) and ga_batch_rank_selftest.cpp (ga_batch_rank's, at the end), under AddressSanitizer /
-// UBSan.
+// (ga_batch_count's, after that), ga_batch_rank_selftest.cpp (ga_batch_rank's, after that) and
+// ga_batch_support_selftest.cpp (ga_batch_support's, at the end), under AddressSanitizer / UBSan.
 //
 // A batch is a list of sequences (codes concatenated, seq_off[s] .. seq_off[s + 1]) and a list of pairs of sequence
 // indices.  The planner checks every pair as check_problem (ga_check.h) checks a single problem -- with that pair's
@@ -559,6 +559,92 @@ inline int plan_batch_rank(const uint8_t* codes, const int64_t* seq_off, int64_t
         out.table_off.push_back(table);
         ch.tb_words += w;
         table += e;
+        ch.count++;
+    }
+    if (ch.count > 0) close_chunk();
+    return GA_OK;
+}
+
+// ------------------------------------------------------------------ match support (ga_batch_support)
+// batch_words_kernel fills a chunk's pairs as for ga_batch_count; batch_support_table_kernel keeps N(i, j, 0) of every
+// interior cell in the pair's slice of the chunk's tables (ga_batch_rank.h has the layout), batch_flow_kernel runs the
+// wavefront backwards over the same words and leaves support(i, j) in the same tables, and
+// batch_support_gather_kernel copies it to the pair's m * n dense doubles in the chunk's output (ga_batch_support.hip,
+// DESIGN.md 5.15).
+
+// The dense output of one fill chunk, all its pairs (GA_BATCH_SUPPORT_BYTES overrides): 2 GiB, a quarter of the
+// tables' cap -- a pair's table is at least three times its output.
+constexpr int64_t kSupportBytesCap = 2ll << 30;
+
+struct SupportLimits : CountLimits {
+    int64_t chunk_table_bytes = kRankTableBytesCap;   // as RankLimits's
+    int64_t chunk_support_bytes = kSupportBytesCap;
+};
+
+struct SupportPlan : Plan {
+    int CB = 1;
+    std::vector<ga_batch_words_item> words;  // parallel to `kernel`; tb_off counts from the chunk's start
+    std::vector<int64_t> table_off;          // parallel to `kernel`: the pair's table in its chunk's, in 8-byte entries
+    std::vector<int64_t> support_off;        // parallel to `kernel`: the pair's m * n doubles in its chunk's output
+    std::vector<int64_t> chunk_table;        // parallel to `chunks`: 8-byte entries of the chunk's tables
+    std::vector<int64_t> chunk_support;      // parallel to `chunks`: doubles of the chunk's output
+    std::vector<FillChunk> chunks;           // (launch_first / launch_count unused)
+    int64_t count_rows = 0;                  // as CountPlan's
+};
+
+// plan_batch_count's checks, error order, stripe geometry and routing.  A pair of two letters a side whose own table
+// exceeds lim.chunk_table_bytes, or whose own m * n doubles exceed lim.chunk_support_bytes, is refused, the lowest such
+// pair first.  A chunk closes when its words would exceed lim.chunk_tb_words, its tables lim.chunk_table_bytes or its
+// output lim.chunk_support_bytes; a pair never appears in two chunks.
+inline int plan_batch_support(const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                              const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                              const SupportLimits& lim, SupportPlan& out, std::string& err) {
+    out = SupportPlan();
+    auto fail = [&](int code, const std::string& msg) {
+        err = msg;
+        return code;
+    };
+    CountPlan base;
+    if (int r = plan_batch_count(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim, base, err)) return r;
+    if (npairs == 0) return GA_OK;
+    const int64_t table_cap = std::max<int64_t>(lim.chunk_table_bytes, 0);
+    const int64_t support_cap = std::max<int64_t>(lim.chunk_support_bytes, 0);
+    for (int64_t k = 0; k < npairs; k++) {
+        const int64_t m = seq_off[pair_a[k] + 1] - seq_off[pair_a[k]], n = seq_off[pair_b[k] + 1] - seq_off[pair_b[k]];
+        if (std::min(m, n) < 2) continue;
+        if (rank_table_bytes(m, n) > table_cap)
+            return fail(GA_E_ARG, "pair " + std::to_string(k) + ": count table exceeds the rank table budget");
+        if (m * n * 8 > support_cap)
+            return fail(GA_E_ARG, "pair " + std::to_string(k) + ": support matrix exceeds the support output budget");
+    }
+    static_cast<Plan&>(out) = std::move(static_cast<Plan&>(base));
+    out.CB = base.CB;
+    out.count_rows = base.count_rows;
+    const int64_t words_cap = std::max<int64_t>(lim.chunk_tb_words, 0);
+    FillChunk ch;
+    int64_t table = 0, support = 0;
+    auto close_chunk = [&]() {
+        out.chunks.push_back(ch);
+        out.chunk_table.push_back(table);
+        out.chunk_support.push_back(support);
+    };
+    for (int64_t t = 0; t < (int64_t)out.kernel.size(); t++) {
+        const ga_batch_item& it = out.kernel[(size_t)t];
+        const int64_t w = tb_slice_words(it.m, it.T, it.nstripes, out.CB);
+        const int64_t e = rank_table_entries(it.m, it.T, it.nstripes);
+        const int64_t d = (int64_t)it.m * it.n;
+        if (ch.count > 0 && (ch.tb_words + w > words_cap || (table + e) * 8 > table_cap || (support + d) * 8 > support_cap)) {
+            close_chunk();
+            ch = FillChunk();
+            ch.first = t;
+            table = support = 0;
+        }
+        out.words.push_back(ga_batch_words_item{ch.tb_words, w});
+        out.table_off.push_back(table);
+        out.support_off.push_back(support);
+        ch.tb_words += w;
+        table += e;
+        support += d;
         ch.count++;
     }
     if (ch.count > 0) close_chunk();

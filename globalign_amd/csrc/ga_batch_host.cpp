@@ -1,6 +1,7 @@
 // ga_batch_host.cpp -- the batch engine behind ga_batch_costs, ga_batch_align, ga_batch_sample, ga_batch_count,
-// ga_batch_rank and ga_debug_pair_tables: staging and launches of the batch kernels, the one table stage and the
+// ga_batch_rank, ga_batch_support and ga_debug_pair_tables: staging and launches of the batch kernels, the one table stage and the
 // one decode of the calls with strings.  It reaches the rest of the engine through ga_host_internal.h.
+#include <cmath>
 #include <cstring>
 
 #include "ga_host_internal.h"
@@ -1074,6 +1075,231 @@ static int batch_rank_impl(ga_ctx* c, const uint8_t* codes, const int64_t* seq_o
     return GA_OK;
 }
 
+// ga_batch_support: every pair filled as ga_batch_count fills it; batch_support_table_kernel keeps the
+// doubles N(i, j, 0) in the pair's table, batch_flow_kernel runs the wavefront backwards and leaves support(i, j)
+// there, batch_support_gather_kernel makes the pair's dense rows, and one copy a chunk brings costs, counts and
+// supports back.  No table stage, no RNG and no decode.
+static int batch_support_impl(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                              const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                              const int64_t* support_off, double* support_out, int64_t* cost_out, double* count_out) {
+    if (int r = check_ctx(c)) return r;
+    for (int64_t& x : c->batch_support_info) x = 0;
+    for (float& x : c->batch_support_ms) x = 0.f;
+    if (npairs == 0) return GA_OK;  // an empty batch: no launch
+    if (!support_off || !support_out || !cost_out || !count_out) return fail(GA_E_ARG, "null argument");
+    const int64_t max_waves = batch_max_waves(c);
+    const int W = gabatch::kWavesPerGroup;
+    gabatch::SupportLimits lim;
+    if (c->bk.align_max_cells) lim.max_cells = *c->bk.align_max_cells;
+    if (c->bk.sample_chunk_words) lim.chunk_tb_words = *c->bk.sample_chunk_words;
+    if (c->bk.rank_table_bytes) lim.chunk_table_bytes = *c->bk.rank_table_bytes;
+    if (c->bk.support_bytes) lim.chunk_support_bytes = *c->bk.support_bytes;
+    lim.scratch_rows_cap = gabatch::scratch_rows_cap(max_waves);
+    lim.count_rows_cap = gabatch::count_rows_cap(max_waves);
+    gabatch::SupportPlan plan;
+    std::string why;
+    if (int r = gabatch::plan_batch_support(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim, plan, why))
+        return fail(r, why);
+    auto len_of = [&](int64_t s) { return seq_off[s + 1] - seq_off[s]; };
+    // What left the kernel route is handled from a single-pair fill with stored words or not at all: the lowest pair
+    // that cannot be is refused before anything is launched (ga_batch_count's rule and reasons).
+    {
+        int64_t bad = -1, avail = -1;
+        const char* reason = nullptr;
+        for (const int64_t k : plan.single) {
+            if (bad >= 0 && k > bad) continue;
+            const int64_t m = len_of(pair_a[k]), n = len_of(pair_b[k]);
+            const char* r = nullptr;
+            if (std::min(m, n) < 2) {
+                r = "support needs sequences of at least two letters";
+            } else {
+                if (avail < 0) avail = c->wk.tb_band_rows ? 0 : dev_avail_bytes(c, (int64_t)c->fb.tb.cap);
+                if (gawalk::band_rows(m, n, plan.CB, c->wk, avail) != 0)
+                    r = "traceback words exceed the budget, and support has no banded route";
+                else if (gabatch::needs_scratch(m, n) && m > gabatch::count_rows_cap(W))
+                    r = "edge column exceeds the count scratch";
+            }
+            if (r) bad = k, reason = r;
+        }
+        if (bad >= 0) return fail(GA_E_ARG, "pair " + std::to_string(bad) + ": " + reason);
+    }
+    if (support_off[0] != 0) return fail(GA_E_ARG, "support_off must start at 0");
+    for (int64_t k = 0; k < npairs; k++)
+        if (support_off[k + 1] - support_off[k] < len_of(pair_a[k]) * len_of(pair_b[k]))
+            return fail(GA_E_ARG, "pair " + std::to_string(k) + ": support_off leaves fewer than m * n doubles");
+    if (int r = refuse_slab_single(c, plan.single, "fill")) return r;
+    HIPCHK(c->bm_count.ensure(sizeof(double) * npairs));
+    HIPCHK(c->bm_ticket.ensure(sizeof(unsigned) * 2));
+
+    // The pairs of one fill: their work list, slices and places in the tables and the output on the device, their
+    // words in tb (tb_words u32s, `layout`, `tc`), their tables in bm_table, their dense rows in bm_out.
+    struct Filled {
+        const ga_batch_item* items_dev;
+        const ga_batch_words_item* words_dev;
+        int nitems;
+        const uint32_t* tb;
+        int64_t tb_words;
+        int CB, layout, tc;
+        int64_t table_entries, support_entries, max_cells;
+    };
+    // The N-table, flow and gather launches behind the fill on the context's stream, with the events c->wev[0], c->wev[1],
+    // c->rev[0] and c->rev[1] around them; edge_rows: the HBM edge rows a wave needs (0: none).
+    auto enqueue_support = [&](const Filled& f, int waves, int64_t edge_rows) -> int {
+        if (edge_rows > 0) HIPCHK(c->bc_scratch.ensure(sizeof(double2) * 2 * (size_t)edge_rows * waves));
+        // both tickets start at zero for every chunk
+        HIPCHK(hipMemsetAsync(c->bm_ticket.p, 0, sizeof(unsigned) * 2, c->stream));
+        ga::SupportArgs q{cs->gap_open, f.items_dev, f.words_dev, c->bm_toff.as<int64_t>(), c->bm_ooff.as<int64_t>(), f.nitems,
+                          c->bm_ticket.as<unsigned>(), c->bm_count.as<double>(), (long long)npairs, f.tb,
+                          (long long)f.tb_words, f.tc, c->bm_table.as<unsigned long long>(), (long long)f.table_entries,
+                          c->bm_out.as<double>(), (long long)f.support_entries,
+                          edge_rows > 0 ? c->bc_scratch.as<double2>() : nullptr, (long long)edge_rows};
+        HIPCHK(hipEventRecord(c->wev[0], c->stream));
+        ga::launch_batch_support_table(c->stream, q, f.CB, f.layout, waves);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->wev[1], c->stream));
+        q.ticket = c->bm_ticket.as<unsigned>() + 1;
+        ga::launch_batch_flow(c->stream, q, f.CB, f.layout, waves);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->rev[0], c->stream));
+        ga::launch_batch_support_gather(c->stream, q, f.CB, f.layout, f.max_cells);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->rev[1], c->stream));
+        c->batch_support_info[4]++;
+        return GA_OK;
+    };
+    // the three launches' times of the chunk just waited for, into slots `at` .. `at` + 2
+    auto take_times = [&](int at) -> int {
+        float ms[3] = {0.f, 0.f, 0.f};
+        HIPCHK(hipEventElapsedTime(&ms[0], c->wev[0], c->wev[1]));
+        HIPCHK(hipEventElapsedTime(&ms[1], c->wev[1], c->rev[0]));
+        HIPCHK(hipEventElapsedTime(&ms[2], c->rev[0], c->rev[1]));
+        for (int x = 0; x < 3; x++) c->batch_support_ms[at + x] += ms[x];
+        return GA_OK;
+    };
+    // the lowest pair whose count is not finite: its supports would be 0 * inf
+    int64_t not_finite = -1;
+    // pair: the pair the message names, or -1 where batch_single_pair names it itself
+    auto take_count = [&](double got, int64_t k, int64_t pair) -> int {
+        if (!(got >= 1.0))
+            return fail(GA_E_STATE, (pair >= 0 ? "pair " + std::to_string(pair) + ": " : std::string()) +
+                                        "work item does not fit the support launches");
+        count_out[k] = got;
+        if (!std::isfinite(got) && (not_finite < 0 || k < not_finite)) not_finite = k;
+        return GA_OK;
+    };
+    for (hipEvent_t& e : c->rev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+
+    // the kernel pairs, fill chunk by fill chunk
+    for (size_t ci = 0; ci < plan.chunks.size(); ci++) {
+        const gabatch::FillChunk& ch = plan.chunks[ci];
+        const std::vector<ga_batch_item> items(plan.kernel.begin() + ch.first, plan.kernel.begin() + ch.first + ch.count);
+        BatchStage bs;
+        if (int r = stage_batch(c, codes, seq_off, nseq, npairs, cs, items, plan.scratch_rows, bs)) return r;
+        HIPCHK(c->bs_words.ensure(sizeof(ga_batch_words_item) * items.size()));
+        HIPCHK(c->bm_toff.ensure(sizeof(int64_t) * items.size()));
+        HIPCHK(c->bm_ooff.ensure(sizeof(int64_t) * items.size()));
+        if (c->bs_tb.ensure(sizeof(uint32_t) * (size_t)ch.tb_words) != hipSuccess ||
+            c->bm_table.ensure(sizeof(uint64_t) * (size_t)plan.chunk_table[ci]) != hipSuccess ||
+            c->bm_out.ensure(sizeof(double) * (size_t)plan.chunk_support[ci]) != hipSuccess) {
+            (void)hipStreamSynchronize(c->stream);  // the staged uploads read this call's buffers
+            return fail(GA_E_NOMEM, "no device memory for the batch's traceback words, tables and supports");
+        }
+        HIPCHK(hipMemcpyAsync(c->bs_words.p, plan.words.data() + ch.first, sizeof(ga_batch_words_item) * items.size(),
+                              hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->bm_toff.p, plan.table_off.data() + ch.first, sizeof(int64_t) * items.size(),
+                              hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->bm_ooff.p, plan.support_off.data() + ch.first, sizeof(int64_t) * items.size(),
+                              hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipEventRecord(c->fb.ev[0], c->stream));
+        const ga::WordsArgs q{bs.args, c->bs_words.as<ga_batch_words_item>(), c->bs_tb.as<uint32_t>(),
+                              (long long)ch.tb_words};
+        ga::launch_batch_words(c->stream, q, plan.qbytes, plan.CB, bs.waves);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->fb.ev[1], c->stream));
+        c->batch_support_info[3]++;
+        // (the work list is sorted by cells, largest first)
+        const Filled f{c->bt_items.as<ga_batch_item>(), c->bs_words.as<ga_batch_words_item>(), (int)items.size(),
+                       c->bs_tb.as<uint32_t>(), ch.tb_words, plan.CB, gabatch::LAYOUT_BATCH, 0, plan.chunk_table[ci],
+                       plan.chunk_support[ci], (int64_t)items[0].m * items[0].n};
+        if (int r = enqueue_support(f, bs.waves, plan.count_rows)) return r;
+        std::vector<long long> got((size_t)npairs);
+        std::vector<double> cnt((size_t)npairs), dense((size_t)plan.chunk_support[ci]);
+        HIPCHK(hipMemcpyAsync(got.data(), c->bt_out.p, sizeof(long long) * npairs, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(cnt.data(), c->bm_count.p, sizeof(double) * npairs, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(dense.data(), c->bm_out.p, sizeof(double) * dense.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipEventElapsedTime(&c->fill_ms, c->fb.ev[0], c->fb.ev[1]));
+        c->batch_support_ms[0] += c->fill_ms;
+        if (int r = take_times(1)) return r;
+        if (int r = take_batch_costs(got, items.data(), items.size(), cost_out)) return r;
+        for (size_t t = 0; t < items.size(); t++) {
+            const ga_batch_item& it = items[t];
+            if (int r = take_count(cnt[(size_t)it.out], it.out, it.out)) return r;
+            std::copy_n(dense.data() + plan.support_off[(size_t)ch.first + t], (size_t)it.m * (size_t)it.n,
+                        support_out + support_off[it.out]);
+            c->batch_support_info[5] += gabatch::needs_scratch(it.m, it.n);
+        }
+        c->batch_support_info[0] += (int64_t)items.size();
+        c->batch_support_info[2]++;
+    }
+
+    // A pair that left the kernel route for its size: one single-pair fill with stored words, as ga_batch_count's
+    // large route, then one wave makes its table and its flow from c->fb.tb in that fill's layout.  They go through the
+    // context's problem slot, so no problem is loaded afterwards.
+    for (const int64_t k : plan.single) {
+        const int64_t sa = pair_a[k], sb = pair_b[k];
+        const int64_t m = len_of(sa), n = len_of(sb);
+        c->rc_used = false;
+        auto fill = [&](int64_t, int64_t) -> int {
+            if (band_rows(c) != 0) return fail(GA_E_ARG, "traceback words exceed the budget, and support has no banded route");
+            if (int r = enqueue_fill(c, GA_FILL_TRACEBACK)) return r;
+            if (int r = finish_fill(c, &cost_out[k], nullptr)) return r;
+            c->batch_support_ms[4] += c->fill_ms;
+            c->batch_support_info[3]++;
+            const gaplan::FillPlan& pl = c->plan;
+            const int64_t tb_words = (int64_t)pl.nstripes * pl.T * pl.TC * 256;
+            if ((int64_t)pl.TC * (16 / c->CB) < m || tb_words < gabatch::stripe_words(n, pl.TC))
+                return fail(GA_E_STATE, "the fill's words do not cover the pair");
+            ga_batch_item it{(int32_t)seq_off[sa], (int32_t)m, (int32_t)seq_off[sb], (int32_t)n, 0, (int32_t)k, 0, 0};
+            gabatch::stripe_geometry(n, it.T, it.nstripes);
+            const ga_batch_words_item ws{0, tb_words};
+            const int64_t zero = 0, entries = gabatch::rank_table_entries(m, it.T, it.nstripes);
+            HIPCHK(c->bt_items.ensure(sizeof(ga_batch_item)));
+            HIPCHK(c->bs_words.ensure(sizeof(ga_batch_words_item)));
+            HIPCHK(c->bm_toff.ensure(sizeof(int64_t)));
+            HIPCHK(c->bm_ooff.ensure(sizeof(int64_t)));
+            if (c->bm_table.ensure(sizeof(uint64_t) * (size_t)entries) != hipSuccess ||
+                c->bm_out.ensure(sizeof(double) * (size_t)(m * n)) != hipSuccess)
+                return fail(GA_E_NOMEM, "no device memory for the pair's table and supports");
+            HIPCHK(hipMemcpyAsync(c->bt_items.p, &it, sizeof(it), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->bs_words.p, &ws, sizeof(ws), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->bm_toff.p, &zero, sizeof(zero), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->bm_ooff.p, &zero, sizeof(zero), hipMemcpyHostToDevice, c->stream));
+            const bool hbm = gabatch::needs_scratch(m, n);
+            const Filled f{c->bt_items.as<ga_batch_item>(), c->bs_words.as<ga_batch_words_item>(), 1, c->fb.tb.as<uint32_t>(),
+                           tb_words, c->CB, gabatch::LAYOUT_STRIPE, pl.TC, entries, m * n, m * n};
+            if (int r = enqueue_support(f, W, hbm ? m : 0)) return r;
+            double got = 0.0;
+            HIPCHK(hipMemcpyAsync(&got, c->bm_count.as<double>() + k, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(support_out + support_off[k], c->bm_out.p, sizeof(double) * (size_t)(m * n),
+                                  hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));  // (the uploads' sources live until here)
+            if (int r = take_times(5)) return r;
+            c->batch_support_info[1]++;
+            c->batch_support_info[5] += hbm;
+            return take_count(got, k, -1);
+        };
+        if (int r = batch_single_pair(c, codes, seq_off, pair_a, pair_b, pair_max_cost, cs, k, fill)) return r;
+        c->filled_tb = false;
+    }
+    if (not_finite >= 0)
+        return fail(GA_E_COUNT, "pair " + std::to_string(not_finite) + ": the count of co-optimal alignments is not finite");
+    return GA_OK;
+}
+
+int ga_batch_support_info(ga_ctx* c, int64_t* out8) { return copy_figures(c, &ga_ctx::batch_support_info, out8); }
+int ga_batch_support_timings(ga_ctx* c, float* out8) { return copy_figures(c, &ga_ctx::batch_support_ms, out8); }
 int ga_batch_rank_info(ga_ctx* c, int64_t* out8) { return copy_figures(c, &ga_ctx::batch_rank_info, out8); }
 int ga_batch_rank_timings(ga_ctx* c, float* out8) { return copy_figures(c, &ga_ctx::batch_rank_ms, out8); }
 int ga_batch_count_info(ga_ctx* c, int64_t* out8) { return copy_figures(c, &ga_ctx::batch_count_info, out8); }
@@ -1176,6 +1402,13 @@ int ga_batch_count(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int6
                    int64_t* cost_out, double* count_out) {
     return guard_end(c, batch_count_impl(c, codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, cost_out,
                                          count_out));
+}
+
+int ga_batch_support(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                     const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                     const int64_t* support_off, double* support_out, int64_t* cost_out, double* count_out) {
+    return guard_end(c, batch_support_impl(c, codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, support_off,
+                                           support_out, cost_out, count_out));
 }
 
 int ga_batch_rank(ga_ctx* c, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,

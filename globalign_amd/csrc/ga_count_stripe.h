@@ -1,8 +1,10 @@
 // ga_count_stripe.h -- the stripe loop of the path-count recurrence, one pair by one wave (gfx950): what
 // batch_count_kernel (ga_batch_count.hip) and batch_rank_table_kernel (ga_batch_rank.hip, DESIGN.md
-// 5.14) share.  The number type comes in as a policy: CountF64 adds IEEE doubles and keeps nothing but N(m, n, 0);
-// CountU64Sat adds u64s that saturate at 2^64 - 1 and stores N(i, j, 0 .. 2) of every interior cell to the pair's
-// count table (gabatch::rank_table_index, ga_batch_rank.h).
+// 5.14) share, and batch_support_table_kernel (ga_batch_support.hip).  The number type comes in as a
+// policy: CountF64 adds IEEE doubles and keeps nothing but N(m, n, 0); CountU64Sat adds u64s that saturate at 2^64 - 1
+// and stores N(i, j, 0 .. 2) of every interior cell to the pair's count table (gabatch::rank_table_index,
+// ga_batch_rank.h); CountF64Keep adds as CountF64 does and stores N(i, j, 0), the one plane the flow pass reads, to the
+// same places.
 //
 //   T0 = N(i-1, j-1, 0)   T1 = N(i, j-1, 1)   T2 = N(i-1, j, 2)
 //   N(i, j, L) = sum of T_k over k in S_L(i, j),   N = 1 in row 0 and column 0,   count = N(m, n, 0).
@@ -44,6 +46,8 @@ struct CountU64Sat {
     using Num = unsigned long long;
     using Edge = ulonglong2;
     static constexpr bool kStore = true;
+    static constexpr bool kStoreAll = true;
+    static __device__ __forceinline__ unsigned long long bits(Num x) { return x; }
     static __device__ __forceinline__ Num zero() { return 0ull; }
     static __device__ __forceinline__ Num one() { return 1ull; }
     static __device__ __forceinline__ Num add(Num a, Num b) { return __builtin_elementwise_add_sat(a, b); }
@@ -51,6 +55,14 @@ struct CountU64Sat {
     static __device__ __forceinline__ int lo(Num x) { return (int)(unsigned)x; }
     static __device__ __forceinline__ int hi(Num x) { return (int)(unsigned)(x >> 32); }
     static __device__ __forceinline__ Num join(int h, int l) { return ((Num)(unsigned)h << 32) | (unsigned)l; }
+};
+
+// CountF64's additions, and N(i, j, 0) of every interior cell kept as the double's bits in plane 0 of the cell's
+// entry; planes 1 and 2 are left as they are (batch_flow_kernel puts its result in plane 1)
+struct CountF64Keep : CountF64 {
+    static constexpr bool kStore = true;
+    static constexpr bool kStoreAll = false;
+    static __device__ __forceinline__ unsigned long long bits(Num x) { return (unsigned long long)__double_as_longlong(x); }
 };
 
 // x of the lane to the left (lane 0: `edge`)
@@ -140,11 +152,14 @@ __device__ typename P::Num count_pair(int o, int tc, long long srows, const ga_b
                 const Num n1 = count_terms<P>(sets >> 3, t0, t1, t2);
                 const Num n2 = count_terms<P>(sets >> 6, t0, t1, t2);
                 if constexpr (P::kStore) {
-                    // the step's 3 T stores are 64 consecutive u64 each (a lane off the matrix leaves its hole)
+                    // the step's 3 T (kStoreAll; else T) stores are 64 consecutive u64 each (a lane off the matrix
+                    // leaves its hole)
                     if (act && j0 + lane * T + k + 1 <= n) {
-                        tp[(3 * k + 0) * 64] = n0;
-                        tp[(3 * k + 1) * 64] = n1;
-                        tp[(3 * k + 2) * 64] = n2;
+                        tp[(3 * k + 0) * 64] = P::bits(n0);
+                        if constexpr (P::kStoreAll) {
+                            tp[(3 * k + 1) * 64] = P::bits(n1);
+                            tp[(3 * k + 2) * 64] = P::bits(n2);
+                        }
                     }
                 }
                 t0 = N0[k];  // N(i - 1, this column, 0): the next column's diagonal

@@ -343,6 +343,34 @@ struct RankWalkArgs {
 };
 void launch_batch_rank_table(hipStream_t s, const RankTableArgs& q, int CB, int layout, int waves);
 void launch_batch_rank_walk(hipStream_t s, const RankWalkArgs& q, int CB, int layout, int waves);
+// match support (ga_batch_support; ga_batch_support.hip): batch_support_table_kernel keeps N(i, j, 0) of
+// every interior cell as a double in plane 0 of the pair's table (gabatch::rank_table_index), one wave per pair;
+// batch_flow_kernel, the next launch, runs the wavefront backwards and writes support(i, j) to plane 1;
+// batch_support_gather_kernel copies plane 1 to the pair's dense row-major doubles.  One argument set for the three.
+struct SupportArgs {
+    int o;                               // the gap-open cost (the words' rank test)
+    const ga_batch_item* items;          // the chunk's work list, as the fill had it
+    const ga_batch_words_item* words;    // parallel to items
+    const int64_t* table_off;            // parallel to items: the pair's table in `table`, in 8-byte entries
+    const int64_t* support_off;          // parallel to items: the pair's m * n doubles in `support`
+    int nitems;
+    unsigned* ticket;                    // the launch's own ticket word, zeroed by the host (table and flow: one each)
+    double* count_out;                   // [npairs], indexed by ga_batch_item::out; -1.0: the item does not fit
+    long long npairs;
+    const uint32_t* tb;                  // the words, written by an earlier launch and only read here
+    long long tb_words;
+    int tc;                              // LAYOUT_STRIPE: 16-byte words per lane of the fill that wrote tb
+    unsigned long long* table;           // the chunk's tables
+    long long table_entries;
+    double* support;                     // the chunk's dense output
+    long long support_entries;
+    double2* scratch;                    // [waves][2][scratch_rows] edge columns in HBM (nullptr: no pair needs them)
+    long long scratch_rows;
+};
+void launch_batch_support_table(hipStream_t s, const SupportArgs& q, int CB, int layout, int waves);
+void launch_batch_flow(hipStream_t s, const SupportArgs& q, int CB, int layout, int waves);
+// max_cells: the cells of the launch's largest pair
+void launch_batch_support_gather(hipStream_t s, const SupportArgs& q, int CB, int layout, long long max_cells);
 // the device-routed items' tie-break tables, one wave per item (batch_rng_kernel, ga_batch_rng.hip)
 struct RngArgs {
     const gabrng::Item* items;   // seed, steps and tab_off of each item

@@ -195,6 +195,7 @@ void guard_each(ga_ctx* c, F&& dev, P&& pin) {
     GA_D(bt_rstatus), GA_D(bt_rbase), GA_D(jlut), GA_D(bs_words), GA_D(bs_tb), GA_D(bs_witems), GA_D(bs_ticket);
     GA_D(bc_out), GA_D(bc_ticket), GA_D(bc_scratch);
     GA_D(br_table), GA_D(br_toff), GA_D(br_out), GA_D(br_ranks), GA_D(br_items), GA_D(br_ticket);
+    GA_D(bm_table), GA_D(bm_toff), GA_D(bm_ooff), GA_D(bm_out), GA_D(bm_count), GA_D(bm_ticket);
 #define GA_PP(x) pin(c->pipe.x, #x)
     GA_P(res_pin), GA_P(prog), pin(c->pipe.pin, "pipe_pin"), GA_PP(chain_tab), GA_PP(chain_ctl), GA_PP(chain_io);
     GA_P(rc_ops_pin), GA_P(rc_ops_prog), GA_P(up_pin);

@@ -291,6 +291,12 @@ struct ga_ctx {
     DevBuf br_table, br_toff, br_out, br_ranks, br_items, br_ticket;
     int64_t batch_rank_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     float batch_rank_ms[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    // ga_batch_support fills as ga_batch_count does and adds the chunk's N tables, the pairs' places in
+    // them and in the dense output, that output, the double counts and the table and flow launches' ticket words (the
+    // edge columns go through bc_scratch); ga_batch_support_info's and _timings's figures of its last call
+    DevBuf bm_table, bm_toff, bm_ooff, bm_out, bm_count, bm_ticket;
+    int64_t batch_support_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    float batch_support_ms[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int walk_jump_diag[3] = {0, 0, 0};  // the tie-to-tie walk's trips, region re-checks, ties (result[12..14])
     DevBuf jlut;           // the jump workers' LUT for gap open jlut_o (ga::jump_lut_build)
     int jlut_o = -1;

@@ -1047,7 +1047,7 @@ void test_batch_knobs() {
     for (bool x : {false, true}) {  // (no knob of a dropped path among them: both builds read the same)
         const BatchKnobs kn = parse_knobs<BatchKnobs>({}, x);
         CHECK(!kn.rng_device_default && kn.rng_max_steps == 1024 && kn.rng_cap_words == 48 && kn.rng_threads == 0 && !kn.max_cells &&
-                  !kn.align_max_cells && !kn.sample_chunk_words && !kn.sample_walk_entries && !kn.rank_table_bytes,
+                  !kn.align_max_cells && !kn.sample_chunk_words && !kn.sample_walk_entries && !kn.rank_table_bytes && !kn.support_bytes,
               "GA_BATCH_* defaults");
     }
     const IntKnob<BatchKnobs> knobs[] = {
@@ -1064,14 +1064,15 @@ void test_batch_knobs() {
     for (const Floor& f : {Floor{"GA_BATCH_MAX_CELLS", &BatchKnobs::max_cells, 0}, Floor{"GA_BATCH_ALIGN_MAX_CELLS", &BatchKnobs::align_max_cells, 0},
                            Floor{"GA_BATCH_SAMPLE_CHUNK_WORDS", &BatchKnobs::sample_chunk_words, 1},
                            Floor{"GA_BATCH_SAMPLE_WALK_ENTRIES", &BatchKnobs::sample_walk_entries, 1},
-                           Floor{"GA_BATCH_RANK_TABLE_BYTES", &BatchKnobs::rank_table_bytes, 1}})
+                           Floor{"GA_BATCH_RANK_TABLE_BYTES", &BatchKnobs::rank_table_bytes, 1},
+                           Floor{"GA_BATCH_SUPPORT_BYTES", &BatchKnobs::support_bytes, 1}})
         for (int64_t v : {(int64_t)-7, (int64_t)-1, (int64_t)0, (int64_t)1, (int64_t)2, (int64_t)5000000000LL}) {
             const BatchKnobs kn = parse_knobs<BatchKnobs>({{f.name, std::to_string(v)}});
             const std::optional<int64_t>& got = kn.*f.field;
             CHECK(got && *got == std::max(v, f.floor), "%s=%lld", f.name, (long long)v);
             // each name fills its own field and no other
             int set = 0;
-            for (const auto* o : {&kn.max_cells, &kn.align_max_cells, &kn.sample_chunk_words, &kn.sample_walk_entries, &kn.rank_table_bytes}) set += o->has_value();
+            for (const auto* o : {&kn.max_cells, &kn.align_max_cells, &kn.sample_chunk_words, &kn.sample_walk_entries, &kn.rank_table_bytes, &kn.support_bytes}) set += o->has_value();
             CHECK(set == 1, "%s set %d fields", f.name, set);
         }
 }

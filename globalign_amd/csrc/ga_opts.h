@@ -187,6 +187,7 @@ struct BatchKnobs {
     std::optional<int64_t> sample_chunk_words;         // GA_BATCH_SAMPLE_CHUNK_WORDS, >= 1
     std::optional<int64_t> sample_walk_entries;        // GA_BATCH_SAMPLE_WALK_ENTRIES, >= 1
     std::optional<int64_t> rank_table_bytes;           // GA_BATCH_RANK_TABLE_BYTES, >= 1
+    std::optional<int64_t> support_bytes;              // GA_BATCH_SUPPORT_BYTES, >= 1
     template <typename Get, typename XGet>
     static BatchKnobs parse(Get&& get, XGet&&) {
         BatchKnobs kn;
@@ -199,6 +200,7 @@ struct BatchKnobs {
         if (const char* e = get("GA_BATCH_SAMPLE_CHUNK_WORDS")) kn.sample_chunk_words = std::max<int64_t>(1, atoll(e));
         if (const char* e = get("GA_BATCH_SAMPLE_WALK_ENTRIES")) kn.sample_walk_entries = std::max<int64_t>(1, atoll(e));
         if (const char* e = get("GA_BATCH_RANK_TABLE_BYTES")) kn.rank_table_bytes = std::max<int64_t>(1, atoll(e));
+        if (const char* e = get("GA_BATCH_SUPPORT_BYTES")) kn.support_bytes = std::max<int64_t>(1, atoll(e));
         return kn;
     }
 };

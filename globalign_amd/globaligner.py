@@ -26,7 +26,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _native
-from .results import (AlignmentResults, BatchAlignments, BatchCounts, BatchRanked, BatchSamples, BatchScores,
+from .results import (AlignmentResults, BatchAlignments, BatchCounts, BatchRanked, BatchSamples, BatchScores, BatchSupport,
                       final_cost_to_score)
 from .scoring import MAX_SEQ_LEN_PROD, get_max_val, validate_and_transform_args
 
@@ -220,6 +220,35 @@ class GlobalAligner:
         costs, counts = eng.batch_count(b.codes, b.seq_off, b.pair_a, b.pair_b, b.tables, b.pair_max_cost)
         return BatchCounts(counts, counts < 2.0 ** 53, costs, b.scores(costs), b.scoring_mat, b.costing_mat,
                            b.gap_open_score, b.gap_open_cost)
+
+    def match_support(self, seqs_1, seqs_2):
+        """For every pair and every letter i of seqs_1[k] and letter j of seqs_2[k]: how many of the pair's co-optimal
+        alignments (``count_alignments`` says how many there are) align the two in one column.  ``support[k][i, j] ==
+        counts[k]`` marks a column every co-optimal alignment has, 0 one that none has; ``fraction``, ``core``,
+        ``unaligned_1`` / ``unaligned_2`` and ``column_support`` of the result read the matrix.  The supports are exact
+        integers in float64 where ``exact[k]`` (counts[k] < 2**53) and the same recurrence's doubles above.  They come
+        from one fill of the pair and two passes over its traceback words on the GPU -- the number of paths below every
+        state, then the number of walk prefixes above it -- with no enumeration and no sampling; the process-global
+        ``random`` state is not touched.  Validation and refusals are count_alignments's; a pair whose count is not
+        finite (+inf, past the double range) raises ValueError, the lowest such pair named.
+        -> BatchSupport."""
+        _, b, _ = self._strings_batch("match_support", seqs_1, seqs_2, "host", lambda P: None)
+        if b is None:
+            e = self._empty_batch((0,))
+            return BatchSupport([], np.zeros(0, dtype=np.float64), np.zeros(0, dtype=bool), e.costs, e.scores, [], [],
+                                *e[2:])
+        lens = np.diff(b.seq_off)
+        short = np.flatnonzero(np.minimum(lens[b.pair_a], lens[b.pair_b]) < 2)
+        if short.size:
+            raise ValueError(f"pair {int(short[0])}: match_support needs sequences of at least two letters")
+        eng = _native.default_engine(self.device)
+        costs, counts, offsets, flat = eng.batch_support(b.codes, b.seq_off, b.pair_a, b.pair_b, b.tables, b.pair_max_cost)
+        support = [flat[offsets[k]:offsets[k + 1]].reshape(int(lens[b.pair_a[k]]), int(lens[b.pair_b[k]]))
+                   for k in range(len(b.pair_a))]
+        text = b.text.decode("latin-1")
+        seqs = [text[b.seq_off[s]:b.seq_off[s + 1]] for s in range(len(b.seq_off) - 1)]
+        return BatchSupport(support, counts, counts < 2.0 ** 53, costs, b.scores(costs), [seqs[a] for a in b.pair_a],
+                            [seqs[q] for q in b.pair_b], b.scoring_mat, b.costing_mat, b.gap_open_score, b.gap_open_cost)
 
     def alignments_by_rank(self, seqs_1, seqs_2, ranks):
         """The co-optimal alignments of seqs_1[k] with seqs_2[k] that ``ranks[k]`` names, for every k.  The reference

@@ -238,3 +238,77 @@ class BatchRanked(NamedTuple):
         n = int(self.counts[k])
         r = self.ranks[k]
         return not bool(self.saturated[k]) and len(r) == n and all(int(x) == q for q, x in enumerate(r))
+
+
+class BatchSupport(NamedTuple):
+    """Match support of every pair (GlobalAligner.match_support): support, per pair a numpy float64 array of shape
+    (m, n) whose entry [i, j] is the number of the pair's co-optimal alignments that align letter i of seq_1 with letter
+    j of seq_2 (0-based) in one column; counts, exact, costs and scores as BatchCounts has them -- where exact[k] every
+    support of pair k is an exact integer, above 2**53 it is the recurrence's double; seqs_1, seqs_2: the pairs'
+    upper-cased sequences; and the settings, as BatchScores reports them.  The methods are plain numpy on these."""
+    support: list
+    counts: "numpy.ndarray"
+    exact: "numpy.ndarray"
+    costs: "numpy.ndarray"
+    scores: "numpy.ndarray"
+    seqs_1: list
+    seqs_2: list
+    scoring_mat: dict
+    costing_mat: dict
+    gap_open_score: int
+    gap_open_cost: int
+
+    def count(self, k):
+        """Pair k's count: a Python int when it is exact, else the float."""
+        return int(self.counts[k]) if self.exact[k] else float(self.counts[k])
+
+    def fraction(self, k):
+        """support[k] / counts[k]: per cell the share of the family that has the column."""
+        return self.support[k] / self.counts[k]
+
+    def core(self, k):
+        """The columns every co-optimal alignment of pair k has: an int64 array (r, 2) of the 0-based (i, j) with
+        support == counts[k], in increasing i (and with it j: they lie on one path)."""
+        import numpy as np
+        return np.argwhere(self.support[k] == self.counts[k]).astype(np.int64).reshape(-1, 2)
+
+    def unaligned_1(self, k):
+        """Per letter of seq_1: the number of members in which it faces a gap, counts[k] - support[k].sum(axis=1) (a
+        member has the letter in one column: with one letter of seq_2 or with a gap); an exact integer where
+        exact[k]."""
+        return self.counts[k] - self.support[k].sum(axis=1)
+
+    def unaligned_2(self, k):
+        """Per letter of seq_2: the number of members in which it faces a gap, counts[k] - support[k].sum(axis=0)."""
+        return self.counts[k] - self.support[k].sum(axis=0)
+
+    def column_support(self, k, seq_1_aligned, seq_2_aligned):
+        """Per column of an alignment of pair k (its two lines, gaps as '-'): the fraction of the family that has the
+        column -- fraction(k) at a column of two letters, the unaligned fraction of the letter at a gap column (the
+        share in which that letter faces a gap, wherever the gap lies).  -> float64 array, one entry per column.
+        ValueError if the lines differ in length, have a column of two gaps, or are not, dashes removed, the pair's
+        upper-cased sequences."""
+        import numpy as np
+        a, b = str(seq_1_aligned), str(seq_2_aligned)
+        if len(a) != len(b):
+            raise ValueError("the aligned lines differ in length")
+        if a.replace("-", "") != self.seqs_1[k] or b.replace("-", "") != self.seqs_2[k]:
+            raise ValueError(f"the lines are not an alignment of pair {k}'s sequences")
+        frac = self.fraction(k)
+        gap_1, gap_2 = self.unaligned_1(k) / self.counts[k], self.unaligned_2(k) / self.counts[k]
+        out = np.zeros(len(a), dtype=np.float64)
+        i = j = 0
+        for c, (x, y) in enumerate(zip(a, b)):
+            if x == "-" and y == "-":
+                raise ValueError(f"column {c} holds two gaps")
+            if x == "-":
+                out[c] = gap_2[j]
+                j += 1
+            elif y == "-":
+                out[c] = gap_1[i]
+                i += 1
+            else:
+                out[c] = frac[i, j]
+                i += 1
+                j += 1
+        return out

@@ -29,6 +29,7 @@ extern "C" {
 #define GA_E_TIMEOUT -5  /* a device-side wait exceeded its spin bound      */
 #define GA_E_NOMEM -6    /* device memory too small for the chosen path      */
 #define GA_E_GUARD -7    /* guard mode: bytes outside a buffer were changed   */
+#define GA_E_COUNT -8    /* ga_batch_support: a pair's count is not finite (maps to ValueError) */
 
 /* Python-visible outcome of a traceback (dp_array_backward semantics). */
 #define GA_TB_OK 0
@@ -278,6 +279,43 @@ int ga_batch_rank_info(ga_ctx* ctx, int64_t* out8);
  * single-pair fills ms, batch_rank_table_kernel ms over their pairs} of the last ga_batch_rank, summed over its
  * launches. */
 int ga_batch_rank_timings(ga_ctx* ctx, float* out8);
+/* Match support: for every pair k and every cell (i, j), how
+ * many of the pair's co-optimal alignments (ga_batch_count's family) align
+ * letter i of seq_1 with letter j of seq_2:
+ *   support(i, j) = A_0(i, j) * N(i-1, j-1, 0),
+ * A_0 the number of walk prefixes from (m, n) that leave cell (i, j) by the
+ * diagonal and N the number of paths from the cell they enter on, all in IEEE
+ * double in a fixed order: the exact integer while count_out[k] < 2^53, the
+ * recurrence's double above.  Pair k's m * n doubles go to support_out at
+ * support_off[k], row-major (npairs + 1 entries from 0, at least m * n doubles
+ * a pair); count_out[k] and cost_out[k] are ga_batch_count's.  codes .. costs,
+ * checks, errors ("pair <k>: ...") and refusals are ga_batch_count's.
+ * Kernel pairs are filled chunk by chunk by batch_words_kernel as for
+ * ga_batch_count; batch_support_table_kernel, one wave per pair, keeps N(i, j, 0)
+ * in the pair's table (ga_batch_rank's layout and size), batch_flow_kernel, one
+ * wave per pair, runs the wavefront backwards over the same words and leaves
+ * the supports in the same table, and batch_support_gather_kernel makes the
+ * dense rows; all are later launches on the same stream.  A chunk closes when
+ * its words would exceed GA_BATCH_SAMPLE_CHUNK_WORDS, its tables
+ * GA_BATCH_RANK_TABLE_BYTES or its dense output GA_BATCH_SUPPORT_BYTES (option,
+ * default 2^31: 2 GiB); a pair whose own table or output exceeds its cap is
+ * refused with GA_E_ARG before any launch, the lowest such pair first.  A pair
+ * that leaves the kernel route for its size is filled by the single-pair fill
+ * with stored traceback words and handled by one wave of the same kernels.
+ * After the counts are back, a pair whose count is not finite (+inf: its
+ * supports would be 0 * inf) fails the call with GA_E_COUNT, the lowest such
+ * pair named; the outputs are then unspecified. */
+int ga_batch_support(ga_ctx* ctx, const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                     const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* costs,
+                     const int64_t* support_off, double* support_out, int64_t* cost_out, double* count_out);
+/* out8 = {pairs on the kernel route, pairs filled by the single-pair fill, fill chunks, fill launches
+ * (batch_words_kernel's and single-pair fills), support launch sets (N table, flow, gather), pairs whose edge column
+ * went through HBM, 0, 0} of the last ga_batch_support. */
+int ga_batch_support_info(ga_ctx* ctx, int64_t* out8);
+/* out8 = {batch_words_kernel ms, batch_support_table_kernel ms, batch_flow_kernel ms, batch_support_gather_kernel ms
+ * over those pairs, single-pair fills ms, and the three kernels' ms over their pairs} of the last ga_batch_support,
+ * summed over its launches. */
+int ga_batch_support_timings(ga_ctx* ctx, float* out8);
 /* The tie-break tables alone, with no alignment: item t's steps[t] entries under seeds[t], concatenated in
  * tab_out, by route 1 (host) or 2 (device; an item over GA_BATCH_RNG_DEVICE_MAX_STEPS is built on the host, as
  * in the real call).  status_out[t]: 0 complete, 1 the word cap was reached (entries past the stop are

@@ -34,6 +34,11 @@ JSON line per workload with pairs, cells, ms (median of 5 calls after 2 warm-ups
                                                 the table and walk launches' kernel ms, and count_alignments's count
                                                 launch on the same batch in the same run; B1 once more with the tables'
                                                 cap raised so that it takes one chunk
+    python tools/batch_bench.py --support       B1 cut to the pairs whose dense output fits one chunk's default cap, and
+                                                S3's 10k x 10k pair, through match_support: median,
+                                                least and most of 5 after 2 warm-ups, with the N-table, flow and gather
+                                                launches' kernel ms and count_alignments's count launch on the same
+                                                batch in the same run
 
 Workloads (SplitMix64 sequences of tests.conftest, lengths from a seeded random.Random):
   B1  4096 DNA pairs, lengths 200-400         B2  1024 BLOSUM62 pairs, lengths 100-600
@@ -350,6 +355,57 @@ def rank_workloads():
     run("S3-rank", [(splitmix_seq(10000, 1, "dna"), splitmix_seq(10000, 2, "dna"))], 64)
 
 
+def support_workloads():
+    """B1 cut to the pairs whose dense output fits the default cap of one chunk (2 GiB) and S3's 10k x 10k pair through
+    match_support, with count_alignments on the same batch in the same run: median of REPEATS after WARMUP."""
+    def run(name, pairs):
+        al = GlobalAligner(max_seq_len_prod=None, **DNA)
+        a, b = [p[0] for p in pairs], [p[1] for p in pairs]
+        eng, parts, cparts, last = _native.default_engine(0), [], [], {}
+
+        def call():
+            last["res"] = al.match_support(a, b)
+            parts.append(eng.batch_support_timings())
+
+        def count():
+            al.count_alignments(a, b)
+            cparts.append(eng.batch_count_timings())
+
+        for _ in range(WARMUP):
+            call()
+            count()
+        ms = []
+        for _ in range(REPEATS):
+            t0 = time.perf_counter()
+            call()
+            ms.append((time.perf_counter() - t0) * 1e3)
+            count()
+        parts, cparts, res = parts[-REPEATS:], cparts[-REPEATS:], last["res"]
+        cells = sum(len(x) * len(y) for x, y in pairs)
+        med = {k: round(statistics.median(x[k] for x in parts), 4) for k in parts[0]}
+        cmed = {"count_" + k: round(statistics.median(x[k] for x in cparts), 4) for k in cparts[0]}
+        table_ms, flow_ms = med["table_ms"] + med["single_table_ms"], med["flow_ms"] + med["single_flow_ms"]
+        gather_ms = med["gather_ms"] + med["single_gather_ms"]
+        count_ms = cmed["count_count_ms"] + cmed["count_single_count_ms"]
+        print(json.dumps(dict(workload=name, pairs=len(pairs), cells=cells, ms=round(statistics.median(ms), 4),
+                              ms_min=round(min(ms), 4), ms_max=round(max(ms), 4), **med, **cmed,
+                              table_over_count=round(table_ms / count_ms, 3), flow_over_count=round(flow_ms / count_ms, 3),
+                              table_ns_per_cell=round(table_ms * 1e6 / cells, 4),
+                              flow_ns_per_cell=round(flow_ms * 1e6 / cells, 4),
+                              gather_ns_per_cell=round(gather_ms * 1e6 / cells, 4), info=eng.batch_support_info(),
+                              exact=int(res.exact.sum()),
+                              core_columns=int(sum(len(res.core(k)) for k in range(min(len(pairs), 64)))))), flush=True)
+
+    b1, out_bytes = [], 0
+    for x, y in pairs_of(4096, 200, 400, "dna", 1):
+        if out_bytes + len(x) * len(y) * 8 > (2 << 30):
+            break
+        b1.append((x, y))
+        out_bytes += len(x) * len(y) * 8
+    run("B1-support", b1)
+    run("S3-support", [(splitmix_seq(10000, 1, "dna"), splitmix_seq(10000, 2, "dna"))])
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--loop", type=int, default=0, metavar="K")
@@ -361,8 +417,11 @@ def main():
     ap.add_argument("--sample", action="store_true")
     ap.add_argument("--count", action="store_true")
     ap.add_argument("--rank", action="store_true")
+    ap.add_argument("--support", action="store_true")
     args = ap.parse_args()
-    if args.rank:
+    if args.support:
+        support_workloads()
+    elif args.rank:
         rank_workloads()
     elif args.count:
         count_workloads()
