@@ -2,8 +2,9 @@
 // with strings (ga_batch_align, at the end); no HIP: built into the engine, into the kernels' translation unit for the
 // work-item layout, and into the planner self-tests, ga_batch_selftest.cpp, ga_batch_align_selftest.cpp,
 // ga_batch_sample_selftest.cpp (ga_batch_sample's planner, after ga_batch_align's), ga_batch_count_selftest.cpp
-// (ga_batch_count's, after that), ga_batch_rank_selftest.cpp (ga_batch_rank's, after that) and
-// ga_batch_support_selftest.cpp (ga_batch_support's, at the end), under AddressSanitizer / UBSan.
+// (ga_batch_count's, after that, and what the four stored-words calls share), ga_batch_rank_selftest.cpp
+// (ga_batch_rank's, after that) and ga_batch_support_selftest.cpp (ga_batch_support's, at the end), under
+// AddressSanitizer / UBSan.
 //
 // A batch is a list of sequences (codes concatenated, seq_off[s] .. seq_off[s + 1]) and a list of pairs of sequence
 // indices.  The planner checks every pair as check_problem (ga_check.h) checks a single problem -- with that pair's
@@ -16,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "ga_batch_layout.h"
 #include "ga_batch_rank.h"
 #include "ga_check.h"
 
@@ -239,10 +241,22 @@ inline int plan_batch_align(const uint8_t* codes, const int64_t* seq_off, int64_
 
 }  // namespace gabatch
 
-// ------------------------------------------------------------------ many seeded walks of a pair (ga_batch_sample)
-// The fill of a pair does not depend on the seed, its walk does: batch_words_kernel fills every kernel pair once and
-// keeps its traceback words in a slice of the pair's own, batch_walks_kernel then walks it once per sample, one wave
-// per walk (ga_batch.hip).
+// ------------------------------------------------------------------ the stored-words calls
+// ga_batch_sample, ga_batch_count, ga_batch_rank and ga_batch_support fill alike: the fill of a pair
+// does not depend on what is asked of it, so batch_words_kernel fills every kernel pair once, chunk by chunk, and keeps
+// its traceback words in a slice of the pair's own; the call's kernels, later launches on the same stream, read them:
+//   sample   batch_walks_kernel walks a pair once per sample, one wave per walk (ga_batch.hip);
+//   count    batch_count_kernel counts a pair's co-optimal alignments, one wave per pair (ga_batch_count.hip, 5.13).  A
+//            stripe hands the next one two doubles a row, N(i, edge, 0) and N(i, edge, 1): through the wave's LDS
+//            share while m fits (kLdsEdgeRows rows), else through a ping-pong pair of HBM slices of the wave's own;
+//   rank     batch_rank_table_kernel runs the count recurrence in saturating u64 and keeps every interior cell's three
+//            counts in the pair's slice of the chunk's tables (ga_batch_rank.h has the layout); batch_rank_walk_kernel
+//            walks a pair once per requested rank, one lane per walk (ga_batch_rank.hip, 5.14);
+//   support  batch_support_table_kernel keeps N(i, j, 0) in the same tables, batch_flow_kernel runs the wavefront
+//            backwards over the same words and leaves support(i, j) there, batch_support_gather_kernel copies it to
+//            the pair's m * n dense doubles in the chunk's output (ga_batch_support.hip, 5.15).
+// So they share their limits, the fill side of their plans, one chunker and what the engine asks about the pairs that
+// leave the kernel route.
 
 // What batch_words_kernel needs per pair beyond its ga_batch_item (same index in the chunk's work list).
 struct ga_batch_words_item {
@@ -250,7 +264,7 @@ struct ga_batch_words_item {
     int64_t tb_words;  // its length: tb_slice_words of the pair
 };
 
-// One walk: a sample of a pair.
+// One walk of ga_batch_sample: a sample of a pair.
 struct ga_batch_sample_item {
     int64_t tab_off;  // the sample's m + n tie-break entries in the walk launch's table
     int64_t ops_off;  // its ceil((m + n) / 16) u32 words of packed levels
@@ -258,39 +272,202 @@ struct ga_batch_sample_item {
     int32_t out;      // the sample's flat index (pair order, then sample order): walk results and strings go there
 };
 
+// One walk item of ga_batch_rank: up to 64 consecutive slots of one pair, lane l walking slot `out` + l.
+struct ga_batch_rank_item {
+    int64_t ops_off;  // the item's level words in the walk launch's: slot l at ops_off + l * ceil((m + n) / 16)
+    int32_t fill;     // the pair's index in its chunk's work list
+    int32_t out;      // the first slot's flat index (pair order, then rank order): its rank, and where its strings go
+    int32_t nslots;   // 1 .. 64
+    int32_t res;      // the first slot's place among the walk launch's results
+};
+
 namespace gabatch {
 
 constexpr int64_t kWalkTableEntriesCap = 1ll << 28;  // tie-break entries of one walk launch (1 GiB of u32)
+constexpr int64_t kCountEdgeBytes = 16;              // two doubles a row
+// The tables of one fill chunk, all its pairs: the words' cap.
+constexpr int64_t kRankTableBytesCap = kTbScratchBytesCap;
+// The dense output of one fill chunk, all its pairs: 2 GiB, a quarter of the tables' cap -- a pair's table is at
+// least three times its output.
+constexpr int64_t kSupportBytesCap = 2ll << 30;
 
-struct SampleLimits : AlignLimits {
+// The most rows a wave's count scratch slice may have with `waves` resident waves (two ping-pong slices each).
+inline int64_t count_rows_cap(int64_t waves) {
+    return kScratchBytesCap / (std::max<int64_t>(waves, 1) * 2 * kCountEdgeBytes);
+}
+
+// The limits of the four calls; each reads the ones its planner names.
+struct WordsLimits : AlignLimits {
     // u32 words of traceback scratch of one fill chunk, all its pairs (GA_BATCH_SAMPLE_CHUNK_WORDS overrides)
     int64_t chunk_tb_words = kTbScratchBytesCap / 4;
-    // tie-break entries of one walk launch (GA_BATCH_SAMPLE_WALK_ENTRIES overrides)
+    // of one walk launch: tie-break entries (sample) or steps, m + n a slot (rank); GA_BATCH_SAMPLE_WALK_ENTRIES
     int64_t walk_entries = kWalkTableEntriesCap;
+    int64_t count_rows_cap = 0;                       // most rows of HBM count edge a wave may be given (not sample)
+    int64_t chunk_table_bytes = kRankTableBytesCap;   // rank, support (GA_BATCH_RANK_TABLE_BYTES overrides)
+    int64_t chunk_support_bytes = kSupportBytesCap;   // support (GA_BATCH_SUPPORT_BYTES overrides)
 };
+using SampleLimits = WordsLimits;
+using CountLimits = WordsLimits;
+using RankLimits = WordsLimits;
+using SupportLimits = WordsLimits;
 
-// Walk items [first, first + count) of SamplePlan::walk share one launch; tab_off / ops_off count from its start.
-struct WalkLaunch {
-    int64_t first = 0, count = 0;
-    int64_t tab_entries = 0, ops_words = 0;
-};
-
-// Kernel pairs [first, first + count) of SamplePlan::kernel are filled by one launch, their slices side by side in
-// tb_words u32 words; walk launches [launch_first, launch_first + launch_count) walk them.
+// Kernel pairs [first, first + count) of the plan's `kernel` are filled by one launch, their slices side by side in
+// tb_words u32 words; walk launches [launch_first, launch_first + launch_count) walk them (sample, rank).
 struct FillChunk {
     int64_t first = 0, count = 0;
     int64_t tb_words = 0;
     int64_t launch_first = 0, launch_count = 0;
 };
 
-struct SamplePlan : Plan {
+// The fill side of the four plans.
+struct WordsPlan : Plan {
     int CB = 1;
-    std::vector<ga_batch_words_item> words;   // parallel to `kernel`; tb_off counts from the chunk's start
-    std::vector<ga_batch_sample_item> walk;   // chunk by chunk, pair by pair in work-list order, sample by sample
+    std::vector<ga_batch_words_item> words;  // parallel to `kernel`; tb_off counts from the chunk's start
     std::vector<FillChunk> chunks;
+    int64_t count_rows = 0;  // rows per wave and ping-pong slice of the count's HBM edge (0: none; not sample)
+    // rank, support: the pair's table in its chunk's (parallel to `kernel`) and the chunk's tables (parallel to
+    // `chunks`), in 8-byte entries; support: the same for the pair's m * n doubles in its chunk's dense output
+    std::vector<int64_t> table_off, chunk_table;
+    std::vector<int64_t> support_off, chunk_support;
+};
+using CountPlan = WordsPlan;
+using SupportPlan = WordsPlan;
+
+// Walk items [first, first + count) of SamplePlan::walk share one launch; tab_off / ops_off count from its start.
+struct WalkLaunch {
+    int64_t first = 0, count = 0;
+    int64_t tab_entries = 0, ops_words = 0;
+};
+struct SamplePlan : WordsPlan {
+    std::vector<ga_batch_sample_item> walk;  // chunk by chunk, pair by pair in work-list order, sample by sample
     std::vector<WalkLaunch> launches;
 };
 
+// Walk items [first, first + count) of RankPlan::walk share one launch: `slots` results, ops_words level words.
+struct RankLaunch {
+    int64_t first = 0, count = 0;
+    int64_t slots = 0, steps = 0, ops_words = 0;
+};
+struct RankPlan : WordsPlan {
+    std::vector<ga_batch_rank_item> walk;  // chunk by chunk, pair by pair in work-list order, 64 slots at a time
+    std::vector<RankLaunch> launches;
+};
+
+// plan_batch_align's checks, error order, stripe geometry and routing, a pair's traceback words measured against a
+// fill chunk's cap instead of a wave's share.  count_edge (all but sample): also to `single` goes a pair whose count
+// edge needs HBM rows beyond lim.count_rows_cap, and count_rows is set.  No chunks yet.
+inline int plan_words_routed(const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
+                             const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
+                             const WordsLimits& lim, bool count_edge, WordsPlan& out, std::string& err) {
+    out = WordsPlan();
+    const int CB = cs ? tb_word_bytes(cs->gap_open) : 0;  // (0: plan_batch_routed refuses every pair)
+    const int64_t cap = std::max<int64_t>(lim.chunk_tb_words, 0);
+    Plan base;
+    const int r = plan_batch_routed(
+        codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim,
+        [&](int64_t m, int64_t n, int T, int nstripes) {
+            return std::min(m, n) < 2 || CB == 0 || tb_slice_words(m, T, nstripes, CB) > cap ||
+                   (count_edge && needs_scratch(m, n) && m > lim.count_rows_cap);
+        },
+        base, err);
+    if (r) return r;
+    static_cast<Plan&>(out) = std::move(base);
+    out.CB = std::max(CB, 1);
+    for (const ga_batch_item& it : out.kernel)
+        if (count_edge && needs_scratch(it.m, it.n)) out.count_rows = std::max<int64_t>(out.count_rows, it.m);
+    return GA_OK;
+}
+
+// A further meter of a fill chunk beside its words: what a pair adds to it and the most a chunk may hold (one unit),
+// and where the chunker puts every pair's place in its chunk (parallel to the work list) and every chunk's total.
+struct ChunkMeter {
+    int64_t (*size)(const ga_batch_item&);
+    int64_t cap;
+    std::vector<int64_t>*off, *chunk;
+};
+inline int64_t pair_table_entries(const ga_batch_item& it) { return rank_table_entries(it.m, it.T, it.nstripes); }
+inline int64_t pair_cells(const ga_batch_item& it) { return (int64_t)it.m * it.n; }
+
+// The kernel pairs cut into fill chunks, in work-list order, the one chunk loop of the four planners: a chunk takes
+// pairs while their traceback words stay within `cap` u32 words and every meter within its own cap (a pair's own share
+// of each is within it: the planners' rule; a pair never appears in two chunks); pair t's slice is appended to `words`,
+// and close(chunk) is called for every chunk as it ends.
+template <typename Close>
+inline void plan_fill_chunks(const std::vector<ga_batch_item>& kernel, int CB, int64_t cap,
+                             std::vector<ga_batch_words_item>& words, const std::vector<ChunkMeter>& meters, Close close) {
+    FillChunk ch;
+    words.reserve(words.size() + kernel.size());
+    std::vector<int64_t> sum(meters.size(), 0), add(meters.size(), 0);
+    auto end_chunk = [&]() {
+        for (size_t q = 0; q < meters.size(); q++) meters[q].chunk->push_back(sum[q]);
+        close(ch);
+    };
+    for (int64_t t = 0; t < (int64_t)kernel.size(); t++) {
+        const ga_batch_item& it = kernel[(size_t)t];
+        const int64_t w = tb_slice_words(it.m, it.T, it.nstripes, CB);
+        bool over = ch.tb_words + w > cap;
+        for (size_t q = 0; q < meters.size(); q++) {
+            add[q] = meters[q].size(it);
+            over = over || sum[q] + add[q] > meters[q].cap;
+        }
+        if (ch.count > 0 && over) {
+            end_chunk();
+            ch = FillChunk();
+            ch.first = t;
+            std::fill(sum.begin(), sum.end(), 0);
+        }
+        words.push_back(ga_batch_words_item{ch.tb_words, w});
+        ch.tb_words += w;
+        ch.count++;
+        for (size_t q = 0; q < meters.size(); q++) {
+            meters[q].off->push_back(sum[q]);
+            sum[q] += add[q];
+        }
+    }
+    if (ch.count > 0) end_chunk();
+}
+
+// The slots of the pairs (sample_off, rank_off): pair k has off[k] .. off[k + 1].  name: the array's, nouns: what a
+// slot holds.
+inline int check_slot_offsets(const int64_t* off, int64_t npairs, const char* name, const char* nouns, std::string& err) {
+    auto fail = [&](int code, const std::string& msg) {
+        err = msg;
+        return code;
+    };
+    if (!off) return fail(GA_E_ARG, "null argument");
+    if (off[0] != 0) return fail(GA_E_ARG, std::string(name) + " must start at 0");
+    for (int64_t k = 0; k < npairs; k++)
+        if (off[k + 1] < off[k]) return fail(GA_E_ARG, std::string(name) + " must not decrease");
+    if (off[npairs] > (int64_t)INT32_MAX) return fail(GA_E_RANGE, std::string("a batch holds at most 2^31 - 1 ") + nouns);
+    return GA_OK;
+}
+
+// bytes of the count table of a pair of n columns (its stripe geometry is the fill's)
+inline int64_t rank_table_bytes(int64_t m, int64_t n) {
+    int T = 1, nstripes = 1;
+    stripe_geometry(n, T, nstripes);
+    return rank_table_entries(m, T, nstripes) * 8;
+}
+
+// A pair of two letters a side whose own table exceeds table_cap bytes, or whose own m * n doubles exceed support_cap
+// bytes (rank: no such cap, INT64_MAX), is refused on whatever route, the lowest such pair first.
+inline int check_pair_budgets(const int64_t* seq_off, const int32_t* pair_a, const int32_t* pair_b, int64_t npairs,
+                              int64_t table_cap, int64_t support_cap, std::string& err) {
+    for (int64_t k = 0; k < npairs; k++) {
+        const int64_t m = seq_off[pair_a[k] + 1] - seq_off[pair_a[k]], n = seq_off[pair_b[k] + 1] - seq_off[pair_b[k]];
+        if (std::min(m, n) < 2) continue;
+        const char* why = rank_table_bytes(m, n) > table_cap ? "count table exceeds the rank table budget"
+                          : m * n > support_cap / 8        ? "support matrix exceeds the support output budget"
+                                                           : nullptr;
+        if (why) {
+            err = "pair " + std::to_string(k) + ": " + why;
+            return GA_E_ARG;
+        }
+    }
+    return GA_OK;
+}
+
+// ------------------------------------------------------------------ many seeded walks of a pair (ga_batch_sample)
 // The walk items of one fill's pairs items[0 .. count) -- pair items[t] has the samples sample_off[items[t].out] ..
 // sample_off[items[t].out + 1] and is walk item field `fill` = t -- appended to `walk`, cut into launches of at most
 // walk_entries table entries (a single item above that gets a launch of its own), appended to `launches`.
@@ -316,167 +493,43 @@ inline void plan_walk_launches(const ga_batch_item* items, int64_t count, const 
     if (wl.count > 0) launches.push_back(wl);
 }
 
-// The kernel pairs cut into fill chunks, in work-list order: a chunk takes pairs while their traceback words stay
-// within `cap` u32 words (every pair's own words are within it: the routing's rule); pair t's slice is appended to
-// `words`, and close(chunk) is called for every chunk as it ends.
-template <typename Close>
-inline void plan_fill_chunks(const std::vector<ga_batch_item>& kernel, int CB, int64_t cap,
-                             std::vector<ga_batch_words_item>& words, Close close) {
-    FillChunk ch;
-    for (int64_t t = 0; t < (int64_t)kernel.size(); t++) {
-        const ga_batch_item& it = kernel[(size_t)t];
-        const int64_t w = tb_slice_words(it.m, it.T, it.nstripes, CB);
-        if (ch.count > 0 && ch.tb_words + w > cap) {
-            close(ch);
-            ch = FillChunk();
-            ch.first = t;
-        }
-        words.push_back(ga_batch_words_item{ch.tb_words, w});
-        ch.tb_words += w;
-        ch.count++;
-    }
-    if (ch.count > 0) close(ch);
-}
-
-// plan_batch_align's checks, error order, stripe geometry and routing, a pair's traceback words measured against a
-// fill chunk's cap instead of a wave's share (lim.tb_words_cap is set from lim.chunk_tb_words here).  Pair k has the
-// samples sample_off[k] .. sample_off[k + 1].  A walk launch takes items while their table entries stay within
-// lim.walk_entries (a single item above it gets a launch of its own); a pair's samples may span several walk
-// launches of its chunk, a pair never appears in two chunks.
+// plan_words_routed without the count edge.  Pair k has the samples sample_off[k] .. sample_off[k + 1].  A walk launch
+// takes items while their table entries stay within lim.walk_entries (a single item above it gets a launch of its
+// own); a pair's samples may span several walk launches of its chunk.
 inline int plan_batch_sample(const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
                              const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
                              const int64_t* sample_off, const SampleLimits& lim, SamplePlan& out, std::string& err) {
     out = SamplePlan();
-    auto fail = [&](int code, const std::string& msg) {
-        err = msg;
-        return code;
-    };
-    AlignLimits al = lim;
-    al.tb_words_cap = std::max<int64_t>(lim.chunk_tb_words, 0);
-    AlignPlan base;
-    if (int r = plan_batch_align(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, al, base, err)) return r;
+    WordsPlan base;
+    if (int r = plan_words_routed(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim, false, base, err))
+        return r;
     if (npairs == 0) return GA_OK;
-    if (!sample_off) return fail(GA_E_ARG, "null argument");
-    if (sample_off[0] != 0) return fail(GA_E_ARG, "sample_off must start at 0");
-    for (int64_t k = 0; k < npairs; k++)
-        if (sample_off[k + 1] < sample_off[k]) return fail(GA_E_ARG, "sample_off must not decrease");
-    if (sample_off[npairs] > (int64_t)INT32_MAX) return fail(GA_E_RANGE, "a batch holds at most 2^31 - 1 samples");
-    static_cast<Plan&>(out) = std::move(static_cast<Plan&>(base));
-    out.CB = base.CB;
-    out.words.reserve(out.kernel.size());
+    if (int r = check_slot_offsets(sample_off, npairs, "sample_off", "samples", err)) return r;
+    static_cast<WordsPlan&>(out) = std::move(base);
     auto close_chunk = [&](FillChunk& ch) {
         ch.launch_first = (int64_t)out.launches.size();
         plan_walk_launches(out.kernel.data() + ch.first, ch.count, sample_off, lim.walk_entries, out.walk, out.launches);
         ch.launch_count = (int64_t)out.launches.size() - ch.launch_first;
         out.chunks.push_back(ch);
     };
-    plan_fill_chunks(out.kernel, out.CB, al.tb_words_cap, out.words, close_chunk);
+    plan_fill_chunks(out.kernel, out.CB, std::max<int64_t>(lim.chunk_tb_words, 0), out.words, {}, close_chunk);
     return GA_OK;
 }
 
 // ------------------------------------------------------------------ co-optimal alignment counts (ga_batch_count)
-// batch_words_kernel fills a chunk's pairs as for ga_batch_sample; batch_count_kernel, a later launch on the same
-// stream, then counts every pair's co-optimal alignments from its words, one wave per pair (ga_batch.hip, DESIGN.md
-// 5.13).  A stripe hands the next one two doubles a row, N(i, edge, 0) and N(i, edge, 1): through the wave's LDS share
-// while m fits (kLdsEdgeRows rows), else through a ping-pong pair of HBM slices of the wave's own.
-constexpr int64_t kCountEdgeBytes = 16;  // two doubles a row
-
-// The most rows a wave's count scratch slice may have with `waves` resident waves (two ping-pong slices each).
-inline int64_t count_rows_cap(int64_t waves) {
-    return kScratchBytesCap / (std::max<int64_t>(waves, 1) * 2 * kCountEdgeBytes);
-}
-
-struct CountLimits : AlignLimits {
-    int64_t chunk_tb_words = kTbScratchBytesCap / 4;  // as SampleLimits's
-    int64_t count_rows_cap = 0;                       // most rows of HBM count edge a wave may be given
-};
-
-struct CountPlan : Plan {
-    int CB = 1;
-    std::vector<ga_batch_words_item> words;  // parallel to `kernel`; tb_off counts from the chunk's start
-    std::vector<FillChunk> chunks;           // (launch_first / launch_count unused: a chunk has one count launch)
-    int64_t count_rows = 0;                  // rows per wave and ping-pong slice of the count's HBM edge (0: none)
-};
-
-// plan_batch_sample's fill side: plan_batch_align's checks, error order, stripe geometry and routing with a pair's
-// words measured against a fill chunk's cap, and the same chunks.  Also to `single` goes a pair whose count edge needs
-// HBM rows beyond lim.count_rows_cap.  The caller decides what becomes of `single` (a pair with a one-letter sequence
-// has no count; the others are filled by the single-pair fill).
+// plan_words_routed with the count edge, and plan_batch_sample's chunks.  The caller decides what becomes of `single`
+// (a pair with a one-letter sequence has no count; the others are filled by the single-pair fill).
 inline int plan_batch_count(const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
                             const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
                             const CountLimits& lim, CountPlan& out, std::string& err) {
-    out = CountPlan();
-    const int CB = cs ? tb_word_bytes(cs->gap_open) : 0;  // (0: plan_batch_routed refuses every pair)
-    const int64_t cap = std::max<int64_t>(lim.chunk_tb_words, 0);
-    Plan base;
-    const int r = plan_batch_routed(
-        codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim,
-        [&](int64_t m, int64_t n, int T, int nstripes) {
-            return std::min(m, n) < 2 || CB == 0 || tb_slice_words(m, T, nstripes, CB) > cap ||
-                   (needs_scratch(m, n) && m > lim.count_rows_cap);
-        },
-        base, err);
-    if (r) return r;
-    static_cast<Plan&>(out) = std::move(base);
-    out.CB = std::max(CB, 1);
-    out.words.reserve(out.kernel.size());
-    for (const ga_batch_item& it : out.kernel)
-        if (needs_scratch(it.m, it.n)) out.count_rows = std::max<int64_t>(out.count_rows, it.m);
-    plan_fill_chunks(out.kernel, out.CB, cap, out.words, [&](const FillChunk& ch) { out.chunks.push_back(ch); });
+    if (int r = plan_words_routed(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim, true, out, err))
+        return r;
+    plan_fill_chunks(out.kernel, out.CB, std::max<int64_t>(lim.chunk_tb_words, 0), out.words, {},
+                     [&](const FillChunk& ch) { out.chunks.push_back(ch); });
     return GA_OK;
 }
 
-}  // namespace gabatch
-
 // ------------------------------------------------------------------ co-optimal alignments by rank (ga_batch_rank)
-// batch_words_kernel fills a chunk's pairs as for ga_batch_count; batch_rank_table_kernel, a later launch on the same
-// stream, runs the count recurrence in saturating u64 and keeps every interior cell's three counts in the pair's slice
-// of the chunk's tables (ga_batch_rank.h has the layout); batch_rank_walk_kernel then walks a pair once per requested
-// rank, one lane per walk (ga_batch_rank.hip).
-
-// One walk item: up to 64 consecutive slots of one pair, lane l walking slot `out` + l.
-struct ga_batch_rank_item {
-    int64_t ops_off;  // the item's level words in the walk launch's: slot l at ops_off + l * ceil((m + n) / 16)
-    int32_t fill;     // the pair's index in its chunk's work list
-    int32_t out;      // the first slot's flat index (pair order, then rank order): its rank, and where its strings go
-    int32_t nslots;   // 1 .. 64
-    int32_t res;      // the first slot's place among the walk launch's results
-};
-
-namespace gabatch {
-
-// The tables of one fill chunk, all its pairs (GA_BATCH_RANK_TABLE_BYTES overrides): the words' cap.
-constexpr int64_t kRankTableBytesCap = kTbScratchBytesCap;
-
-struct RankLimits : CountLimits {
-    int64_t chunk_table_bytes = kRankTableBytesCap;
-    int64_t walk_entries = kWalkTableEntriesCap;  // steps (m + n a slot) of one walk launch, as SampleLimits's
-};
-
-// Walk items [first, first + count) of RankPlan::walk share one launch: `slots` results, ops_words level words.
-struct RankLaunch {
-    int64_t first = 0, count = 0;
-    int64_t slots = 0, steps = 0, ops_words = 0;
-};
-
-struct RankPlan : Plan {
-    int CB = 1;
-    std::vector<ga_batch_words_item> words;  // parallel to `kernel`; tb_off counts from the chunk's start
-    std::vector<int64_t> table_off;          // parallel to `kernel`: the pair's table in its chunk's, in u64 entries
-    std::vector<int64_t> chunk_table;        // parallel to `chunks`: u64 entries of the chunk's tables
-    std::vector<FillChunk> chunks;           // launch_first / launch_count index `launches`
-    std::vector<ga_batch_rank_item> walk;    // chunk by chunk, pair by pair in work-list order, 64 slots at a time
-    std::vector<RankLaunch> launches;
-    int64_t count_rows = 0;                  // as CountPlan's
-};
-
-// bytes of the count table of a pair of n columns (its stripe geometry is the fill's)
-inline int64_t rank_table_bytes(int64_t m, int64_t n) {
-    int T = 1, nstripes = 1;
-    stripe_geometry(n, T, nstripes);
-    return rank_table_entries(m, T, nstripes) * 8;
-}
-
 // plan_walk_launches' shape for rank items: the slots rank_off[items[t].out] .. rank_off[items[t].out + 1] of pair
 // items[t] in groups of 64, appended to `walk`, cut into launches of at most walk_entries steps (m + n a slot; a
 // single item above that gets a launch of its own), appended to `launches`.
@@ -506,149 +559,88 @@ inline void plan_rank_launches(const ga_batch_item* items, int64_t count, const 
 }
 
 // plan_batch_count's checks, error order, stripe geometry and routing.  Pair k has the ranks rank_off[k] ..
-// rank_off[k + 1] (none is legal: the pair is filled and counted).  A pair of two letters a side whose own table
-// exceeds lim.chunk_table_bytes is refused, the lowest such pair first.  A chunk closes when either its words would
-// exceed lim.chunk_tb_words or its tables lim.chunk_table_bytes; a pair never appears in two chunks, and a chunk's walk
-// items follow plan_rank_launches.
+// rank_off[k + 1] (none is legal: the pair is filled and counted).  check_pair_budgets' refusal for the tables.  A
+// chunk closes when either its words would exceed lim.chunk_tb_words or its tables lim.chunk_table_bytes; a chunk's
+// walk items follow plan_rank_launches.
 inline int plan_batch_rank(const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
                            const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
                            const int64_t* rank_off, const RankLimits& lim, RankPlan& out, std::string& err) {
     out = RankPlan();
-    auto fail = [&](int code, const std::string& msg) {
-        err = msg;
-        return code;
-    };
-    CountPlan base;
-    if (int r = plan_batch_count(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim, base, err)) return r;
+    WordsPlan base;
+    if (int r = plan_words_routed(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim, true, base, err))
+        return r;
     if (npairs == 0) return GA_OK;
-    if (!rank_off) return fail(GA_E_ARG, "null argument");
-    if (rank_off[0] != 0) return fail(GA_E_ARG, "rank_off must start at 0");
-    for (int64_t k = 0; k < npairs; k++)
-        if (rank_off[k + 1] < rank_off[k]) return fail(GA_E_ARG, "rank_off must not decrease");
-    if (rank_off[npairs] > (int64_t)INT32_MAX) return fail(GA_E_RANGE, "a batch holds at most 2^31 - 1 ranks");
+    if (int r = check_slot_offsets(rank_off, npairs, "rank_off", "ranks", err)) return r;
     const int64_t table_cap = std::max<int64_t>(lim.chunk_table_bytes, 0);
-    for (int64_t k = 0; k < npairs; k++) {
-        const int64_t m = seq_off[pair_a[k] + 1] - seq_off[pair_a[k]], n = seq_off[pair_b[k] + 1] - seq_off[pair_b[k]];
-        if (std::min(m, n) >= 2 && rank_table_bytes(m, n) > table_cap)
-            return fail(GA_E_ARG, "pair " + std::to_string(k) + ": count table exceeds the rank table budget");
-    }
-    static_cast<Plan&>(out) = std::move(static_cast<Plan&>(base));
-    out.CB = base.CB;
-    out.count_rows = base.count_rows;
-    const int64_t words_cap = std::max<int64_t>(lim.chunk_tb_words, 0);
-    FillChunk ch;
-    int64_t table = 0;
-    auto close_chunk = [&]() {
+    if (int r = check_pair_budgets(seq_off, pair_a, pair_b, npairs, table_cap, INT64_MAX, err)) return r;
+    static_cast<WordsPlan&>(out) = std::move(base);
+    auto close_chunk = [&](FillChunk& ch) {
         ch.launch_first = (int64_t)out.launches.size();
         plan_rank_launches(out.kernel.data() + ch.first, ch.count, rank_off, lim.walk_entries, out.walk, out.launches);
         ch.launch_count = (int64_t)out.launches.size() - ch.launch_first;
         out.chunks.push_back(ch);
-        out.chunk_table.push_back(table);
     };
-    for (int64_t t = 0; t < (int64_t)out.kernel.size(); t++) {
-        const ga_batch_item& it = out.kernel[(size_t)t];
-        const int64_t w = tb_slice_words(it.m, it.T, it.nstripes, out.CB);
-        const int64_t e = rank_table_entries(it.m, it.T, it.nstripes);
-        if (ch.count > 0 && (ch.tb_words + w > words_cap || (table + e) * 8 > table_cap)) {
-            close_chunk();
-            ch = FillChunk();
-            ch.first = t;
-            table = 0;
-        }
-        out.words.push_back(ga_batch_words_item{ch.tb_words, w});
-        out.table_off.push_back(table);
-        ch.tb_words += w;
-        table += e;
-        ch.count++;
-    }
-    if (ch.count > 0) close_chunk();
+    plan_fill_chunks(out.kernel, out.CB, std::max<int64_t>(lim.chunk_tb_words, 0), out.words,
+                     {{pair_table_entries, table_cap / 8, &out.table_off, &out.chunk_table}}, close_chunk);
     return GA_OK;
 }
 
 // ------------------------------------------------------------------ match support (ga_batch_support)
-// batch_words_kernel fills a chunk's pairs as for ga_batch_count; batch_support_table_kernel keeps N(i, j, 0) of every
-// interior cell in the pair's slice of the chunk's tables (ga_batch_rank.h has the layout), batch_flow_kernel runs the
-// wavefront backwards over the same words and leaves support(i, j) in the same tables, and
-// batch_support_gather_kernel copies it to the pair's m * n dense doubles in the chunk's output (ga_batch_support.hip,
-// DESIGN.md 5.15).
-
-// The dense output of one fill chunk, all its pairs (GA_BATCH_SUPPORT_BYTES overrides): 2 GiB, a quarter of the
-// tables' cap -- a pair's table is at least three times its output.
-constexpr int64_t kSupportBytesCap = 2ll << 30;
-
-struct SupportLimits : CountLimits {
-    int64_t chunk_table_bytes = kRankTableBytesCap;   // as RankLimits's
-    int64_t chunk_support_bytes = kSupportBytesCap;
-};
-
-struct SupportPlan : Plan {
-    int CB = 1;
-    std::vector<ga_batch_words_item> words;  // parallel to `kernel`; tb_off counts from the chunk's start
-    std::vector<int64_t> table_off;          // parallel to `kernel`: the pair's table in its chunk's, in 8-byte entries
-    std::vector<int64_t> support_off;        // parallel to `kernel`: the pair's m * n doubles in its chunk's output
-    std::vector<int64_t> chunk_table;        // parallel to `chunks`: 8-byte entries of the chunk's tables
-    std::vector<int64_t> chunk_support;      // parallel to `chunks`: doubles of the chunk's output
-    std::vector<FillChunk> chunks;           // (launch_first / launch_count unused)
-    int64_t count_rows = 0;                  // as CountPlan's
-};
-
-// plan_batch_count's checks, error order, stripe geometry and routing.  A pair of two letters a side whose own table
-// exceeds lim.chunk_table_bytes, or whose own m * n doubles exceed lim.chunk_support_bytes, is refused, the lowest such
-// pair first.  A chunk closes when its words would exceed lim.chunk_tb_words, its tables lim.chunk_table_bytes or its
-// output lim.chunk_support_bytes; a pair never appears in two chunks.
+// plan_batch_count's checks, error order, stripe geometry and routing.  check_pair_budgets' refusals for the tables
+// and the output.  A chunk closes when its words would exceed lim.chunk_tb_words, its tables lim.chunk_table_bytes or
+// its output lim.chunk_support_bytes.
 inline int plan_batch_support(const uint8_t* codes, const int64_t* seq_off, int64_t nseq, const int32_t* pair_a,
                               const int32_t* pair_b, const int32_t* pair_max_cost, int64_t npairs, const ga_costs* cs,
                               const SupportLimits& lim, SupportPlan& out, std::string& err) {
     out = SupportPlan();
-    auto fail = [&](int code, const std::string& msg) {
-        err = msg;
-        return code;
-    };
-    CountPlan base;
-    if (int r = plan_batch_count(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim, base, err)) return r;
+    WordsPlan base;
+    if (int r = plan_words_routed(codes, seq_off, nseq, pair_a, pair_b, pair_max_cost, npairs, cs, lim, true, base, err))
+        return r;
     if (npairs == 0) return GA_OK;
     const int64_t table_cap = std::max<int64_t>(lim.chunk_table_bytes, 0);
     const int64_t support_cap = std::max<int64_t>(lim.chunk_support_bytes, 0);
-    for (int64_t k = 0; k < npairs; k++) {
-        const int64_t m = seq_off[pair_a[k] + 1] - seq_off[pair_a[k]], n = seq_off[pair_b[k] + 1] - seq_off[pair_b[k]];
-        if (std::min(m, n) < 2) continue;
-        if (rank_table_bytes(m, n) > table_cap)
-            return fail(GA_E_ARG, "pair " + std::to_string(k) + ": count table exceeds the rank table budget");
-        if (m * n * 8 > support_cap)
-            return fail(GA_E_ARG, "pair " + std::to_string(k) + ": support matrix exceeds the support output budget");
-    }
-    static_cast<Plan&>(out) = std::move(static_cast<Plan&>(base));
-    out.CB = base.CB;
-    out.count_rows = base.count_rows;
-    const int64_t words_cap = std::max<int64_t>(lim.chunk_tb_words, 0);
-    FillChunk ch;
-    int64_t table = 0, support = 0;
-    auto close_chunk = [&]() {
-        out.chunks.push_back(ch);
-        out.chunk_table.push_back(table);
-        out.chunk_support.push_back(support);
-    };
-    for (int64_t t = 0; t < (int64_t)out.kernel.size(); t++) {
-        const ga_batch_item& it = out.kernel[(size_t)t];
-        const int64_t w = tb_slice_words(it.m, it.T, it.nstripes, out.CB);
-        const int64_t e = rank_table_entries(it.m, it.T, it.nstripes);
-        const int64_t d = (int64_t)it.m * it.n;
-        if (ch.count > 0 && (ch.tb_words + w > words_cap || (table + e) * 8 > table_cap || (support + d) * 8 > support_cap)) {
-            close_chunk();
-            ch = FillChunk();
-            ch.first = t;
-            table = support = 0;
-        }
-        out.words.push_back(ga_batch_words_item{ch.tb_words, w});
-        out.table_off.push_back(table);
-        out.support_off.push_back(support);
-        ch.tb_words += w;
-        table += e;
-        support += d;
-        ch.count++;
-    }
-    if (ch.count > 0) close_chunk();
+    if (int r = check_pair_budgets(seq_off, pair_a, pair_b, npairs, table_cap, support_cap, err)) return r;
+    out = std::move(base);
+    plan_fill_chunks(out.kernel, out.CB, std::max<int64_t>(lim.chunk_tb_words, 0), out.words,
+                     {{pair_table_entries, table_cap / 8, &out.table_off, &out.chunk_table},
+                      {pair_cells, support_cap / 8, &out.support_off, &out.chunk_support}},
+                     [&](const FillChunk& ch) { out.chunks.push_back(ch); });
     return GA_OK;
+}
+
+// ------------------------------------------------------------------ the pairs that left the kernel route
+// What the engine decides about a pair of plan.single of ga_batch_count, _rank and _support before anything is
+// launched: empty, or why the pair cannot be handled.  band: gawalk::band_rows of the pair on this device (0: its
+// stored words fit the budget); rows_cap: count_rows_cap of the one workgroup that handles such a pair; subject and
+// activity word the call ("count needs" / "counting", "ranks need" / "ranking", "support needs" / "support").
+inline std::string no_band_reason(const char* activity) {
+    return std::string("traceback words exceed the budget, and ") + activity + " has no banded route";
+}
+inline std::string single_pair_verdict(int64_t m, int64_t n, int64_t band, int64_t rows_cap, const char* subject,
+                                       const char* activity) {
+    if (std::min(m, n) < 2) return std::string(subject) + " sequences of at least two letters";
+    if (band != 0) return no_band_reason(activity);
+    if (needs_scratch(m, n) && m > rows_cap) return "edge column exceeds the count scratch";
+    return std::string();
+}
+
+// The one-pair work list of the large route: pair k (m x n, codes at a_off / b_off) filled by the single-pair engine
+// with stored words at TC 16-byte words per lane, nstripes * T stripes of 64 columns and CB bytes a word, as the four
+// calls' kernels take it under LAYOUT_STRIPE: the pair's own stripe geometry (the count, table and support kernels
+// read it; where a word lies comes from TC), its codes' places (batch_walks_kernel reads them) and one slice, the
+// fill's words.  nullptr, or the refusal.
+struct LargeWork {
+    ga_batch_item item;
+    ga_batch_words_item words;  // {0, tb_words}
+};
+inline const char* large_route_work(int64_t m, int64_t n, int64_t k, int64_t a_off, int64_t b_off, int nstripes, int T,
+                                    int TC, int CB, LargeWork& out) {
+    const int64_t tb_words = (int64_t)nstripes * T * TC * 256;
+    if ((int64_t)TC * (16 / CB) < m || tb_words < stripe_words(n, TC)) return "the fill's words do not cover the pair";
+    out.item = ga_batch_item{(int32_t)a_off, (int32_t)m, (int32_t)b_off, (int32_t)n, 0, (int32_t)k, 0, 0};
+    stripe_geometry(n, out.item.T, out.item.nstripes);
+    out.words = ga_batch_words_item{0, tb_words};
+    return nullptr;
 }
 
 }  // namespace gabatch

@@ -1,6 +1,7 @@
 // ga_batch_count_selftest.cpp -- CPU self-test of the host's share of ga_batch_count: the count planner (ga_batch.h
-// plan_batch_count: plan_batch_sample's fill side plus the count launch's edge scratch) and the CPU model of the count
-// recurrence (ga_batch_count.h), in double against 128-bit integers and against a walk of every path, plain and under
+// plan_batch_count: plan_batch_sample's fill side plus the count launch's edge scratch), what the four stored-words
+// calls share (the chunker's meters, the large route's work list, the verdict on a pair of `single`) and the CPU model
+// of the count recurrence (ga_batch_count.h), in double against 128-bit integers and against a walk of every path, plain and under
 // AddressSanitizer + UndefinedBehaviorSanitizer (make -C globalign_amd/csrc batch_count_selftest batch_count_asan; run
 // by tests/test_batch_count_host.py).  No HIP: the kernel is tested on the GPU.
 #include <cmath>
@@ -151,25 +152,32 @@ void check_plan(const Batch& b, const Tables& t, const CountLimits& lim, const C
     }
 }
 
+// Round `round` of the random batches: its gap open cost (one-, two- and four-byte words in turn), its pairs into b
+// and its limits.
+int round_gap_open(int round) { return round % 3 == 0 ? 4 : round % 3 == 1 ? 30 : 200; }
+CountLimits random_round(std::mt19937& rng, int round, Batch& b) {
+    const int npairs = 1 + (int)(rng() % 40);
+    for (int k = 0; k < npairs; k++) {
+        // one-letter sequences now and then, and pairs tall and wide enough for an HBM edge column
+        auto len = [&](int max_len) { return rng() % 9 == 0 ? 1 : 2 + (int64_t)(rng() % (unsigned)(max_len - 1)); };
+        if (rng() % 6 == 0) b.add(len(3000), len(1200), rng);
+        else b.add(len(300), len(700), rng);
+    }
+    CountLimits lim = wide_limits();
+    if (round % 2) {
+        lim.max_cells = 1 + (int64_t)(rng() % 2000000);
+        lim.chunk_tb_words = 64 + (int64_t)(rng() % 400000);
+    }
+    if (round % 4 == 3) lim.count_rows_cap = 1100 + (int64_t)(rng() % 1500);
+    return lim;
+}
+
 void test_random_batches() {
     std::mt19937 rng(13);
     for (int round = 0; round < 200; round++) {
-        const int open = round % 3 == 0 ? 4 : round % 3 == 1 ? 30 : 200;  // one-, two- and four-byte words
-        Tables t(5, 5, 3, open);
+        Tables t(5, 5, 3, round_gap_open(round));
         Batch b;
-        const int npairs = 1 + (int)(rng() % 40);
-        for (int k = 0; k < npairs; k++) {
-            // one-letter sequences now and then, and pairs tall and wide enough for an HBM edge column
-            auto len = [&](int max_len) { return rng() % 9 == 0 ? 1 : 2 + (int64_t)(rng() % (unsigned)(max_len - 1)); };
-            if (rng() % 6 == 0) b.add(len(3000), len(1200), rng);
-            else b.add(len(300), len(700), rng);
-        }
-        CountLimits lim = wide_limits();
-        if (round % 2) {
-            lim.max_cells = 1 + (int64_t)(rng() % 2000000);
-            lim.chunk_tb_words = 64 + (int64_t)(rng() % 400000);
-        }
-        if (round % 4 == 3) lim.count_rows_cap = 1100 + (int64_t)(rng() % 1500);
+        const CountLimits lim = random_round(rng, round, b);
         CountPlan p;
         std::string err;
         CHECK(plan(b, t, lim, p, err) == GA_OK, "round %d: plan failed: %s", round, err.c_str());
@@ -244,6 +252,111 @@ void test_errors() {
     one.pb = {1};
     CHECK(plan(one, t, wide_limits(), p, err) == GA_OK && p.single == std::vector<int64_t>{0} && p.kernel.empty(),
           "a one-letter sequence goes to the single list");
+}
+
+// ------------------------------------------------------------------ what the four stored-words calls share
+// plan_fill_chunks with one and two meters beside the words, over test_random_batches' batches (its seed)
+void test_chunker_meters() {
+    std::mt19937 rng(13), caps(29);
+    for (int round = 0; round < 200; round++) {
+        Tables t(5, 5, 3, round_gap_open(round));
+        Batch b;
+        const CountLimits lim = random_round(rng, round, b);
+        CountPlan p;
+        std::string err;
+        CHECK(plan(b, t, lim, p, err) == GA_OK, "round %d: plan failed: %s", round, err.c_str());
+        for (int nmeters = 1; nmeters <= 2; nmeters++) {
+            // caps that a lone pair may exceed, now and then
+            const int64_t cap[3] = {lim.chunk_tb_words, 1000 + (int64_t)(caps() % 3000000), 100 + (int64_t)(caps() % 600000)};
+            int64_t (*const size[3])(const ga_batch_item&) = {nullptr, pair_table_entries, pair_cells};
+            std::vector<ga_batch_words_item> words;
+            std::vector<int64_t> off[3], total[3];
+            std::vector<FillChunk> chunks;
+            std::vector<ChunkMeter> meters;
+            for (int q = 1; q <= nmeters; q++) meters.push_back(ChunkMeter{size[q], cap[q], &off[q], &total[q]});
+            plan_fill_chunks(p.kernel, p.CB, cap[0], words, meters, [&](const FillChunk& ch) { chunks.push_back(ch); });
+            auto add = [&](int q, int64_t at) {
+                const ga_batch_item& it = p.kernel[(size_t)at];
+                return q == 0 ? tb_slice_words(it.m, it.T, it.nstripes, p.CB) : size[q](it);
+            };
+            CHECK(words.size() == p.kernel.size(), "round %d: one slice per pair", round);
+            int64_t next_pair = 0;
+            for (size_t c = 0; c < chunks.size(); c++) {
+                const FillChunk& ch = chunks[c];
+                CHECK(ch.first == next_pair && ch.count > 0, "round %d: chunks follow each other", round);
+                next_pair = ch.first + ch.count;
+                bool next_over = false;
+                for (int q = 0; q <= nmeters; q++) {
+                    CHECK(q == 0 || (off[q].size() == p.kernel.size() && total[q].size() == chunks.size()),
+                          "round %d: meter %d has a place per pair and a total per chunk", round, q);
+                    int64_t sum = 0;
+                    for (int64_t at = ch.first; at < next_pair; at++) {
+                        const int64_t place = q == 0 ? words[(size_t)at].tb_off : off[q][(size_t)at];
+                        CHECK(place == sum, "round %d: meter %d, pair %lld sits at the running sum", round, q, (long long)at);
+                        sum += add(q, at);
+                    }
+                    CHECK(sum == (q == 0 ? ch.tb_words : total[q][c]), "round %d: meter %d, chunk %zu's total", round, q, c);
+                    CHECK(sum <= cap[q] || ch.count == 1, "round %d: meter %d, chunk %zu within the cap", round, q, c);
+                    if (c + 1 < chunks.size()) next_over = next_over || sum + add(q, next_pair) > cap[q];
+                }
+                CHECK(c + 1 == chunks.size() || next_over, "round %d: chunk %zu closed for a cap", round, c);
+            }
+            CHECK(next_pair == (int64_t)p.kernel.size(), "round %d: every pair sits in a chunk", round);
+        }
+    }
+}
+
+// large_route_work: the one-pair work list over a single-pair fill's words
+void test_large_route_work() {
+    for (const int CB : {1, 2, 4}) {
+        const int spc = 16 / CB, TC = 7;
+        const int64_t m = (int64_t)TC * spc, n = 130, k = 5;  // three stripes of 64 columns
+        LargeWork w;
+        CHECK(large_route_work(m, n, k, 11, 22, 1, 3, TC, CB, w) == nullptr, "CB %d: TC * (16 / CB) == m is covered", CB);
+        int T, ns;
+        stripe_geometry(n, T, ns);
+        CHECK(w.item.a_off == 11 && w.item.m == m && w.item.b_off == 22 && w.item.n == n && w.item.big == 0 && w.item.out == k &&
+                  w.item.T == T && w.item.nstripes == ns, "CB %d: the item is the pair with its own geometry", CB);
+        CHECK(w.words.tb_off == 0 && w.words.tb_words == 3 * TC * 256 && w.words.tb_words == stripe_words(n, TC),
+              "CB %d: one slice, the fill's words, exactly stripe_words", CB);
+        const std::string refusal = "the fill's words do not cover the pair";
+        const char* why = large_route_work(m + 1, n, k, 11, 22, 1, 3, TC, CB, w);
+        CHECK(why && why == refusal, "CB %d: TC * (16 / CB) == m - 1 is refused", CB);
+        // (the words come in stripes of TC * 256: the nearest shortfall is one stripe)
+        why = large_route_work(m, n, k, 11, 22, 1, 2, TC, CB, w);
+        CHECK(why && why == refusal, "CB %d: a stripe fewer than stripe_words is refused", CB);
+        CHECK(large_route_work(m, 128, k, 0, 0, 2, 1, TC, CB, w) == nullptr && w.words.tb_words == stripe_words(128, TC) &&
+                  large_route_work(m, 129, k, 0, 0, 2, 1, TC, CB, w) != nullptr, "CB %d: the last covered column", CB);
+        // a wide pair: the fill's stripes of 64 columns, the item's of 64 * T
+        CHECK(large_route_work(m, 1000, k, 0, 0, 4, 4, TC, CB, w) == nullptr && w.item.T == 8 && w.item.nstripes == 2 &&
+                  w.words.tb_words == 16 * TC * 256, "CB %d: a two-stripe item over sixteen fill stripes", CB);
+    }
+}
+
+// single_pair_verdict: each reason, their precedence, and the calls' words
+void test_single_pair_verdict() {
+    const int64_t cap = count_rows_cap(kWavesPerGroup);
+    const char* words[3][2] = {{"count needs", "counting"}, {"ranks need", "ranking"}, {"support needs", "support"}};
+    const std::string short_seq[3] = {"count needs sequences of at least two letters", "ranks need sequences of at least two letters",
+                                      "support needs sequences of at least two letters"};
+    const std::string no_band[3] = {"traceback words exceed the budget, and counting has no banded route",
+                                    "traceback words exceed the budget, and ranking has no banded route",
+                                    "traceback words exceed the budget, and support has no banded route"};
+    const std::string edge = "edge column exceeds the count scratch";
+    for (int q = 0; q < 3; q++) {
+        auto verdict = [&](int64_t m, int64_t n, int64_t band, int64_t rows_cap) {
+            return single_pair_verdict(m, n, band, rows_cap, words[q][0], words[q][1]);
+        };
+        CHECK(verdict(50, 60, 0, cap).empty() && verdict(2, 2, 0, cap).empty(), "call %d: a pair that can be handled", q);
+        CHECK(verdict(1, 60, 0, cap) == short_seq[q] && verdict(60, 1, 0, cap) == short_seq[q], "call %d: one letter", q);
+        CHECK(verdict(50, 60, 256, cap) == no_band[q] && no_band_reason(words[q][1]) == no_band[q], "call %d: banded", q);
+        // an edge column in HBM (more than 512 columns, more than 1024 rows) beyond the cap, and at it
+        CHECK(verdict(2000, 600, 0, 1999) == edge && verdict(2000, 600, 0, 2000).empty(), "call %d: the edge's cap", q);
+        CHECK(verdict(2000, 512, 0, 10).empty() && verdict(1024, 600, 0, 10).empty(), "call %d: no HBM edge, no cap", q);
+        CHECK(verdict(1, 600, 256, 0) == short_seq[q], "call %d: one letter comes first", q);
+        CHECK(verdict(2000, 600, 256, 10) == no_band[q], "call %d: the band comes before the edge", q);
+    }
+    CHECK(cap > 3000, "one workgroup's count scratch holds tall pairs (%lld rows)", (long long)cap);
 }
 
 // ------------------------------------------------------------------ the recurrence
@@ -325,6 +438,9 @@ int main() {
     test_random_batches();
     test_forced_routes();
     test_errors();
+    test_chunker_meters();
+    test_large_route_work();
+    test_single_pair_verdict();
     test_model();
     if (failures) {
         std::fprintf(stderr, "%d checks failed\n", failures);

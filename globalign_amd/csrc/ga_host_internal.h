@@ -274,24 +274,26 @@ struct ga_ctx {
     bool rbase_ready = false;
     hipEvent_t rev[2] = {nullptr, nullptr};  // (created with the first generator launch)
     int32_t batch_rng_info[4] = {0, 0, 0, 0};  // device-routed items, host-routed items, fell back, generator blocks
-    // ga_batch_sample adds the pairs' slices (ga_batch_words_item), the chunk's traceback words, a
-    // walk launch's items and the walks' own ticket word; ga_batch_sample_info's and _timings's figures of its last call
+    // The stored-words fill (ga_batch_host.cpp enqueue_chunk_fill, large_route) adds the pairs' slices
+    // (ga_batch_words_item) and the chunk's traceback words, for ga_batch_sample, _count, _rank and _support alike;
+    // ga_batch_sample a walk launch's items and the walks' own ticket word, and ga_batch_sample_info's and _timings's
+    // figures of its last call
     DevBuf bs_words, bs_tb, bs_witems, bs_ticket;
     int64_t batch_sample_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     float batch_sample_ms[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    // ga_batch_count fills as ga_batch_sample does and adds the counts, the count launch's own ticket
+    // ga_batch_count adds, behind that fill, the counts, the count launch's own ticket
     // word and the waves' HBM edge columns of doubles; ga_batch_count_info's and _timings's figures of its last call
     DevBuf bc_out, bc_ticket, bc_scratch;
     int64_t batch_count_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     float batch_count_ms[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    // ga_batch_rank fills as ga_batch_count does and adds the chunk's count tables and the pairs'
+    // ga_batch_rank adds, behind that fill, the chunk's count tables and the pairs'
     // places in them, the u64 counts, the call's ranks, a walk launch's items and the two launches' ticket word (the
     // edge columns go through bc_scratch, the walks' results and level words through bt_walk and bt_ops);
     // ga_batch_rank_info's and _timings's figures of its last call
     DevBuf br_table, br_toff, br_out, br_ranks, br_items, br_ticket;
     int64_t batch_rank_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     float batch_rank_ms[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    // ga_batch_support fills as ga_batch_count does and adds the chunk's N tables, the pairs' places in
+    // ga_batch_support adds, behind that fill, the chunk's N tables, the pairs' places in
     // them and in the dense output, that output, the double counts and the table and flow launches' ticket words (the
     // edge columns go through bc_scratch); ga_batch_support_info's and _timings's figures of its last call
     DevBuf bm_table, bm_toff, bm_ooff, bm_out, bm_count, bm_ticket;
